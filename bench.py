@@ -10,6 +10,10 @@ RCCL all-gather of the images per step.  `python bench.py --gpus N` launches its
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`) when it is not already
 running under a launcher, and fails loudly when fewer than N devices are visible.
 Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times --steps steps and prints the line (metric, value, ms_per_step, dtype); `--full` adds
+everything else this file measures or checks: the roofline step, the other conv arithmetics, the reduced-precision modes, the
+other BASELINE workloads, the CPU baseline and the parity check against the oracle.  `--dump-outputs DIR` writes the images of
+the last timed step as DIR/images.npy (float32; a fixed, seeded sample of the images when they exceed 64 MB).
 """
 from __future__ import annotations
 
@@ -25,6 +29,7 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parent
 sys.path.insert(0, str(ROOT))
 
+import numpy as np
 import torch
 
 PEAK_FP32_TFLOPS = 157.3           # MI355X fp32 matrix/vector peak (MI355X_MICROARCH.md): SURVEY §8(d)'s denominator for the ALGORITHMIC flops
@@ -236,6 +241,20 @@ def pmc_match(by_name, kernel):
     return None
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, img):
+    """DIR/images.npy: the images of the last timed step, float32 [n, 3, H, W]; beyond DUMP_BYTES a fixed, seeded choice of whole images
+    (rows in ascending order), so that two builds run with the same arguments write the same rows"""
+    a = img.detach().float().cpu().numpy()
+    n_max = max(1, DUMP_BYTES // (a.nbytes // a.shape[0]))
+    if a.shape[0] > n_max:
+        a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], n_max, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "images.npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -252,7 +271,10 @@ def main():
     ap.add_argument("--alt-precision", type=int, default=None, choices=sorted(ARITH), help="also time the same step on this arithmetic (default: the other fp32-class ones)")
     ap.add_argument("--no-alt-path", action="store_true", help="skip the extra timed steps on the other conv arithmetics")
     ap.add_argument("--cpu-all-threads", action="store_true", help="re-measure the oracle's UNet forward on ALL logical CPUs next to the 32-thread baseline (~100 s)")
-    ap.add_argument("--no-other-workloads", action="store_true", help="skip the other BASELINE.json configs (cfg3 g=1 / g=8, cfg4, cfg5) that a default cfg2 run also times")
+    ap.add_argument("--no-other-workloads", action="store_true", help="skip the other BASELINE.json configs (cfg3 g=1 / g=8, cfg4, cfg5) that a --full cfg2 run also times")
+    ap.add_argument("--full", action="store_true", help="after the headline steps, also run the roofline step, the other arithmetics and workloads, the CPU "
+                                                       "baseline and the parity check (each --no-* option above still switches its part off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the images of the last timed step to DIR/images.npy (float32)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -313,6 +335,7 @@ def main():
         fence()
         dt = time.perf_counter() - t0
         per_rank[:] = [dt]
+        last_img[:] = [img]
         if world > 1:
             tt = torch.tensor([dt], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
             every = [torch.empty_like(tt) for _ in range(world)]
@@ -322,16 +345,18 @@ def main():
         assert img.shape[0] == n_global and bool(torch.isfinite(img).all())
         return dt
 
-    per_rank = []
+    per_rank, last_img = [], []
     for w in range(args.warmup):
         one_step(1000 + w)
     dt = timed(args.steps)
     rank_ms = [round(v / args.steps * 1e3, 2) for v in per_rank]
     ips = n_global * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_img[0])
 
     roof = None
     ar = ARITH[prec]
-    if not args.no_roofline and rank == 0:
+    if args.full and not args.no_roofline and rank == 0:
         # live launch timing: one more full step of the SAME workload with every launch bracketed by hipEvents on its stream (mf_prof_*);
         # rocprofv3 --kernel-trace of this command sees the same mix (profiles/)
         with K.prof() as p:
@@ -412,7 +437,7 @@ def main():
                 "families_ms": {k: round(v[0], 3) for k, v in sorted(tab.items(), key=lambda kv: -kv[1][0])},
                 "hbm_bound_passes": hbm}
     alts = []
-    if not args.no_alt_path and rank == 0 and world == 1:
+    if args.full and not args.no_alt_path and rank == 0 and world == 1:
         # the same step on the other conv arithmetics, timed the same way (1 warm-up + max(1, steps) runs), for comparison
         others = [args.alt_precision] if args.alt_precision is not None else [a for a in (5, 1, 0) if a != prec][:2]
         for a in others:
@@ -446,7 +471,7 @@ def main():
             alts.append(ent)
         BLK.CONV_PRECISION = prec
     reduced = []
-    if not args.no_alt_path and rank == 0 and world == 1 and args.alt_precision is None and args.conv_precision is None:
+    if args.full and not args.no_alt_path and rank == 0 and world == 1 and args.alt_precision is None and args.conv_precision is None:
         # the two opt-in REDUCED-precision modes on the same step (never the headline).  The single-term fp16 mode is also the
         # gauge VERDICT r03 asked for: one matrix term instead of three on the same kernel -- what it gains is what is NOT fixed cost.
         for a in (6, 4):
@@ -457,7 +482,7 @@ def main():
                             "headline": False})
         BLK.CONV_PRECISION = prec
     others_wl = []
-    if (not args.no_other_workloads and rank == 0 and world == 1 and args.workload == "cfg2" and not args.ddim_steps and not args.batch
+    if (args.full and not args.no_other_workloads and rank == 0 and world == 1 and args.workload == "cfg2" and not args.ddim_steps and not args.batch
             and args.conv_precision is None):
         # every other BASELINE.json config at its per-GPU size, in THIS process and on the default arithmetic: a warm-up
         # (short for cfg4: its loop is the 1000-iteration one), then the timed steps, fenced like the headline.  ~15 s in all.
@@ -490,7 +515,7 @@ def main():
                                                              "bulk200": "none -- the reference's bulk harness chunk (scripts/helpers/sample_dataset.py:26-27), a batch outside every plan table"}[name]}})
         del pipes
     cpu = parity = None
-    if not args.no_cpu_baseline and rank == 0 and world == 1:
+    if args.full and not args.no_cpu_baseline and rank == 0 and world == 1:
         cpu = cpu_baseline(wl["classes"])
         if CHECK and wl["classes"] is None:
             # the oracle evaluations that were just timed, as the CHECKER of what was benchmarked (same seeded weights): one UNet forward at

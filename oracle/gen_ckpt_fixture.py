@@ -7,6 +7,7 @@ Writes a checkpoint pair with the LAYOUT of a real Medfusion run, produced by th
                                                     (a path RELATIVE to the training cwd, like scripts/train_diffusion.py:114), use_ema=True with
                                                     EMA weights that differ from the live ones (diffusion_pipeline.py:57-60, 70-74)
 and tests/golden/ckpt_sample.npz: what the reference samples from that checkpoint (EMA weights and live weights) with injected noise.
+The pipeline checkpoint is committed as last.ckpt.npz, its compact byte-exact form (oracle/ckpt_fixture.py).
 The hyper-parameters hold reference CLASS objects pickled by reference (medical_diffusion.models...), torch.optim.AdamW, torch.nn.L1Loss:
 exactly what the product's Lightning-free reader (medfusion_amd/checkpoint.py) has to cope with.
 
@@ -79,7 +80,11 @@ def main():
     assert not torch.equal(out["ema"], out["live"])
     np.savez_compressed(ROOT / "tests" / "golden" / "ckpt_sample.npz", image_ema=out["ema"].numpy(), image_live=out["live"].numpy(),
                         condition=cond.numpy(), seed=21, steps=5, draws=draws)
-    for f in ("runs/tiny_vae/last_vae.ckpt", "runs/tiny_diffusion/last.ckpt"):
+    # the pipeline checkpoint is committed in its compact form (oracle/ckpt_fixture.py; tests/util.py:ckpt_runs rebuilds it byte for byte)
+    from oracle import ckpt_fixture
+    ckpt_fixture.pack(Path("runs/tiny_diffusion/last.ckpt"), Path("runs/tiny_diffusion/last.ckpt.npz"))
+    os.remove("runs/tiny_diffusion/last.ckpt")
+    for f in ("runs/tiny_vae/last_vae.ckpt", "runs/tiny_diffusion/last.ckpt.npz"):
         print(f, os.path.getsize(f) // 1024, "KiB")
     print("checkpoint fixture written; reference sampled it with EMA and live weights")
 

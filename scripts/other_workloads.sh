@@ -4,7 +4,7 @@ cd /root/repo; mkdir -p gpurun_out
 OUT=${1:-gpurun_out/r03_other_workloads.txt}
 for wl in cfg3_g8 cfg3_g1 cfg5 cfg4; do
   st=2; [ $wl = cfg4 ] && st=1
-  timeout 900 python bench.py --workload $wl --steps $st --warmup 1 --no-cpu-baseline --no-roofline --alt-precision 1 2> gpurun_out/ow_$wl.err | python -c "
+  timeout 900 python bench.py --full --workload $wl --steps $st --warmup 1 --no-cpu-baseline --no-roofline --alt-precision 1 2> "$(dirname "$OUT")/ow_$wl.err" | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 print('$wl', d['value'], 'images/s', d['ms_per_step'], 'ms/step |', d['config']['workload'], '| exact bf16 triplets:', [a['value'] for a in d.get('other_conv_arithmetic', [])])"

@@ -23,10 +23,9 @@ from medfusion_amd import published as P
 from oracle import restate as R
 from oracle import synth as S
 from tests.test_oracle_cpu import build_oracle_pipe
-from tests.util import T, gold, oracle_noise, relerr
+from tests.util import T, ckpt_runs, gold, oracle_noise, relerr
 
 ROOT = Path(__file__).resolve().parents[1]
-CKPT = ROOT / "tests" / "golden" / "ckpt" / "runs"
 TOL = 1e-4
 GUIDED_HARNESS_TOL = 1e-4   # guidance 8 on the published widths, 6 iterations: measured on MI355X 7.1e-6 / 8.9e-6 (f16x2), 7.9e-6 / 8.6e-6 (split3), cfg3 rows 5.5e-6 / 7.0e-6 (the prints)
 
@@ -35,6 +34,11 @@ GUIDED_HARNESS_TOL = 1e-4   # guidance 8 on the published widths, 6 iterations: 
 def dev():
     assert torch.cuda.is_available()
     return torch.device("cuda:0")
+
+
+@pytest.fixture(scope="module")
+def ckpt_dir(tmp_path_factory):
+    return ckpt_runs(tmp_path_factory.mktemp("ckpt"))
 
 
 @pytest.fixture(params=[5, 1], ids=["f16x2", "split3"], autouse=True)
@@ -47,12 +51,12 @@ def conv_precision(request):
 
 
 @torch.no_grad()
-def test_reference_written_checkpoint_samples_like_the_reference(dev):
+def test_reference_written_checkpoint_samples_like_the_reference(dev, ckpt_dir):
     """rows f1 + E: DiffusionPipeline.load_from_checkpoint on the reference-written fixture (nested VAE checkpoint, use_ema=True in the
     hyper-parameters), then sample() against what the reference produced from the same file -- with the EMA weights
     (diffusion_pipeline.py:234-235) and with the live ones."""
     g = gold("ckpt_sample")
-    pipe = M.DiffusionPipeline.load_from_checkpoint(CKPT / "tiny_diffusion" / "last.ckpt").to(dev)
+    pipe = M.DiffusionPipeline.load_from_checkpoint(ckpt_dir / "tiny_diffusion" / "last.ckpt").to(dev)
     assert pipe.use_ema
     cond = T(g["condition"]).to(dev)
     imgs = {}
@@ -66,9 +70,9 @@ def test_reference_written_checkpoint_samples_like_the_reference(dev):
 
 
 @torch.no_grad()
-def test_default_noise_moves_on_between_calls(dev):
+def test_default_noise_moves_on_between_calls(dev, ckpt_dir):
     """two sample() calls in a row differ, reseeding reproduces the first (like the reference's default generator)"""
-    pipe = M.DiffusionPipeline.load_from_checkpoint(CKPT / "tiny_diffusion" / "last.ckpt").to(dev)
+    pipe = M.DiffusionPipeline.load_from_checkpoint(ckpt_dir / "tiny_diffusion" / "last.ckpt").to(dev)
     torch.manual_seed(0)
     a = pipe.sample(2, (8, 8, 8), steps=2, decode=False)
     b = pipe.sample(2, (8, 8, 8), steps=2, decode=False)

@@ -179,7 +179,10 @@ def test_checkpoint_reader_without_lightning(tmp_path):
 
 
 # ----------------------------------------------------------------------------- the real checkpoint layout
-CKPT = Path(__file__).resolve().parent / "golden" / "ckpt" / "runs"
+@pytest.fixture(scope="module")
+def ckpt_dir(tmp_path_factory):
+    from tests.util import ckpt_runs
+    return ckpt_runs(tmp_path_factory.mktemp("ckpt"))
 
 
 def _ref_tensors(path):
@@ -188,12 +191,12 @@ def _ref_tensors(path):
     return read_checkpoint(path)
 
 
-def test_checkpoint_written_by_the_reference_classes_loads(tmp_path):
+def test_checkpoint_written_by_the_reference_classes_loads(tmp_path, ckpt_dir):
     """tests/golden/ckpt/ was written by the REFERENCE's DiffusionPipeline / VAE through oracle/gen_ckpt_fixture.py: hyper-parameters
     captured by save_hyperparameters() hold reference class objects, torch.optim.AdamW, torch.nn.L1Loss; the VAE path baked into them is
     relative to the training cwd (scripts/train_diffusion.py:114); use_ema=True.  Three ways to the nested VAE, one result."""
     import shutil
-    ck = _ref_tensors(CKPT / "tiny_diffusion" / "last.ckpt")
+    ck = _ref_tensors(ckpt_dir / "tiny_diffusion" / "last.ckpt")
     hp, sd = ck["hyper_parameters"], ck["state_dict"]
     assert isinstance(hp, dict) and hp["noise_estimator"] is M.UNet and hp["latent_embedder"] is M.VAE and hp["noise_scheduler"] is M.GaussianNoiseScheduler
     assert hp["noise_estimator_kwargs"]["time_embedder"] is M.TimeEmbbeding and hp["noise_estimator_kwargs"]["cond_embedder"] is M.LabelEmbedder
@@ -210,24 +213,24 @@ def test_checkpoint_written_by_the_reference_classes_loads(tmp_path):
         assert not torch.equal(got["noise_estimator.outc.conv.conv.weight"], got["ema_model.averaged_model.outc.conv.conv.weight"])
 
     # 1. the baked relative path resolved against the checkpoint's own `runs/` tree
-    check(M.DiffusionPipeline.load_from_checkpoint(CKPT / "tiny_diffusion" / "last.ckpt"))
+    check(M.DiffusionPipeline.load_from_checkpoint(ckpt_dir / "tiny_diffusion" / "last.ckpt"))
     # 2. the pipeline checkpoint alone (what usually reaches a sampling box): VAE hyper-parameters inferred from the tensor shapes
     lone = tmp_path / "last.ckpt"
-    shutil.copy(CKPT / "tiny_diffusion" / "last.ckpt", lone)
+    shutil.copy(ckpt_dir / "tiny_diffusion" / "last.ckpt", lone)
     pipe = M.DiffusionPipeline.load_from_checkpoint(lone)
     check(pipe)
     from medfusion_amd.checkpoint import infer_vae_kwargs
     kw = infer_vae_kwargs({k[len("latent_embedder."):]: v for k, v in sd.items() if k.startswith("latent_embedder.")})
     assert kw["hid_chs"] == [32, 32, 32, 32] and kw["emb_channels"] == 8 and kw["strides"] == [1, 2, 2, 2] and kw["deep_supervision"] == 1
     # 3. an explicit path
-    check(M.DiffusionPipeline.load_from_checkpoint(lone, latent_embedder_checkpoint=str(CKPT / "tiny_vae" / "last_vae.ckpt")))
+    check(M.DiffusionPipeline.load_from_checkpoint(lone, latent_embedder_checkpoint=str(ckpt_dir / "tiny_vae" / "last_vae.ckpt")))
     # the VAE checkpoint on its own (VAE.load_from_checkpoint of scripts/helpers/sample_latent_embedder.py:50)
     from medfusion_amd.checkpoint import load_module_from_checkpoint
-    vae = load_module_from_checkpoint(M.VAE, CKPT / "tiny_vae" / "last_vae.ckpt")
+    vae = load_module_from_checkpoint(M.VAE, ckpt_dir / "tiny_vae" / "last_vae.ckpt")
     assert torch.equal(vae.state_dict()["outc.conv.weight"], sd["latent_embedder.outc.conv.weight"])
 
 
-def test_checkpoint_reader_refuses_foreign_globals_and_wrong_architectures(tmp_path):
+def test_checkpoint_reader_refuses_foreign_globals_and_wrong_architectures(tmp_path, ckpt_dir):
     """the unpickler resolves nothing outside its allow-list (a checkpoint is data), and a state dict that does not fit raises"""
     import pickle
     from medfusion_amd.checkpoint import load_module_from_checkpoint, read_checkpoint
@@ -254,7 +257,7 @@ def test_checkpoint_reader_refuses_foreign_globals_and_wrong_architectures(tmp_p
     torch.save({"state_dict": {}, "hyper_parameters": {"payload": inner.getvalue()}}, nested, pickle_protocol=4)
     assert isinstance(read_checkpoint(nested)["hyper_parameters"]["payload"], bytes)   # bytes stay bytes: nothing unpickles them
     with pytest.raises(RuntimeError, match="missing"):
-        load_module_from_checkpoint(M.VAE, CKPT / "tiny_vae" / "last_vae.ckpt", deep_supervision=2)   # a head the checkpoint has no weights for
+        load_module_from_checkpoint(M.VAE, ckpt_dir / "tiny_vae" / "last_vae.ckpt", deep_supervision=2)   # a head the checkpoint has no weights for
 
 
 def test_seeded_fill_matches_the_test_fill():

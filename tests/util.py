@@ -83,6 +83,23 @@ def oracle_fp64_drift(ora, seed: int, *args, **kw) -> float:
     return relerr(w32, w64)
 
 
+def ckpt_runs(dst: Path) -> Path:
+    """The reference-written checkpoint pair of tests/golden/ckpt/runs/ (oracle/gen_ckpt_fixture.py) as files under `dst`/runs: the
+    pipeline checkpoint is stored in its compact form (oracle/ckpt_fixture.py) and rebuilt byte for byte, the VAE checkpoint beside it is
+    copied, so the VAE path baked into the pipeline's hyper-parameters resolves as in the golden tree."""
+    import shutil
+
+    from oracle import ckpt_fixture
+
+    src = GOLD / "ckpt" / "runs"
+    runs = dst / "runs"
+    (runs / "tiny_diffusion").mkdir(parents=True, exist_ok=True)
+    (runs / "tiny_vae").mkdir(parents=True, exist_ok=True)
+    (runs / "tiny_diffusion" / "last.ckpt").write_bytes(ckpt_fixture.unpack(src / "tiny_diffusion" / "last.ckpt.npz"))
+    shutil.copy(src / "tiny_vae" / "last_vae.ckpt", runs / "tiny_vae" / "last_vae.ckpt")
+    return runs
+
+
 def oracle_noise(seed: int):
     """HostNoise that replays the oracle's numpy-Philox draws (same draws the golden fixtures were made with)."""
     import medfusion_amd as M
