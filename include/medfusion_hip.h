@@ -468,6 +468,22 @@ int mf_diag_gaussian_sample_f32(const float* moments, const float* noise, float*
  * accumulation -- the `emb_loss` VAE.forward returns (:778), evaluation-time only */
 int mf_diag_gaussian_kl_f32(const float* moments, float* kl, int N, int C, int HW, void* stream);
 
+/* VectorQuantizer.forward of VQVAE / VQGAN (latent_embedders.py:40-71; additive to ABI 250): nearest-codebook search, gather and loss term.
+ * z NCHW [N][C][HW] fp32 (what the sampler hands to decode), codebook [K][C] fp32 (nn.Embedding weight, key quantizer.embedder.weight) ->
+ *   z_q NCHW [N][C][HW] = z + (e_idx - z) in fp32 (the reference's straight-through value :67, which can differ from the code row by an ulp),
+ *   idx[N*HW] int32 (optional, NULL: not written), pixel order n * HW + hw,
+ *   sqerr[0] = sum over all elements of (e_idx - z)^2, each square in fp32, summed in fp64 (optional, NULL) -- the reference's
+ *   emb_loss = (1 + beta) * sqerr / (N * C * HW) (:62).
+ * Distance: the reference's cancelling formula d_k = (sum_c z_c^2 + sum_c e_kc^2) - 2 * sum_c z_c e_kc (:51-54), every sum in fp32 in index
+ * order, no contraction; d may be negative.  argmin (:56): equal distances resolve to the LOWEST index; a NaN distance beats every number and
+ * the first NaN wins (torch.argmin).  The result does not depend on launch order (the codebook slices combine through a commutative 64-bit
+ * minimum; the loss partials are summed in a fixed order): two calls give bit-identical outputs.
+ * 1 <= C <= 16 (larger: MF_EUNSUPPORTED), K >= 1, N = 0 returns at once.  workspace: mf_vq_workspace_bytes(N * HW) bytes of caller scratch.
+ * 3 launches, a 4th with sqerr. */
+size_t mf_vq_workspace_bytes(int64_t pixels);
+int mf_vector_quantize_f32(const float* z, const float* codebook, float* z_q, int32_t* idx, double* sqerr, void* workspace,
+                           size_t workspace_bytes, int N, int C, int HW, int K, void* stream);
+
 /* learnable_interpolation=False (ABI 210): BasicDown = nn.AvgPool2d(k, stride, get_padding(k, stride)) (conv_blocks.py:57-63; count_include_pad
  * like torch's default: the divisor counts the padding), BasicUp = F.interpolate(nearest-exact) to twice the size (conv_blocks.py:128-130).
  * NHWC fp32, C % 4 == 0. */

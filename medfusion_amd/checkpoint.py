@@ -6,10 +6,12 @@ CLASS objects of the reference package (`medical_diffusion.models...UNet`).  An 
 references onto this package's classes, so trained Medfusion weights load into the HIP path with
 `DiffusionPipeline.load_from_checkpoint(path)` and no reference / Lightning import.
 
-The nested VAE (diffusion_pipeline.py:57-58 calls `latent_embedder.load_from_checkpoint(latent_embedder_checkpoint)` with a path
+The nested latent embedder (diffusion_pipeline.py:57-58 calls `latent_embedder.load_from_checkpoint(latent_embedder_checkpoint)` with a path
 baked in at training time) is resolved in this order: the `latent_embedder_checkpoint=` override; the baked path (as given, then
-relative to the pipeline checkpoint's directory); `latent_embedder_kwargs=`; and finally the VAE's hyper-parameters INFERRED from the
-shapes of the `latent_embedder.*` tensors the pipeline checkpoint itself carries (a LightningModule saves its sub-modules' weights).
+relative to the pipeline checkpoint's directory); `latent_embedder_kwargs=`; and finally the embedder's hyper-parameters INFERRED from the
+shapes of the `latent_embedder.*` tensors the pipeline checkpoint itself carries (a LightningModule saves its sub-modules' weights).  The
+embedder may be any of the reference's four (latent_embedders.py: VAE, VAEGAN, VQVAE, VQGAN); a pipeline checkpoint naming another class is
+refused rather than loaded without its embedder.
 """
 from __future__ import annotations
 
@@ -27,6 +29,9 @@ _CLASS_MAP = {
     "LabelEmbedder": ("medfusion_amd.unet", "LabelEmbedder"),
     "GaussianNoiseScheduler": ("medfusion_amd.scheduler", "GaussianNoiseScheduler"),
     "VAE": ("medfusion_amd.vae", "VAE"),
+    "VAEGAN": ("medfusion_amd.vq", "VAEGAN"),
+    "VQVAE": ("medfusion_amd.vq", "VQVAE"),
+    "VQGAN": ("medfusion_amd.vq", "VQGAN"),
     "DiffusionPipeline": ("medfusion_amd.pipeline", "DiffusionPipeline"),
 }
 # training-only objects a checkpoint may reference: replaced by an inert placeholder
@@ -89,7 +94,8 @@ class _RemapUnpickler(pickle.Unpickler):
         if name == "AttributeDict":   # Lightning's hparams container (a dict subclass)
             return dict
         if module.startswith(_PLACEHOLDER_PREFIXES):
-            return _Placeholder
+            # a named subclass: the pipeline loader can tell WHICH class a hyper-parameter referred to (an unknown latent embedder is refused)
+            return type(name, (_Placeholder,), {"ref_name": f"{module}.{name}"})
         if name in _ALLOWED.get(module, ()):
             return super().find_class(module, name)
         raise pickle.UnpicklingError(f"checkpoint references {module}.{name}, which is not on the allow-list of medfusion_amd.checkpoint")
@@ -113,9 +119,13 @@ def _strip(sd: dict, prefix: str) -> dict:
     return {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
 
 
+def _is_placeholder(v) -> bool:
+    return isinstance(v, _Placeholder) or (isinstance(v, type) and issubclass(v, _Placeholder))
+
+
 def _clean_hparams(hp: dict) -> dict:
     def bad(v):
-        return v is _Placeholder or isinstance(v, _Placeholder)
+        return _is_placeholder(v)
 
     out = {}
     for k, v in hp.items():
@@ -127,7 +137,8 @@ def _clean_hparams(hp: dict) -> dict:
     return out
 
 
-_TRAINING_ONLY = re.compile(r"^(perceiver|loss|loss_fct|discriminator|vqvae|ssim_fct)\b|\.num_batches_tracked$")
+# (not `vqvae`: VQGAN / VAEGAN keep their whole autoencoder under that name -- a checkpoint without it must not load with random weights)
+_TRAINING_ONLY = re.compile(r"^(perceiver|loss|loss_fct|discriminator|ssim_fct)\b|\.num_batches_tracked$")
 
 
 def _check_missing(missing, what):
@@ -136,16 +147,27 @@ def _check_missing(missing, what):
         raise RuntimeError(f"{what}: the checkpoint is missing {len(bad)} tensors of the model, e.g. {bad[:4]} -- different architecture or key names")
 
 
-def infer_vae_kwargs(sd: dict) -> dict:
-    """Hyper-parameters of a `VAE` (latent_embedders.py:620-749) from the SHAPES of its state-dict tensors (keys without the
-    `latent_embedder.` prefix).  GroupNorm group counts leave no trace in the shapes: the reference default (8 groups) is assumed."""
+_GROUP_DEFAULT = {"VAE": 8, "VAEGAN": 8, "VQVAE": 32, "VQGAN": 32}
+
+
+def infer_vae_kwargs(sd: dict, cls_name: str = "VAE") -> dict:
+    """Hyper-parameters of a latent embedder from the SHAPES of its state-dict tensors (keys without the `latent_embedder.` prefix):
+    `VAE` (latent_embedders.py:620-749), `VAEGAN` (:860-925, a VAE under `vqvae.`), `VQVAE` (:191-302: a single 1x1 `out_enc` block, the
+    codebook `quantizer.embedder.weight` [num_embeddings, emb_channels]) or `VQGAN` (:408-462, a VQVAE under `vqvae.`).  GroupNorm group
+    counts leave no trace in the shapes and are not returned: each class's own default applies (8 groups for VAE and VAEGAN, 32 for VQVAE
+    and VQGAN)."""
+    if cls_name not in _GROUP_DEFAULT:
+        raise RuntimeError(f"cannot infer the architecture of a {cls_name}: only {sorted(_GROUP_DEFAULT)}")
+    if cls_name in ("VQGAN", "VAEGAN"):
+        sd = _strip(sd, "vqvae.")
+
     def shape(key):
         if key not in sd:
-            raise RuntimeError(f"cannot infer the VAE architecture: tensor '{key}' is not in the checkpoint")
+            raise RuntimeError(f"cannot infer the {cls_name} architecture: tensor '{key}' is not in the checkpoint")
         return tuple(sd[key].shape)
 
     if any(".attention." in k for k in sd):
-        raise RuntimeError("the VAE in this checkpoint uses attention blocks: pass latent_embedder_kwargs=... explicitly")
+        raise RuntimeError(f"the {cls_name} in this checkpoint uses attention blocks: pass latent_embedder_kwargs=... explicitly")
     res = any(".basic_block." in k for k in sd)
     conv0 = "inc.block_seq.0.basic_block.conv.weight" if res else "inc.block_seq.0.conv.weight"
     w0 = shape(conv0)
@@ -159,8 +181,15 @@ def infer_vae_kwargs(sd: dict) -> dict:
         strides.append(2 if f"encoders.{i}.down_op.down_op.weight" in sd else 1)
     emb = shape("inc_dec.block_seq.0." + ("basic_block.conv.weight" if res else "conv.weight"))[1]
     deep = 1 + max([int(m.group(1)) for k in sd for m in [re.match(r"outc_ver\.(\d+)\.", k)] if m], default=-1)
-    return dict(in_channels=w0[1], out_channels=shape("outc.conv.weight")[0], spatial_dims=2, emb_channels=emb, hid_chs=hid, kernel_sizes=ks,
-                strides=strides, use_res_block=res, deep_supervision=deep, use_attention="none")
+    kw = dict(in_channels=w0[1], out_channels=shape("outc.conv.weight")[0], spatial_dims=2, emb_channels=emb, hid_chs=hid, kernel_sizes=ks,
+              strides=strides, use_res_block=res, deep_supervision=deep, use_attention="none")
+    if cls_name in ("VQVAE", "VQGAN"):
+        n_codes, emb_q = shape("quantizer.embedder.weight")
+        if emb_q != emb or shape("out_enc.conv.weight")[:2] != (emb, hid[-1]):
+            raise RuntimeError(f"the {cls_name} in this checkpoint does not fit together: codebook {n_codes}x{emb_q}, decoder input {emb}, "
+                               f"out_enc {shape('out_enc.conv.weight')}")
+        kw["num_embeddings"] = n_codes
+    return kw
 
 
 def load_module_from_checkpoint(cls, path, map_location="cpu", **overrides):
@@ -180,6 +209,10 @@ def load_pipeline_from_checkpoint(cls, path, map_location="cpu", **overrides):
     vae_kwargs = overrides.pop("latent_embedder_kwargs", None)
     hp.update(overrides)
     sd = ck["state_dict"]
+    named = dict(ck.get("hyper_parameters", {})).get("latent_embedder")
+    if _is_placeholder(named) and "latent_embedder" not in overrides:
+        raise RuntimeError(f"{path}: the latent embedder class {getattr(named, 'ref_name', named)!r} has no counterpart in medfusion_amd "
+                           f"(supported: VAE, VAEGAN, VQVAE, VQGAN) -- sampling without it would return latents, not images")
     vae_cls = hp.get("latent_embedder")
     if isinstance(vae_cls, type):
         baked = hp.get("latent_embedder_checkpoint", "") or ""
@@ -195,7 +228,7 @@ def load_pipeline_from_checkpoint(cls, path, map_location="cpu", **overrides):
             if not vsd:
                 raise RuntimeError(f"latent_embedder_checkpoint '{baked}' is not readable and the pipeline checkpoint carries no latent_embedder.* "
                                    f"tensors: pass latent_embedder_checkpoint=<path of the VAE checkpoint>")
-            hp["latent_embedder"] = vae_cls(**(vae_kwargs if vae_kwargs is not None else infer_vae_kwargs(vsd)))  # weights: from `sd` below
+            hp["latent_embedder"] = vae_cls(**(vae_kwargs if vae_kwargs is not None else infer_vae_kwargs(vsd, vae_cls.__name__)))  # weights: `sd`
     pipe = cls(**hp)
     missing, _unexpected = pipe.load_state_dict(sd, strict=False)
     _check_missing(missing, f"DiffusionPipeline.load_from_checkpoint({path})")

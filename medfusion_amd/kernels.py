@@ -1221,6 +1221,31 @@ def diag_gaussian_kl(moments_nchw: torch.Tensor) -> torch.Tensor:
     return kl.reshape(())
 
 
+def vector_quantize(z_nchw: torch.Tensor, codebook: torch.Tensor, want_idx: bool = False, want_sqerr: bool = False):
+    """VectorQuantizer.forward (latent_embedders.py:40-71) on the device: z [N,C,H,W], codebook [K,C] -> (z_q [N,C,H,W] = z + (e_idx - z),
+    idx int32 [N*H*W] or None, sum of (e_idx - z)^2 as a 0-dim fp64 device tensor or None).  Nearest code by the reference's formula, lowest
+    index on ties, first NaN wins (include/medfusion_hip.h)."""
+    _gpu(z_nchw, codebook)
+    if z_nchw.dim() != 4 or codebook.dim() != 2 or z_nchw.dtype != torch.float32 or codebook.dtype != torch.float32:
+        raise RuntimeError(f"vector_quantize: z {tuple(z_nchw.shape)} {z_nchw.dtype} / codebook {tuple(codebook.shape)} {codebook.dtype}: "
+                           f"expected fp32 [N,C,H,W] and [K,C]")
+    n, c, h, w = z_nchw.shape
+    k, ce = codebook.shape
+    if ce != c:
+        raise RuntimeError(f"vector_quantize: z has {c} channels, the codebook {ce}")
+    z = z_nchw.contiguous()
+    cb = codebook.detach().contiguous()
+    zq = torch.empty_like(z)
+    idx = torch.empty((n * h * w,), dtype=torch.int32, device=z.device) if want_idx else None
+    sq = torch.zeros((1,), dtype=torch.float64, device=z.device) if want_sqerr else None
+    lib = L.load()
+    nbytes = lib.mf_vq_workspace_bytes(n * h * w)
+    ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=z.device)
+    L.check(lib.mf_vector_quantize_f32(z.data_ptr(), cb.data_ptr(), zq.data_ptr(), _ptr(idx), _ptr(sq), ws.data_ptr(), nbytes, n, c, h * w, k,
+                                       stream()), "mf_vector_quantize_f32")
+    return zq, idx, (sq.reshape(()) if sq is not None else None)
+
+
 # ----------------------------------------------------------------------------- launch timing
 _PROF_ACTIVE = [False]
 

@@ -22,6 +22,11 @@ class DiagonalGaussianDistribution(nn.Module):
         return K.diag_gaussian_sample(moments_nchw, noise), None
 
 
+def _require_device(x: torch.Tensor, who: str) -> None:
+    if not x.is_cuda:
+        raise RuntimeError(f"medfusion_amd.{who} runs on a ROCm device only (no CPU fallback)")
+
+
 class VAE(nn.Module):
     def __init__(self, in_channels=3, out_channels=3, spatial_dims=2, emb_channels=4, hid_chs=[64, 128, 256, 512], kernel_sizes=[3, 3, 3, 3],
                  strides=[1, 2, 2, 2], norm_name=("GROUP", {"num_groups": 8, "affine": True}), act_name=("Swish", {}), dropout=None,
@@ -58,8 +63,7 @@ class VAE(nn.Module):
     @torch.no_grad()
     def encode(self, x: torch.Tensor, noise: Optional[NoiseSource] = None) -> torch.Tensor:
         """x [B,3,H,W] NCHW -> z [B,emb,H/8,W/8] NCHW (stochastic: one N(0,1) draw of z's shape)."""
-        if not x.is_cuda:
-            raise RuntimeError("medfusion_amd.VAE runs on a ROCm device only (no CPU fallback)")
+        _require_device(x, type(self).__name__)
         K.SyncWords.reset(x.device)
 
         moments = K.with_fused_fallback(x.device, lambda: self._encode_moments(x))
@@ -73,19 +77,25 @@ class VAE(nn.Module):
     @torch.no_grad()
     def decode(self, z: torch.Tensor) -> torch.Tensor:
         """z [B,emb,h,w] NCHW -> x [B,3,8h,8w] NCHW."""
-        if not z.is_cuda:
-            raise RuntimeError("medfusion_amd.VAE runs on a ROCm device only (no CPU fallback)")
+        _require_device(z, type(self).__name__)
         if z.shape[0] == 0:   # an empty shard of a multi-GPU batch (more ranks than samples): nothing to launch
             return z.new_empty((0, self.out_channels, z.shape[2] * self.scale, z.shape[3] * self.scale))
         K.SyncWords.reset(z.device)
+        return K.with_fused_fallback(z.device, lambda: self._decode_pass(self._decode_input(z)))
 
-        def run():
-            h = self.inc_dec(z.contiguous(), None, in_layout=L.LAYOUT_NCHW)
-            for i in range(len(self.decoders), 0, -1):
-                h = self.decoders[i - 1](h)
-            return self.outc(h, out_layout=L.LAYOUT_NCHW)
+    def _decode_input(self, z):
+        """what the decoder's first block reads: the latent itself (VQVAE quantizes it here)"""
+        return z
 
-        return K.with_fused_fallback(z.device, run)
+    def _decode_pass(self, z, out_hor=None):
+        """inc_dec -> decoders (coarsest first) -> outc; with a list `out_hor`, the deep-supervision outputs of the coarser levels are
+        appended to it on the way (coarsest first, like the reference's loop before its `[::-1]`)"""
+        h = self.inc_dec(z.contiguous(), None, in_layout=L.LAYOUT_NCHW)
+        for i in range(len(self.decoders) - 1, -1, -1):
+            if out_hor is not None and i < len(self.outc_ver):
+                out_hor.append(self.outc_ver[i](h, out_layout=L.LAYOUT_NCHW))
+            h = self.decoders[i](h)
+        return self.outc(h, out_layout=L.LAYOUT_NCHW)
 
     def _encode_moments(self, x):
         h = self.inc(x.contiguous(), None, in_layout=L.LAYOUT_NCHW)
@@ -99,8 +109,7 @@ class VAE(nn.Module):
         """latent_embedders.py:771-790 -- the reconstruction pass of the evaluation harness: (out [B,3,H,W], the deep-supervision outputs of
         the coarser decoder levels (finest first, like the reference's `out_hor[::-1]`), the KL term of the quantizer).  Inference only:
         the losses built on these (`_step`, :803-840) are training code and out of scope."""
-        if not x_in.is_cuda:
-            raise RuntimeError("medfusion_amd.VAE runs on a ROCm device only (no CPU fallback)")
+        _require_device(x_in, type(self).__name__)
         K.SyncWords.reset(x_in.device)
         src = noise if noise is not None else default_noise()
 
@@ -115,11 +124,7 @@ class VAE(nn.Module):
             z_q, _ = self.quantizer(moments, drawn[0])
             emb_loss = K.diag_gaussian_kl(moments)
             out_hor = []
-            h = self.inc_dec(z_q.contiguous(), None, in_layout=L.LAYOUT_NCHW)
-            for i in range(len(self.decoders) - 1, -1, -1):
-                if i < len(self.outc_ver):
-                    out_hor.append(self.outc_ver[i](h, out_layout=L.LAYOUT_NCHW))
-                h = self.decoders[i](h)
-            return self.outc(h, out_layout=L.LAYOUT_NCHW), out_hor[::-1], emb_loss
+            out = self._decode_pass(z_q, out_hor)
+            return out, out_hor[::-1], emb_loss
 
         return K.with_fused_fallback(x_in.device, run)
