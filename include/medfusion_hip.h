@@ -484,6 +484,35 @@ size_t mf_vq_workspace_bytes(int64_t pixels);
 int mf_vector_quantize_f32(const float* z, const float* codebook, float* z_q, int32_t* idx, double* sqerr, void* workspace,
                            size_t workspace_bytes, int N, int C, int HW, int K, void* stream);
 
+/* --- 3-D convolution (spatial_dims=3; additive to ABI 250): MONAI Convolution with Conv[CONV, 3] at conv_blocks.py:48,169,229 -- BasicBlock /
+ * BasicResBlock / UnetBasicBlock / UnetResBlock convolutions, BasicDown (stride 2 or (1, 2, 2)), BasicUp (nearest x2 per axis, then 3x3x3), the
+ * fused torch.cat([h, skip]) of unet2.py:259 -- on the MF_CONV_FP32_F16X2 arithmetic (the only one built in 3-D).
+ * Operands: x1 / x2 NDHWC fp16 pairs, i.e. what mf_split_f16x2 / mf_gn_apply_*_pairs / mf_pack_nchw_pairs_f32 write for the [N, D*H, W, C] view
+ * of an NDHWC tensor, with per-sample bounds [N] (or NULL: unscaled); C1 and C2 whole 32-channel chunks (a network input with fewer channels is
+ * zero-padded: mf_pack_nchw_pairs_f32 with HW = D*H*W, CP = 32).  Weights: mf_pack_conv3d_weight_f32 (OIDHW -> [Cout][KD][KH][KW][cin_pad],
+ * input channels Cin.. zero), then split into pairs once by mf_split_f16x2 under their max |w| (= w_bound).  y: fp32 NDHWC [N][Do][Ho][Wo][Cout]
+ * plus bias.  Any Cout >= 1 (masked on store).  Split-K slices go to `workspace` (mf_conv3d_workspace_bytes) and are summed in slice order by a
+ * second launch: bit-identical from run to run.  mf_conv3d_ok(d) == 1 guarantees that mf_conv3d_f16x2 accepts d (with that workspace). */
+typedef struct MfConv3dDesc {
+  int32_t N, D, H, W;      /* batch, input size per axis (BEFORE a fused upsample) */
+  int32_t C1, C2;          /* channels of x1 and x2 (C2 = 0: single source), multiples of 32 */
+  int32_t Cout;
+  int32_t k;               /* 1 or 3 on every axis */
+  int32_t stride[3];       /* per axis (d, h, w): 1 or 2 */
+  int32_t pad[3];          /* per axis: MONAI get_padding(k, stride) */
+  int32_t upsample[3];     /* per axis: 1 = nearest x2 of the input folded into the gather (source voxel u >> 1) */
+  int32_t tile_hint;       /* 0 = planner; 1..4 = 64x64, 128x64, 64x128, 128x128 voxels x channels */
+  int32_t splitk_hint;     /* 0 = planner; else 1..16 slices of the (chunk, tap) loop */
+  int32_t precision;       /* must be MF_CONV_FP32_F16X2 */
+} MfConv3dDesc;
+int mf_conv3d_ok(const MfConv3dDesc* d);
+int mf_conv3d_out_dims(const MfConv3dDesc* d, int32_t* out3);
+int mf_conv3d_plan_query(const MfConv3dDesc* d, int32_t* tile, int32_t* splitk);
+size_t mf_conv3d_workspace_bytes(const MfConv3dDesc* d);
+int mf_pack_conv3d_weight_f32(const float* w_oidhw, float* out, int Cout, int Cin, int k, int cin_pad, void* stream);
+int mf_conv3d_f16x2(const void* x1_pairs, const void* x2_pairs, const void* w_pairs, const float* bias, float* y, const float* x1_bound,
+                    const float* x2_bound, float w_bound, void* workspace, size_t workspace_bytes, const MfConv3dDesc* d, void* stream);
+
 /* learnable_interpolation=False (ABI 210): BasicDown = nn.AvgPool2d(k, stride, get_padding(k, stride)) (conv_blocks.py:57-63; count_include_pad
  * like torch's default: the divisor counts the padding), BasicUp = F.interpolate(nearest-exact) to twice the size (conv_blocks.py:128-130).
  * NHWC fp32, C % 4 == 0. */

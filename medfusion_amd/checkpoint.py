@@ -181,7 +181,9 @@ def infer_vae_kwargs(sd: dict, cls_name: str = "VAE") -> dict:
         strides.append(2 if f"encoders.{i}.down_op.down_op.weight" in sd else 1)
     emb = shape("inc_dec.block_seq.0." + ("basic_block.conv.weight" if res else "conv.weight"))[1]
     deep = 1 + max([int(m.group(1)) for k in sd for m in [re.match(r"outc_ver\.(\d+)\.", k)] if m], default=-1)
-    kw = dict(in_channels=w0[1], out_channels=shape("outc.conv.weight")[0], spatial_dims=2, emb_channels=emb, hid_chs=hid, kernel_sizes=ks,
+    # spatial_dims from the rank of the convolution weights (OIHW: 2, OIDHW: 3); a 3-D down-sampling stride leaves no trace in the shapes
+    # either: 2 on every axis, like the reference's default -- an anisotropic one needs latent_embedder_kwargs=...
+    kw = dict(in_channels=w0[1], out_channels=shape("outc.conv.weight")[0], spatial_dims=len(w0) - 2, emb_channels=emb, hid_chs=hid, kernel_sizes=ks,
               strides=strides, use_res_block=res, deep_supervision=deep, use_attention="none")
     if cls_name in ("VQVAE", "VQGAN"):
         n_codes, emb_q = shape("quantizer.embedder.weight")

@@ -787,6 +787,70 @@ def conv2d_f16x2_gn_apply(x1: torch.Tensor, w_split, bias: Optional[torch.Tensor
     return out
 
 
+def make_conv3d_desc(N, D, H, W, C1, C2, Cout, k, stride=(1, 1, 1), pad=(0, 0, 0), upsample=(0, 0, 0), tile_hint=0, splitk_hint=0,
+                     precision=5) -> L.MfConv3dDesc:
+    """descriptor of a 3-D convolution (mf_conv3d_f16x2): per-axis stride / pad / upsample as 3-tuples (an int: the same on every axis)"""
+    t3 = lambda v: (int(v),) * 3 if isinstance(v, int) else tuple(int(a) for a in v)
+    A = C.c_int32 * 3
+    return L.MfConv3dDesc(N, D, H, W, C1, C2, Cout, k, A(*t3(stride)), A(*t3(pad)), A(*t3(upsample)), tile_hint, splitk_hint, precision)
+
+
+def conv3d_ok(d: L.MfConv3dDesc) -> bool:
+    """True: mf_conv3d_f16x2 accepts `d` (with the workspace mf_conv3d_workspace_bytes names)"""
+    return bool(L.load().mf_conv3d_ok(C.byref(d)))
+
+
+def conv3d_out_dims(d: L.MfConv3dDesc):
+    out = (C.c_int32 * 3)()
+    L.check(L.load().mf_conv3d_out_dims(C.byref(d), out), "mf_conv3d_out_dims")
+    return tuple(out)
+
+
+def conv3d_plan(d: L.MfConv3dDesc):
+    """(tile id 1..4, split-K slices) the planner picks for `d` (the hints of `d` win)"""
+    t, k = C.c_int32(), C.c_int32()
+    L.check(L.load().mf_conv3d_plan_query(C.byref(d), C.byref(t), C.byref(k)), "mf_conv3d_plan_query")
+    return t.value, k.value
+
+
+def pack_conv3d_weight(w_oidhw: torch.Tensor, cin_pad: int = 0) -> torch.Tensor:
+    """OIDHW fp32 [Cout, Cin, k, k, k] -> [Cout, k, k, k, cin_pad] fp32 (input channels Cin.. zero; cin_pad 0: Cin)"""
+    _gpu(w_oidhw)
+    w = w_oidhw.detach().contiguous()
+    co, ci, k = w.shape[0], w.shape[1], w.shape[2]
+    if w.dim() != 5 or tuple(w.shape[2:]) != (k, k, k):
+        raise RuntimeError(f"pack_conv3d_weight: OIDHW weights with a cubic kernel, got {tuple(w.shape)}")
+    cp = cin_pad or ci
+    out = torch.empty((co, k, k, k, cp), dtype=torch.float32, device=w.device)
+    L.check(L.load().mf_pack_conv3d_weight_f32(w.data_ptr(), out.data_ptr(), co, ci, k, cp, stream()), "mf_pack_conv3d_weight_f32")
+    return out
+
+
+def conv3d_f16x2(x1: torch.Tensor, w_split, bias: Optional[torch.Tensor], d: L.MfConv3dDesc, x2: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """MF_CONV_FP32_F16X2 3-D convolution of NDHWC fp32 tensors (any shape with N leading and d.C1 / d.C2 innermost, e.g. the [N, D*H, W, C]
+    view) whose fp16-pair mirrors are made on demand (or that exist as pairs only: pack_nchw_pairs).  w_split = split_weight_f16x2(
+    pack_conv3d_weight(...)).  Returns y fp32 [N, Do, Ho, Wo, Cout] (or fills `out`, any shape of that size)."""
+    wh, wmax = w_split
+    _gpu(x1, x2, wh, bias)
+    lib = L.load()
+    if not lib.mf_conv3d_ok(C.byref(d)):
+        raise RuntimeError("conv3d_f16x2: descriptor not supported (mf_conv3d_ok)")
+    x1s, b1 = split_of(x1), bound_of(x1)
+    x2s, b2 = (split_of(x2), bound_of(x2)) if x2 is not None else (None, None)
+    do, ho, wo = conv3d_out_dims(d)
+    if out is None:
+        out = torch.empty((d.N, do, ho, wo, d.Cout), dtype=torch.float32, device=x1.device)
+    else:
+        drop_split(out)
+    need = lib.mf_conv3d_workspace_bytes(C.byref(d))
+    ws = Workspace.get(need, x1.device) if need else None
+    rc = lib.mf_conv3d_f16x2(x1s.data_ptr(), _ptr(x2s), wh.data_ptr(), _ptr(bias), out.data_ptr(), b1.data_ptr(), _ptr(b2), wmax, _ptr(ws), need,
+                             C.byref(d), stream())
+    L.check(rc, "mf_conv3d_f16x2")
+    return out
+
+
 def make_conv_desc(N, Hin, Win, C1, C2, Cout, k, stride, pad, upsample=0, in_layout=L.LAYOUT_NHWC, out_layout=L.LAYOUT_NHWC,
                    tile_hint=0, splitk_hint=0, precision=0) -> L.MfConvDesc:
     return L.MfConvDesc(N, Hin, Win, C1, C2, Cout, k, k, stride, pad, upsample, in_layout, out_layout, tile_hint, splitk_hint, precision)

@@ -21,6 +21,11 @@ class MfConvDesc(C.Structure):
         "tile_hint", "splitk_hint", "precision")]
 
 
+class MfConv3dDesc(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("N", "D", "H", "W", "C1", "C2", "Cout", "k")] + [(n, C.c_int32 * 3) for n in ("stride", "pad", "upsample")]
+                + [(n, C.c_int32) for n in ("tile_hint", "splitk_hint", "precision")])
+
+
 class MfSchedStep(C.Structure):
     _fields_ = [("sqrt_recip_ac", C.c_float), ("sqrt_recipm1_ac", C.c_float), ("coef1", C.c_float), ("coef2", C.c_float),
                 ("std_fixed", C.c_float), ("log_var_min", C.c_float), ("log_var_max", C.c_float), ("ddim_sqrt_an", C.c_float),
@@ -146,6 +151,12 @@ _SIGS = {
     "mf_diag_gaussian_kl_f32": (_I, [c_fp, c_fp, _I, _I, _I, c_fp]),
     "mf_vq_workspace_bytes": (_SZ, [_I64]),
     "mf_vector_quantize_f32": (_I, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, _SZ, _I, _I, _I, _I, c_fp]),
+    "mf_conv3d_ok": (_I, [C.POINTER(MfConv3dDesc)]),
+    "mf_conv3d_out_dims": (_I, [C.POINTER(MfConv3dDesc), C.POINTER(C.c_int32)]),
+    "mf_conv3d_plan_query": (_I, [C.POINTER(MfConv3dDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mf_conv3d_workspace_bytes": (_SZ, [C.POINTER(MfConv3dDesc)]),
+    "mf_pack_conv3d_weight_f32": (_I, [c_fp, c_fp, _I, _I, _I, _I, c_fp]),
+    "mf_conv3d_f16x2": (_I, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, _F, c_fp, _SZ, C.POINTER(MfConv3dDesc), c_fp]),
     "mf_prof_enable": (_I, [_I]),
     "mf_prof_reset": (_I, []),
     "mf_prof_query": (_I, [_I, C.POINTER(C.c_double), C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -14,6 +14,7 @@ import torch.nn as nn
 from . import kernels as K
 from . import lib as L
 from . import blocks as BLK
+from . import blocks3d as B3
 from .blocks import (Attention, BasicBlock, BasicDown, BasicUp, Conv, SequentialEmb, UnetBasicBlock, UnetResBlock, _EmbBlock, zero_module)
 
 
@@ -111,11 +112,26 @@ class UNet(nn.Module):
                  estimate_variance=False, use_self_conditioning=False, dropout=0.0, learnable_interpolation=True, use_attention="none",
                  num_res_blocks=2):
         super().__init__()
-        if spatial_dims != 2:
-            raise NotImplementedError("the HIP sampling path is 2-D (published Medfusion models are spatial_dims=2)")
         if act_name[0].upper() != "SWISH":
             raise NotImplementedError("only the Swish activation is on the HIP path")
         use_attention = use_attention if isinstance(use_attention, list) else [use_attention] * len(strides)
+        # the block classes of the path: blocks.py (2-D) or blocks3d.py (3-D: same keys, 5-D weights, the 3-D convolution)
+        if spatial_dims == 2:
+            BasicBlock_, UnetResBlock_, UnetBasicBlock_, BasicDown_, BasicUp_, UnetOutBlock_ = (BasicBlock, UnetResBlock, UnetBasicBlock, BasicDown,
+                                                                                            BasicUp, UnetOutBlock)
+        elif spatial_dims == 3:
+            for a in use_attention:
+                if a != "none":
+                    raise NotImplementedError(f"use_attention={a!r}: attention is not built in 3-D")
+            if use_self_conditioning:
+                raise NotImplementedError("use_self_conditioning=True is not built in 3-D")
+            if estimate_variance:
+                raise NotImplementedError("estimate_variance=True is not built in 3-D")
+            BasicBlock_, UnetResBlock_, UnetBasicBlock_, BasicDown_, BasicUp_, UnetOutBlock_ = (B3.BasicBlock, B3.UnetResBlock, B3.UnetBasicBlock,
+                                                                                            B3.BasicDown, B3.BasicUp, B3.UnetOutBlock)
+        else:
+            raise NotImplementedError(f"spatial_dims={spatial_dims}: the HIP sampling path is 2-D or 3-D")
+        self.spatial_dims = spatial_dims
         self.use_self_conditioning, self.use_res_block = use_self_conditioning, use_res_block
         self.depth, self.num_res_blocks = len(strides), num_res_blocks
         self.out_ch, self.estimate_variance = out_ch, estimate_variance
@@ -124,9 +140,9 @@ class UNet(nn.Module):
         time_emb_dim = self.time_embedder.emb_dim if self.time_embedder is not None else None
         self.cond_embedder = cond_embedder(**dict(cond_embedder_kwargs)) if cond_embedder is not None else None
 
-        ConvBlock = UnetResBlock if use_res_block else UnetBasicBlock
+        ConvBlock = UnetResBlock_ if use_res_block else UnetBasicBlock_
         in_ch = in_ch * 2 if use_self_conditioning else in_ch
-        self.in_conv = BasicBlock(spatial_dims, in_ch, hid_chs[0], kernel_size=kernel_sizes[0], stride=strides[0])
+        self.in_conv = BasicBlock_(spatial_dims, in_ch, hid_chs[0], kernel_size=kernel_sizes[0], stride=strides[0])
 
         def att(ch, lvl):
             return Attention(spatial_dims, ch, ch, 8, ch // 8, norm_name, dropout, time_emb_dim, 1, use_attention[lvl])
@@ -138,7 +154,7 @@ class UNet(nn.Module):
                     ConvBlock(spatial_dims, hid_chs[i - 1 if k == 0 else i], hid_chs[i], kernel_sizes[i], 1, norm_name, act_name, dropout, time_emb_dim),
                     att(hid_chs[i], i)))
             if i < self.depth - 1:
-                in_blocks.append(BasicDown(spatial_dims, hid_chs[i], hid_chs[i], kernel_sizes[i], strides[i], learnable_interpolation))
+                in_blocks.append(BasicDown_(spatial_dims, hid_chs[i], hid_chs[i], kernel_sizes[i], strides[i], learnable_interpolation))
         self.in_blocks = nn.ModuleList(in_blocks)
 
         self.middle_block = SequentialEmb(
@@ -152,19 +168,19 @@ class UNet(nn.Module):
                 oc = hid_chs[i - 1 if k == 0 else i]
                 seq = [ConvBlock(spatial_dims, hid_chs[i] + oc, oc, kernel_sizes[i], 1, norm_name, act_name, dropout, time_emb_dim), att(oc, i)]
                 if i > 1 and k == 0:
-                    seq.append(BasicUp(spatial_dims, oc, oc, strides[i], strides[i], learnable_interpolation))
+                    seq.append(BasicUp_(spatial_dims, oc, oc, strides[i], strides[i], learnable_interpolation))
                 out_blocks.append(SequentialEmb(*seq))
         self.out_blocks = nn.ModuleList(out_blocks)
 
         out_ch_hor = out_ch * 2 if estimate_variance else out_ch
-        self.outc = zero_module(UnetOutBlock(spatial_dims, hid_chs[0], out_ch_hor, dropout=None))
+        self.outc = zero_module(UnetOutBlock_(spatial_dims, hid_chs[0], out_ch_hor, dropout=None))
         if isinstance(deep_supervision, bool):
             deep_supervision = self.depth - 2 if deep_supervision else 0
         self.outc_ver = nn.ModuleList([
-            zero_module(UnetOutBlock(spatial_dims, hid_chs[i] + hid_chs[i - 1], out_ch, dropout=None)) for i in range(2, deep_supervision + 2)])
+            zero_module(UnetOutBlock_(spatial_dims, hid_chs[i] + hid_chs[i - 1], out_ch, dropout=None)) for i in range(2, deep_supervision + 2)])
 
         # all local embedders (Swish -> Linear(E, Cout)) batched into ONE GEMM per forward
-        self._emb_blocks = [m for m in self.modules() if isinstance(m, _EmbBlock) and hasattr(m, "local_embedder")]
+        self._emb_blocks = [m for m in self.modules() if isinstance(m, (_EmbBlock, B3._EmbBlock)) and hasattr(m, "local_embedder")]
         self._emb_cache_key = None
         self._emb_w = self._emb_b = None
         self._emb_off = {}
@@ -291,7 +307,7 @@ class UNet(nn.Module):
         K.rows_axpby(x_t, out=x2[B:])                  #  re-issues exactly those -- pipeline.py)
         if emb_cache is not None:
             h, _ = self.features(x2, None, None, None, emb_cache=emb_cache)
-            return self.outc(h)
+            return self._head(h)
         t2 = torch.cat([t, t], dim=0)
         time_emb = self.time_embedder(t2)              # [2B, E]
         if self.cond_embedder is not None:
@@ -300,7 +316,7 @@ class UNet(nn.Module):
                 K.embedding_add(tab, un_cond, time_emb[:B])
             K.embedding_add(tab, condition, time_emb[B:])
         h, _ = self.features(x2, None, None, None, emb_override=time_emb)
-        return self.outc(h)
+        return self._head(h)
 
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
@@ -310,6 +326,8 @@ class UNet(nn.Module):
             raise RuntimeError("medfusion_amd.UNet runs on a ROCm device only (no CPU fallback)")
         x_t = x_t.contiguous()
         _, lookup = self.embed(t, condition, emb_override, emb_cache)
+        if self.spatial_dims == 3:
+            return self._features3d(x_t, lookup)
         if self.use_self_conditioning:
             # reference concatenates zeros if self_cond is None else x_t ITSELF (unet2.py:245)
             a = K.nchw_to_nhwc(x_t)
@@ -333,6 +351,28 @@ class UNet(nn.Module):
                 y_ver.append(self.outc_ver[depth - 1](hs))
             h = self.out_blocks[i - 1](hs, lookup, out_fp32=(i == 1) or not po)
         return h, y_ver[::-1]
+
+    def _features3d(self, x_t, lookup):
+        """features() at spatial_dims=3: x_t NCDHW [B, C, D, H, W]; activations are [B, D*H, W, C] views (blocks3d), the skip concats are
+        fused into the consuming convolutions, the input goes to its zero-padded pair operand in one launch"""
+        if x_t.dim() != 5:
+            raise RuntimeError(f"UNet(spatial_dims=3) takes NCDHW input, got shape {tuple(x_t.shape)}")
+        x = [self.in_conv(B3.from_ncdhw(x_t, -(-x_t.shape[1] // 32) * 32))]
+        for blk in self.in_blocks:
+            x.append(blk(x[-1], lookup) if isinstance(blk, SequentialEmb) else blk(x[-1]))
+        h = self.middle_block(x[-1], lookup)
+        y_ver = []
+        for i in range(len(self.out_blocks), 0, -1):
+            hs = (h, x.pop())
+            depth, j = i // (self.num_res_blocks + 1), i % (self.num_res_blocks + 1) - 1
+            if len(self.outc_ver) >= depth > 0 and j == 0:
+                y_ver.append(B3.to_ncdhw(self.outc_ver[depth - 1](hs)))
+            h = self.out_blocks[i - 1](hs, lookup)
+        return h, y_ver[::-1]
+
+    def _head(self, h):
+        """the 1x1 out convolution (unet2.py:267) -> NCHW / NCDHW"""
+        return B3.to_ncdhw(self.outc(h)) if self.spatial_dims == 3 else self.outc(h)
 
     def _pairs_only_outputs(self, shape) -> bool:
         """may the conv blocks skip the fp32 form of their outputs for an in_conv output of this shape?  Only when every reader is a fp16-pair
@@ -378,7 +418,7 @@ class UNet(nn.Module):
         """x_t [B,C,H,W] NCHW on the GPU; t [B] (long or float); condition [B] long | None.
         Returns (y NCHW, y_ver list) like unet2.py:222-269.  emb_cache: see `step_embeddings` (sampling loop only)."""
         h, y_ver = self.features(x_t, t, condition, self_cond, emb_cache=emb_cache)
-        return self.outc(h), y_ver
+        return self._head(h), y_ver
 
     @torch.no_grad()
     def forward_split(self, x_t, t=None, condition=None, self_cond=None, emb_cache=None):

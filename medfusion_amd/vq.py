@@ -42,11 +42,17 @@ class VectorQuantizer(nn.Module):
         return self.quantize(z, want_loss=True)
 
 
+def _only_2d(who: str, spatial_dims) -> None:
+    if spatial_dims != 2:
+        raise NotImplementedError(f"{who}(spatial_dims={spatial_dims}): the codebook / GAN embedders are built in 2-D only")
+
+
 class VQVAE(VAE):
     def __init__(self, in_channels=3, out_channels=3, spatial_dims=2, emb_channels=4, num_embeddings=8192, hid_chs=[32, 64, 128, 256],
                  kernel_sizes=[3, 3, 3, 3], strides=[1, 2, 2, 2], norm_name=("GROUP", {"num_groups": 32, "affine": True}), act_name=("Swish", {}),
                  dropout=0.0, use_res_block=True, deep_supervision=False, learnable_interpolation=True, use_attention="none", beta=0.25,
                  **_training_only):
+        _only_2d(type(self).__name__, spatial_dims)
         super().__init__(in_channels, out_channels, spatial_dims, emb_channels, hid_chs, kernel_sizes, strides, norm_name, act_name, dropout,
                          use_res_block, deep_supervision, learnable_interpolation, use_attention)
         # (re-assigning a registered child keeps its place: the state-dict order is the reference's, :241-296)
@@ -117,6 +123,7 @@ class VQGAN(_GanWrapper):
                  kernel_sizes=[3, 3, 3, 3], strides=[1, 2, 2, 2], norm_name=("GROUP", {"num_groups": 32, "affine": True}), act_name=("Swish", {}),
                  dropout=0.0, use_res_block=True, deep_supervision=False, learnable_interpolation=True, use_attention="none", beta=0.25,
                  **_training_only):
+        _only_2d(type(self).__name__, spatial_dims)
         super().__init__()
         self.vqvae = VQVAE(in_channels, out_channels, spatial_dims, emb_channels, num_embeddings, hid_chs, kernel_sizes, strides, norm_name,
                            act_name, dropout, use_res_block, deep_supervision, learnable_interpolation, use_attention, beta)
@@ -128,6 +135,7 @@ class VAEGAN(_GanWrapper):
     def __init__(self, in_channels=3, out_channels=3, spatial_dims=2, emb_channels=4, hid_chs=[64, 128, 256, 512], kernel_sizes=[3, 3, 3, 3],
                  strides=[1, 2, 2, 2], norm_name=("GROUP", {"num_groups": 8, "affine": True}), act_name=("Swish", {}), dropout=0.0,
                  use_res_block=True, deep_supervision=False, learnable_interpolation=True, use_attention="none", **_training_only):
+        _only_2d(type(self).__name__, spatial_dims)
         super().__init__()
         self.vqvae = VAE(in_channels, out_channels, spatial_dims, emb_channels, hid_chs, kernel_sizes, strides, norm_name, act_name, dropout,
                          use_res_block, deep_supervision, learnable_interpolation, use_attention)
