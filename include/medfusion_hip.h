@@ -214,7 +214,8 @@ int mf_conv2d_f16x2_pairs_out(const void* x1s, const void* x2s, const void* ws, 
  * instructions).  The 16 element-wise products summed over the input channels are 16 independent GEMMs; they run on the kernel of
  * mf_conv2d_f16x2 (fp16-pair operands, three product terms, fp32 accumulate, in-launch split-K tree), each row block with the weight slab of
  * its component.  Same values as the direct form to fp32 rounding -- a DIFFERENT summation, not the same bits (error vs fp64 in
- * profiles/r05_winograd_ab.txt); MF_CONV_FP32 / MF_CONV_FP32_SPLIT3_W3 (the exact arithmetics) never take this form.
+ * profiles/r05_winograd_ab.txt).  The exact arithmetics (MF_CONV_FP32 / MF_CONV_FP32_SPLIT3_W3) have their own entry points for this form since
+ * ABI 250 (mf_wino_f32_ok and below).
  *  mf_wino_ok(d): can `d` (3x3, stride 1, pad 1, upsample 0, NHWC, precision MF_CONV_FP32_F16X2, H and W even, C1 % 32 == C2 % 32 == 0,
  *    Cout in {64, 128, 256, 512, 1024}) run so?  mf_wino_preferred(d): ... AND is it the faster form on MI355X?  ABI 240: answered for ANY batch by
  *    a rule in (Cin, Cout, H W, N) fitted to the sweeps at B = 4 ... 69 (Cin Cout >= 190 (Cin + Cout), csrc/conv_f16x2_wino.inc) instead of the

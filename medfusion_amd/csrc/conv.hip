@@ -448,6 +448,9 @@ int make_plan(const MfConvDesc* d, Plan* pl) {
       for (const auto& k : kCfgs) if (k.id == id) pl->cfg = k;
       if (d->splitk_hint <= 0) {
         nk = Cin / pl->cfg.BK;
+        // split mode: the cap of the generic rule below on one truncating bf16-MFMA accumulation chain (<= 96 chunks of 32) holds here too; where the
+        // rule's chain is already that short (every published shape: Cin <= 2048) its choice stands
+        if (d->precision != MF_CONV_FP32 && d->precision != MF_CONV_BF16) while (cdiv(nk, sk) > 96 && sk < 16) sk *= 2;
         pl->nk_per_split = cdiv(nk, sk);
         pl->splitk = cdiv(nk, pl->nk_per_split);
         return MF_OK;

@@ -719,6 +719,7 @@ def conv2d_wino_gn_apply_f32(x1: torch.Tensor, u_packed: torch.Tensor, bias: Opt
     v2 = wino_input_f32(x2) if x2 is not None else None
     g = make_conv_desc(16 * n, 1, t, c1, c2, co, 1, 1, 0, 3, precision=d.precision)
     m = conv2d(v1.view(16 * n, 1, t, c1), u_packed, None, g, x2=None if v2 is None else v2.view(16 * n, 1, t, c2))
+    assert m.numel() == 16 * n * t * co, (tuple(m.shape), n, t, co)   # M [16][n T][Cout]: what the tail reads, no more
     if residual is not None:
         _need_f32(residual)
     out = torch.empty((n, h, w, co), dtype=torch.float32, device=x1.device)
@@ -868,7 +869,7 @@ def convert_conv_weight_bf16(w_packed: torch.Tensor) -> torch.Tensor:
 
 
 def conv_out_hw(d: L.MfConvDesc):
-    up = 1 if d.upsample else 0
+    up = 1 if d.upsample in (1, 2) else 0   # (upsample = 3, the component GEMM of a Winograd convolution, is a plain 1 x T 1x1: csrc/conv_plan.h)
     he, we = d.Hin << up, d.Win << up
     return (he + 2 * d.pad - d.KH) // d.stride + 1, (we + 2 * d.pad - d.KW) // d.stride + 1
 

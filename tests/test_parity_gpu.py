@@ -431,6 +431,47 @@ def test_fp32_mfma_with_the_winograd_form_opt_in(dev, published, conv_precision)
 
 
 @torch.no_grad()
+def test_exact_arithmetic_as_shipped_at_published_size(dev, published, conv_precision):
+    """CONV_PRECISION = 1 with WINOGRAD_F32 = 1, the exact arithmetic as shipped: the Winograd form where the pair arithmetic's rule prefers it and on
+    every shape up to 16 x 16, the direct form elsewhere.  The conv_precision fixture runs modes 0 and 2, which agree with mode 1 at the tiny golden
+    shapes; the published UNet runs a mix of both forms under mode 1 -- the Winograd form at the 16 x 16 and 8 x 8 levels, the direct form at 32 x 32
+    (256 -> 256 and 256 + 256 -> 256, which mode 2 takes in the Winograd form).  B = 4 and 16 against the oracle, with modes 0 and 2 next to it."""
+    if conv_precision != 0:
+        pytest.skip("runs once")
+    from medfusion_amd import blocks as BLK
+    ora, pipe = published
+    old = BLK.CONV_PRECISION, BLK.WINOGRAD_F32
+    try:
+        for b in (4, 16):
+            x = S.synth_input(f"pub256_shipped_x{b}", (b, 8, 32, 32))
+            t = torch.tensor([(731 + 97 * i) % 1000 for i in range(b)])
+            c = torch.tensor([i % 2 for i in range(b)])
+            want, _ = ora.noise_estimator(x, t, c)
+            got, err = {}, {}
+            for mode in (1, 0, 2):
+                BLK.CONV_PRECISION, BLK.WINOGRAD_F32 = 1, mode
+                got[mode] = pipe.noise_estimator(x.to(dev), t.to(dev), c.to(dev))[0].clone()
+                err[mode] = relerr_rows(got[mode], want)
+            BLK.CONV_PRECISION, BLK.WINOGRAD_F32 = 1, 1
+            again, _ = pipe.noise_estimator(x.to(dev), t.to(dev), c.to(dev))      # the producers write V themselves now
+            # which form each convolution took: its ("wino_f32", n, h, w, c1, c2, G, mode, split3) cache entry is the descriptor, or False (direct)
+            forms = {}
+            for m in pipe.noise_estimator.modules():
+                for key, ent in getattr(m, "_descs", {}).items():
+                    if key[0] == "wino_f32" and key[1] == b and key[8]:
+                        forms.setdefault((key[7], key[2]), set()).add(ent is not False)
+            print(f"[measured] exact bf16 triplets at published size, B = {b}: UNet per-sample relerr vs the oracle as shipped (WINOGRAD_F32 = 1: Winograd "
+                  f"at 16 x 16 and 8 x 8, direct at 32 x 32) {err[1]:.2e}; direct everywhere (0) {err[0]:.2e}; Winograd wherever possible (2) {err[2]:.2e}")
+            assert forms[(1, 32)] == {False} and forms[(1, 16)] == forms[(1, 8)] == {True}, forms     # as shipped: both forms in one UNet
+            assert forms[(2, 32)] == forms[(2, 16)] == forms[(2, 8)] == {True}, forms
+            assert all(e < TOL for e in err.values()), err
+            assert not torch.equal(got[1], got[0]) and not torch.equal(got[1], got[2])     # (the shipped mix is neither of the other two)
+            assert torch.equal(again, got[1])
+    finally:
+        BLK.CONV_PRECISION, BLK.WINOGRAD_F32 = old
+
+
+@torch.no_grad()
 def test_published_unet_and_decode_vs_oracle_256px(dev, published):
     """Full published shapes: latent (8,32,32) -> 256x256 image.  Oracle evaluated on CPU on the same inputs."""
     ora, pipe = published

@@ -8,7 +8,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from oracle import synth as S
-from tests.util import relerr
+from tests.util import relerr, relerr_rows
 
 
 @pytest.fixture(scope="module")
@@ -405,3 +405,166 @@ def test_wino_f32_refuses_what_it_cannot_do(dev):
     assert not K.wino_f32_ok(K.make_conv_desc(3, 8, 8, 1024, 0, 1024, 3, 1, 1, 0, precision=3), 32)      # 48 tile rows per component: no tile
     assert not K.wino_f32_ok(K.make_conv_desc(2, 64, 64, 64, 0, 512, 3, 1, 1, 0, precision=3), 32)       # 64 x 64 x 16 channels do not fit in LDS
     assert K.wino_f32_ok(K.make_conv_desc(16, 16, 16, 512, 0, 512, 3, 1, 1, 0, precision=3), 32)
+
+
+# ---- the component GEMM of the exact-arithmetic form alone: mf_conv2d_f32 on the upsample = 3 descriptor against an fp64 GEMM per component.
+# (n, H, W, C1, C2, Cout): one shape per outcome of the planner's rule (tests/test_wino_exact_cpu.py::RULE_OUTCOMES), the long-K cases among them
+WINO_GEMM_CASES = [
+    (16, 16, 16, 512, 0, 512),      # 128 x 256, split-K 1
+    (16, 8, 8, 1024, 0, 1024),      # 128 x 128, split-K 1
+    (8, 8, 8, 1024, 0, 1024),       # 128 x 128, split-K 2
+    (4, 8, 8, 4096, 0, 1024),       # 64 x 128; 128 chunks of 32: split-K 2 on the bf16 triplets (the chain cap)
+    (4, 8, 8, 2048, 2048, 1024),    # the same K from two sources
+    (4, 8, 8, 256, 0, 192),         # Cout % 128 != 0: the generic rule (64 x 64; BK = 64 on the fp32 MFMA kernel)
+    (64, 2, 2, 64, 0, 64),          # T = 1: one pixel tile per sample
+]
+
+
+def _gemm_operands(case, dev, seed, cancel=False):
+    """V [16, n, T, C1 (+ C2)] and U [16, Cout, 1, 1, Cin] fp32.  cancel: channels come in pairs whose products nearly cancel (V: a, -a + 1e-3 r;
+    U: b, b + 1e-3 r'), so every sum is ~1e-3 of the magnitude of its summands."""
+    n, h, w, c1, c2, co = case
+    t, cin = (h // 2) * (w // 2), c1 + c2
+    g = torch.Generator(device=dev).manual_seed(seed)
+    v = torch.randn((16, n, t, cin), generator=g, device=dev)
+    u = torch.randn((16, co, 1, 1, cin), generator=g, device=dev) / np.sqrt(cin)
+    if cancel:
+        v[..., 1::2] = -v[..., 0::2] + 1e-3 * torch.randn(v[..., 1::2].shape, generator=g, device=dev)
+        u[..., 1::2] = u[..., 0::2] + 1e-3 * torch.randn(u[..., 1::2].shape, generator=g, device=dev) / np.sqrt(cin)
+    v1, v2 = v[..., :c1].contiguous(), (v[..., c1:].contiguous() if c2 else None)
+    m64 = torch.bmm(v.double().reshape(16, n * t, cin), u.double().reshape(16, co, cin).transpose(1, 2))
+    scale = torch.bmm(v.double().abs().reshape(16, n * t, cin), u.double().abs().reshape(16, co, cin).transpose(1, 2))   # sum |U| |V| per element
+    return v1, v2, u, m64, scale
+
+
+def _gemm_run(case, v1, v2, w, prec, sk=0):
+    from medfusion_amd import kernels as K
+    n, h, w_, c1, c2, co = case
+    t = (h // 2) * (w_ // 2)
+    g = K.make_conv_desc(16 * n, 1, t, c1, c2, co, 1, 1, 0, 3, splitk_hint=sk, precision=prec)
+    m = K.conv2d(v1.view(16 * n, 1, t, c1), w, None, g, x2=None if v2 is None else v2.view(16 * n, 1, t, c2))
+    assert m.shape == (16 * n, 1, t, co), m.shape
+    return m.view(16, n * t, co), K.conv_plan(g)
+
+
+def _per_sample(m, m64, n):
+    """per-sample relerr of M [16, n T, Cout]: the rows of one component of one sample are a sample"""
+    return relerr_rows(m.reshape(16 * n, -1), m64.reshape(16 * n, -1))
+
+
+@pytest.mark.parametrize("case", WINO_GEMM_CASES, ids=lambda c: "x".join(str(v) for v in c))
+def test_wino_component_gemm_on_the_exact_arithmetics(dev, case):
+    """The 16 component GEMMs of the exact-arithmetic Winograd form on their own (what conv2d_wino_gn_apply_f32 hands to mf_conv2d_f32): fp32 MFMA and
+    bf16 triplets against an fp64 GEMM per component -- per-sample relerr < 1e-5, the triplets within 3x the fp32 MFMA kernel's error + 1e-6 (the
+    criterion of test_conv_igemm_split_bf16x3 wherever one chain is <= 96 chunks, which the planner now keeps), on sums that cancel an error within
+    2e-6 of sum |U| |V| per element (test_conv_split_bf16x3_wide_dynamic_range), and bit-identical repeats."""
+    from medfusion_amd import kernels as K
+    n = case[0]
+    v1, v2, u, m64, _ = _gemm_operands(case, dev, 11)
+    u3 = K.split_conv_weight(u)
+    m0, plan0 = _gemm_run(case, v1, v2, u, 0)
+    m3, plan3 = _gemm_run(case, v1, v2, u3, 3)
+    e0, e3 = _per_sample(m0, m64, n), _per_sample(m3, m64, n)
+    print(f"[measured] component GEMM {case}: per-sample relerr vs fp64 -- fp32 MFMA {e0:.2e} (plan {plan0}), bf16 triplets {e3:.2e} (plan {plan3})")
+    assert e0 < 1e-5 and e3 < 1e-5, (case, e0, e3)
+    assert -(-(case[3] + case[4]) // 32 // plan3[1]) <= 96, plan3
+    assert e3 <= 3 * e0 + 1e-6, (case, e0, e3)
+    assert torch.equal(_gemm_run(case, v1, v2, u3, 3)[0], m3) and torch.equal(_gemm_run(case, v1, v2, u, 0)[0], m0)
+    v1, v2, u, m64, scale = _gemm_operands(case, dev, 12, cancel=True)
+    for prec, w in ((0, u), (3, K.split_conv_weight(u))):
+        m, _ = _gemm_run(case, v1, v2, w, prec)
+        r = float(((m.double() - m64).abs() / scale.clamp_min(1e-30)).max())
+        assert r < 2e-6, (case, prec, r)
+
+
+def test_wino_component_gemm_split_k_hints_on_a_long_k(dev):
+    """splitk_hint 1 ... 16 on the 128-chunk component GEMM (n = 4, 8 x 8, 4096 -> 1024): every hint is taken as written and gives an fp32-class
+    result; where one chain is <= 96 chunks the triplets hold 3x the fp32 MFMA kernel's error.  split-K 1 is the 128-chunk chain the planner used to
+    pick: its error is reported next to the planner's own choice."""
+    from medfusion_amd import kernels as K
+    case = (4, 8, 8, 4096, 0, 1024)
+    n = case[0]
+    v1, v2, u, m64, _ = _gemm_operands(case, dev, 13)
+    u3 = K.split_conv_weight(u)
+    e0 = _per_sample(_gemm_run(case, v1, v2, u, 0)[0], m64, n)
+    m_plan, plan = _gemm_run(case, v1, v2, u3, 3)
+    errs = {}
+    for sk in (1, 2, 4, 8, 16):
+        m, (tile, got_sk) = _gemm_run(case, v1, v2, u3, 3, sk=sk)
+        assert (tile, got_sk) == (3, sk)
+        errs[sk] = _per_sample(m, m64, n)
+        assert errs[sk] < 1e-5, (sk, errs[sk])
+        if 128 / sk <= 96:
+            assert errs[sk] <= 3 * e0 + 1e-6, (sk, errs[sk], e0)
+        assert torch.equal(_gemm_run(case, v1, v2, u3, 3, sk=sk)[0], m), sk
+        if sk == plan[1]:
+            assert torch.equal(m, m_plan)
+    print(f"[measured] 128-chunk component GEMM {case}: per-sample relerr vs fp64, bf16 triplets by split-K "
+          + ", ".join(f"{sk}: {e:.2e}" for sk, e in errs.items()) + f" (before the chain cap: split-K 1; now {plan[1]}); fp32 MFMA {e0:.2e}")
+
+
+# ---- the whole exact-arithmetic form at the edges of its planning: (N, H, W, C1, C2, Cout, G, per-sample input scales or None)
+WINO_F32_EDGE_CASES = [
+    (4, 8, 8, 2048, 2048, 512, 32, None),           # long K from two sources: the component GEMM splits K for the chain cap
+    (64, 2, 2, 64, 0, 64, 8, None),                 # T = 1
+    (4, 8, 16, 256, 0, 256, 32, None),              # non-square
+    (4, 16, 8, 128, 128, 256, 32, None),            # non-square, two sources
+    (2, 32, 32, 128, 0, 256, 16, None),             # the tail's LDS exactly full: 32 x 32 pixels x 16 channels x 4 bytes = 64 KB
+    (4, 8, 8, 512, 0, 512, 32, (1e3, 1e-3, 1.0, 30.0)),   # samples 1e6 apart
+]
+
+
+_EDGE_REF = {}   # case -> the fp64 chain (shared by both arithmetics)
+
+
+@pytest.mark.parametrize("prec", [3, 0])
+@pytest.mark.parametrize("case", WINO_F32_EDGE_CASES, ids=lambda c: "x".join(str(v) for v in c[:7]) + ("_scaled" if c[7] else ""))
+def test_wino_f32_form_at_its_edges(dev, case, prec):
+    """conv3x3 -> GroupNorm -> Swish -> + residual -> + emb on the Winograd form of the exact arithmetics against the fp64 chain and against the direct
+    form of the same arithmetic, per sample (relerr_rows: an error confined to a small sample cannot hide behind a large one)."""
+    from medfusion_amd import kernels as K
+    n, h, w, c1, c2, co, G, scales = case
+    cin = c1 + c2
+    tag = f"edge{case}"
+    s = torch.tensor(scales if scales else [1.0] * n, dtype=torch.float32)[:, None, None, None]
+    x = _rand(f"x{tag}", (n, c1, h, w)) * s
+    x2 = _rand(f"y{tag}", (n, c2, h, w)) * s if c2 else None
+    wt = _rand(f"w{tag}", (co, cin, 3, 3), 1.0 / np.sqrt(cin * 9))
+    b = _rand(f"b{tag}", (co,), 0.1)
+    gamma, beta = 1.0 + 0.3 * _rand(f"g{tag}", (co,)), 0.2 * _rand(f"be{tag}", (co,))
+    res = _rand(f"r{tag}", (n, co, h, w), 2.0) * s
+    emb = _rand(f"e{tag}", (n, co), 0.5)
+    xd, x2d = K.nchw_to_nhwc(x.to(dev)), (K.nchw_to_nhwc(x2.to(dev)) if c2 else None)
+    resd, embd = K.nchw_to_nhwc(res.to(dev)), emb.to(dev)
+    d = K.make_conv_desc(n, h, w, c1, c2, co, 3, 1, 1, 0, precision=prec)
+    assert K.wino_f32_ok(d, G), case
+    u = K.wino_pack_weight(wt.to(dev))
+    got = K.conv2d_wino_gn_apply_f32(xd, K.split_conv_weight(u) if prec == 3 else u, b.to(dev), d, gamma.to(dev), beta.to(dev), G, 1e-5, act=1,
+                                     residual=resd, emb=embd, emb_stride=embd.stride(0), x2=x2d)
+    wp = K.pack_conv_weight(wt.to(dev))
+    y = K.conv2d(xd, K.split_conv_weight(wp) if prec == 3 else wp, b.to(dev), d, x2=x2d)
+    ref = K.gn_apply(y, K.gn_stats(y, G, 1e-5), gamma.to(dev), beta.to(dev), G, 1, resd, embd, embd.stride(0))
+    if case not in _EDGE_REF:
+        xin = x if x2 is None else torch.cat([x, x2], 1)
+        t64 = F.group_norm(F.conv2d(xin.double(), wt.double(), b.double(), padding=1), G, gamma.double(), beta.double(), 1e-5)
+        _EDGE_REF[case] = t64 * torch.sigmoid(t64) + res.double() + emb.double()[:, :, None, None]
+    t64 = _EDGE_REF[case]
+    e64, e64d = relerr_rows(K.nhwc_to_nchw(got), t64), relerr_rows(K.nhwc_to_nchw(ref), t64)
+    e_direct = relerr_rows(got, ref)
+    print(f"[measured] winograd edge {case} precision {prec}: per-sample vs fp64 chain {e64:.2e} (direct form: {e64d:.2e}); vs the direct form {e_direct:.2e}")
+    assert e64 < 5e-6 and e_direct < 5e-6, (case, prec, e64, e_direct)
+
+
+def test_wino_f32_tail_refuses_past_its_lds(dev):
+    """one step past the tail's LDS (32 x 32 pixels x 32 channels per group = 128 KB, or 32 x 64 x 16): not admitted, and the tail itself refuses
+    before launching anything"""
+    from medfusion_amd import kernels as K, lib as L
+    assert K.wino_f32_ok(K.make_conv_desc(2, 32, 32, 128, 0, 256, 3, 1, 1, 0, precision=3), 16)
+    assert not K.wino_f32_ok(K.make_conv_desc(2, 32, 32, 128, 0, 256, 3, 1, 1, 0, precision=3), 8)
+    assert not K.wino_f32_ok(K.make_conv_desc(2, 32, 64, 128, 0, 256, 3, 1, 1, 0, precision=3), 16)
+    for h, w, G in ((32, 32, 8), (32, 64, 16)):
+        m = torch.zeros((16, 2, (h // 2) * (w // 2), 256), dtype=torch.float32, device=dev)
+        out = torch.zeros((2, h, w, 256), dtype=torch.float32, device=dev)
+        rc = L.load().mf_wino_tail_f32(m.data_ptr(), None, None, None, None, None, 0, out.data_ptr(), None, 2, h, w, 256, G, 1, 1e-5, K.stream())
+        assert rc == -2, (h, w, G, rc)                    # MF_EUNSUPPORTED
+        assert not out.any()
