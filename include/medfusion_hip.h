@@ -416,6 +416,31 @@ int mf_sched_step_f32(const MfSchedArgs* a, void* stream);
  * must be NULL.  Replaces torch.randn_like x 2 + the ~49 elementwise ATen ops + the host loop counter of diffusion_pipeline.py:294-304. */
 int mf_sched_step_philox_f32(const MfSchedArgs* a, uint64_t seed, int32_t draw_base, int32_t draw_stride, int64_t sample_offset, int B,
                              int32_t* step_counter, uint32_t* ticket, void* stream);
+/* Inpainting inside the step's launch (img2img / masked sampling; additive to ABI 250).  After the step has produced the next latent, the cells
+ * the caller KEEPS take the known latent at the next timestep, built from the same draw every time:
+ *   x_t_out[i] = mask[sample][cell] ? x_t_out[i] : coef[step].a * z0[i] + coef[step].c * eps0[i]
+ * with the two products rounded separately and then the sum (mf_rows_axpby_f32's chain = GaussianNoiseScheduler.estimate_x_t,
+ * gaussian_scheduler.py:61-77, at t_next; (1, 0) after the last iteration: the kept cells end as z0).  x0_out / xT_out stay the estimator's
+ * estimates.  `step` is the index mf_sched_step_f32 uses for its MfSchedStep table (a->step / *a->step_dev, or *step_counter of the Philox form). */
+typedef struct MfSchedBlend {
+  const float* z0;       /* [n] the known latent (same layout as x_t: [B][channels][cells]) */
+  const float* eps0;     /* [n] the draw that diffused z0 to the loop's first timestep */
+  const uint8_t* mask;   /* [B][cells] one byte per latent cell: != 0 regenerate, 0 keep */
+  const float* coef;     /* device table of (a, c) pairs, one per loop iteration */
+  int64_t cells;         /* spatial cells per sample (h * w, or d * h * w) */
+  int32_t channels;      /* latent channels (the mask is broadcast over them) */
+  int32_t reserved;      /* 0 */
+} MfSchedBlend;
+int mf_sched_step_blend_f32(const MfSchedArgs* a, const MfSchedBlend* blend, void* stream);
+/* mf_sched_step_philox_f32 with the select above on its x_t_out, still ONE launch: cells % 4 == 0, z0 / eps0 16-byte and mask 4-byte aligned. */
+int mf_sched_step_philox_blend_f32(const MfSchedArgs* a, uint64_t seed, int32_t draw_base, int32_t draw_stride, int64_t sample_offset, int B,
+                                   int32_t* step_counter, uint32_t* ticket, const MfSchedBlend* blend, void* stream);
+/* out[n][c][cell] = mask[n][cell] ? a[n][c][cell] : b[n][c][cell] on NCHW / NCDHW fp32, the per-cell mask broadcast over the C channels: the
+ * pixel-space composite of inpainting and the un-fused form of the select above. */
+int mf_select_cells_f32(const uint8_t* mask, const float* a, const float* b, float* out, int N, int C, int64_t cells, void* stream);
+/* [N][1][D][H][W] mask (uint8: != 0; mask_is_f32 = 1: fp32 > 0.5; D = 1 in 2-D) -> [N][1][D/fd][H/fh][W/fw] uint8 0 / 1 by max over fd x fh x fw
+ * blocks: an image-resolution mask reduced to the latent's cells (a cell is regenerated if any of its pixels is). */
+int mf_mask_maxpool_u8(const void* mask, int mask_is_f32, uint8_t* out, int N, int D, int H, int W, int fd, int fh, int fw, void* stream);
 /* out[0..n) = table[step] with step = *step_dev (or `step`): `t.expand(B)` of diffusion_pipeline.py:294 inside a captured graph */
 int mf_broadcast_from_table_f32(const float* table, const int32_t* step_dev, int32_t step, float* out, int n, void* stream);
 /* out[b][:] = table[step][cols[b]][:] for a [S][ncol][row_len] table, step = *step_dev (or `step`): the per-iteration gather of the
@@ -530,6 +555,9 @@ int mf_pixel_shuffle2_add_nhwc_f32(const float* x, float* y, int N, int H, int W
  * mode 1: scripts/sample.py:49-51 + torchvision save_image(normalize=True, scale_each=True): (x+1)/2, clamp(0,1), per-image
  *         min-max, mul(255).add(0.5).clamp(0,255).to(uint8); minmax_ws = 2*N floats of caller scratch. */
 int mf_image_egress_u8(const float* x_nchw, uint8_t* out_nhwc, float* minmax_ws, int N, int C, int H, int W, int mode, void* stream);
+/* Image ingress, the inverse (additive to ABI 250): NHWC uint8 -> NCHW float in [-1, 1] by (x / 255 - 0.5) / 0.5, bit-exact against
+ * tF.normalize(x / 255, 0.5, 0.5) (scripts/evaluate_latent_embedder.py:77). */
+int mf_image_ingress_u8(const uint8_t* x_nhwc, float* out_nchw, int N, int C, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------ built-in launch timing (bench / roofline)
  * When enabled every launch is bracketed by hipEvents on its own stream and attributed to a kernel family.

@@ -131,6 +131,68 @@ __global__ void image_u8_normalized_kernel(const float* __restrict__ x, const fl
   out[i] = (uint8_t)v;
 }
 
+
+// uint8 NHWC -> fp32 NCHW in [-1, 1]: tF.normalize(x / 255, 0.5, 0.5) = (x / 255 - 0.5) / 0.5, each step rounded like torch's chain -- the
+// inverse of image_u8_dataset_kernel.  One thread per OUTPUT element (coalesced fp32 stores; the byte reads of a pixel's C channels share a line).
+__global__ __launch_bounds__(256) void image_ingress_kernel(const uint8_t* __restrict__ x, float* __restrict__ out, int N, int C, int H, int W) {
+#pragma clang fp contract(off)
+  const long total = (long)N * C * H * W;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int w = (int)(i % W);
+    long t = i / W;
+    const int h = (int)(t % H); t /= H;
+    const int c = (int)(t % C);
+    const int n = (int)(t / C);
+    float v = (float)x[(((long)n * H + h) * W + w) * C + c];
+    v = v / 255.0f;
+    v = v - 0.5f;
+    v = v / 0.5f;
+    out[i] = v;
+  }
+}
+
+// [N][1][D][H][W] mask (uint8 != 0, or fp32 > 0.5) -> [N][1][D/fd][H/fh][W/fw] uint8 (0 / 1) by max over each fd x fh x fw block: a latent cell is
+// regenerated if any of its pixels is masked.  One thread per output cell.
+template <typename TM>
+__global__ __launch_bounds__(256) void mask_maxpool_kernel(const TM* __restrict__ m, uint8_t* __restrict__ out, int N, int D, int H, int W, int fd, int fh, int fw) {
+  const int d = D / fd, h = H / fh, w = W / fw;
+  const long total = (long)N * d * h * w;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int ox = (int)(i % w);
+    long t = i / w;
+    const int oy = (int)(t % h); t /= h;
+    const int oz = (int)(t % d);
+    const int n = (int)(t / d);
+    bool any = false;
+    for (int z = 0; z < fd; ++z)
+      for (int y = 0; y < fh; ++y) {
+        const TM* row = m + ((((long)n * D + oz * fd + z) * H + oy * fh + y) * W + (long)ox * fw);
+        for (int k = 0; k < fw; ++k) any = any || (sizeof(TM) == 1 ? row[k] != (TM)0 : (float)row[k] > 0.5f);
+      }
+    out[i] = any ? 1 : 0;
+  }
+}
+
+// out[n][c][cell] = mask[n][cell] ? a : b  (the per-cell mask broadcast over channels); VEC: four cells per thread (cells % 4 == 0)
+template <bool VEC>
+__global__ __launch_bounds__(256) void select_cells_kernel(const uint8_t* __restrict__ mask, const float* __restrict__ a, const float* __restrict__ b,
+                                                            float* __restrict__ out, long cells, long per, long total) {
+  const long stride = (long)gridDim.x * blockDim.x;
+  if (VEC) {
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < (total >> 2); q += stride) {
+      const long i = q * 4, n = i / per, cell = (i - n * per) % cells;
+      const uchar4 m = *reinterpret_cast<const uchar4*>(mask + n * cells + cell);
+      const float4 va = *reinterpret_cast<const float4*>(a + i), vb = *reinterpret_cast<const float4*>(b + i);
+      *reinterpret_cast<float4*>(out + i) = make_float4(m.x ? va.x : vb.x, m.y ? va.y : vb.y, m.z ? va.z : vb.z, m.w ? va.w : vb.w);
+    }
+  } else {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+      const long n = i / per, cell = (i - n * per) % cells;
+      out[i] = mask[n * cells + cell] ? a[i] : b[i];
+    }
+  }
+}
+
 }  // namespace
 
 // nn.AvgPool2d(k, stride, pad) with count_include_pad (torch's default), NHWC: the window is clipped to the PADDED extent for the divisor and
@@ -293,6 +355,50 @@ int mf_image_egress_u8(const float* x_nchw, uint8_t* out_nhwc, float* minmax_ws,
   if (rc) return rc;
   MF_LAUNCH(image_u8_normalized_kernel, dim3(blocks), dim3(256), 0, s, x_nchw, minmax_ws, out_nhwc, N, C, H, W);
   return check_launch("image_egress_normalized");
+}
+
+int mf_image_ingress_u8(const uint8_t* x_nhwc, float* out_nchw, int N, int C, int H, int W, void* stream) {
+  MF_REQUIRE(x_nhwc && out_nchw && N > 0 && C > 0 && H > 0 && W > 0, MF_EINVAL, "image_ingress: bad args");
+  hipStream_t s = (hipStream_t)stream;
+  const long total = (long)N * C * H * W;
+  ProfScope ps(MF_FAM_MISC, s, 3.0 * total, 5.0 * total);
+  long blocks = (total + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  MF_LAUNCH(image_ingress_kernel, dim3((int)blocks), dim3(256), 0, s, x_nhwc, out_nchw, N, C, H, W);
+  return check_launch("image_ingress");
+}
+
+int mf_mask_maxpool_u8(const void* mask, int mask_is_f32, uint8_t* out, int N, int D, int H, int W, int fd, int fh, int fw, void* stream) {
+  MF_REQUIRE(mask && out && N > 0 && D > 0 && H > 0 && W > 0 && fd > 0 && fh > 0 && fw > 0, MF_EINVAL, "mask_maxpool: bad args");
+  MF_REQUIRE(D % fd == 0 && H % fh == 0 && W % fw == 0, MF_EINVAL, "mask_maxpool: %d x %d x %d is not a whole number of %d x %d x %d blocks", D, H, W, fd, fh, fw);
+  MF_REQUIRE(mask_is_f32 == 0 || mask_is_f32 == 1, MF_EINVAL, "mask_maxpool: mask_is_f32");
+  hipStream_t s = (hipStream_t)stream;
+  const long total = (long)N * (D / fd) * (H / fh) * (W / fw);
+  ProfScope ps(MF_FAM_MISC, s, 0, (mask_is_f32 ? 4.0 : 1.0) * N * (double)D * H * W + total);
+  long blocks = (total + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  if (mask_is_f32) {
+    MF_LAUNCH(mask_maxpool_kernel<float>, dim3((int)blocks), dim3(256), 0, s, static_cast<const float*>(mask), out, N, D, H, W, fd, fh, fw);
+  } else {
+    MF_LAUNCH(mask_maxpool_kernel<uint8_t>, dim3((int)blocks), dim3(256), 0, s, static_cast<const uint8_t*>(mask), out, N, D, H, W, fd, fh, fw);
+  }
+  return check_launch("mask_maxpool");
+}
+
+int mf_select_cells_f32(const uint8_t* mask, const float* a, const float* b, float* out, int N, int C, int64_t cells, void* stream) {
+  MF_REQUIRE(mask && a && b && out && N > 0 && C > 0 && cells > 0, MF_EINVAL, "select_cells: bad args");
+  hipStream_t s = (hipStream_t)stream;
+  const long per = (long)C * cells, total = (long)N * per;
+  ProfScope ps(MF_FAM_MISC, s, 0, 12.0 * total + (double)N * cells);
+  const bool vec = cells % 4 == 0 && ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 15) == 0) && (((uintptr_t)mask & 3) == 0);
+  long blocks = ((vec ? total / 4 : total) + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  if (vec) {
+    MF_LAUNCH(select_cells_kernel<true>, dim3((int)blocks), dim3(256), 0, s, mask, a, b, out, (long)cells, per, total);
+  } else {
+    MF_LAUNCH(select_cells_kernel<false>, dim3((int)blocks), dim3(256), 0, s, mask, a, b, out, (long)cells, per, total);
+  }
+  return check_launch("select_cells");
 }
 
 }  // extern "C"

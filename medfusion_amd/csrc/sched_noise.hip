@@ -60,16 +60,36 @@ __device__ __forceinline__ SchedOut sched_elem(const MfSchedArgs& a, const MfSch
   return SchedOut{xn, x0, xT};
 }
 
-__global__ __launch_bounds__(256) void sched_step_kernel(const MfSchedArgs a) {
+// Inpainting (MfSchedBlend): the kept cells of the next latent take the known latent at the next timestep, a * z0 + c * eps0 with the two
+// products rounded separately (rows_axpby_kernel's chain), (a, c) = coef[step].  BL == false compiles the select away.
+struct BlendCoef { float a, c; };
+__device__ __forceinline__ BlendCoef blend_coef(const MfSchedBlend& bl, int step) { return BlendCoef{bl.coef[2 * step], bl.coef[2 * step + 1]}; }
+__device__ __forceinline__ float blend_elem(float xn, float z0, float e0, bool regen, BlendCoef k) {
+#pragma clang fp contract(off)
+  const float p1 = k.a * z0;
+  const float p2 = k.c * e0;
+  const float kn = p1 + p2;
+  return regen ? xn : kn;
+}
+
+template <bool BL>
+__global__ __launch_bounds__(256) void sched_step_kernel(const MfSchedArgs a, const MfSchedBlend bl) {
 #pragma clang fp contract(off)
   const int step = a.step_dev ? *a.step_dev : a.step;
   const MfSchedStep S = a.table[step];
   const float* npost = a.noise_post ? a.noise_post + (long)step * a.noise_step_stride : nullptr;
   const float* nddim = a.noise_ddim ? a.noise_ddim + (long)step * a.noise_step_stride : nullptr;
+  const BlendCoef k = BL ? blend_coef(bl, step) : BlendCoef{0.f, 0.f};
+  const long per = BL ? bl.cells * bl.channels : 1;
   const long stride = (long)gridDim.x * blockDim.x;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) {
-    const SchedOut o = sched_elem(a, S, a.x_t[i], a.pred[i], a.pred_uncond ? a.pred_uncond[i] : 0.f, a.pred_var ? a.pred_var[i] : 0.f, npost ? npost[i] : 0.0f,
-                                  nddim ? nddim[i] : 0.0f);
+    SchedOut o = sched_elem(a, S, a.x_t[i], a.pred[i], a.pred_uncond ? a.pred_uncond[i] : 0.f, a.pred_var ? a.pred_var[i] : 0.f, npost ? npost[i] : 0.0f,
+                            nddim ? nddim[i] : 0.0f);
+    if (BL) {
+      const long b = i / per;
+      const long cell = (i - b * per) % bl.cells;
+      o.xn = blend_elem(o.xn, bl.z0[i], bl.eps0[i], bl.mask[b * bl.cells + cell] != 0, k);
+    }
     a.x_t_out[i] = o.xn;
     if (a.x0_out) a.x0_out[i] = o.x0;
     if (a.xT_out) a.xT_out[i] = o.xT;
@@ -148,10 +168,12 @@ __global__ __launch_bounds__(256) void philox_normal_kernel(float* __restrict__ 
 // every workgroup has read the counter before it takes its ticket) -- four launches of the loop body become one.
 struct PhiloxP { uint32_t seed_lo, seed_hi; int draw_base, draw_stride; long sample_offset, quads_per_sample; int32_t* step_rw; uint32_t* ticket; };
 
-__global__ __launch_bounds__(256) void sched_step_philox_kernel(const MfSchedArgs a, const PhiloxP ph) {
+template <bool BL>
+__global__ __launch_bounds__(256) void sched_step_philox_kernel(const MfSchedArgs a, const PhiloxP ph, const MfSchedBlend bl) {
 #pragma clang fp contract(off)
   const int step = *ph.step_rw;
   const MfSchedStep S = a.table[step];
+  const BlendCoef k = BL ? blend_coef(bl, step) : BlendCoef{0.f, 0.f};
   const uint32_t draw = (uint32_t)(ph.draw_base + ph.draw_stride * step);
   const bool ddim = S.mode == 1;
   const long total = a.n >> 2;
@@ -166,7 +188,15 @@ __global__ __launch_bounds__(256) void sched_step_philox_kernel(const MfSchedArg
     const float4 pv = a.pred_var ? *reinterpret_cast<const float4*>(a.pred_var + i * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
     const SchedOut o0 = sched_elem(a, S, xt.x, pr.x, pu.x, pv.x, np.x, nd.x), o1 = sched_elem(a, S, xt.y, pr.y, pu.y, pv.y, np.y, nd.y);
     const SchedOut o2 = sched_elem(a, S, xt.z, pr.z, pu.z, pv.z, np.z, nd.z), o3 = sched_elem(a, S, xt.w, pr.w, pu.w, pv.w, np.w, nd.w);
-    *reinterpret_cast<float4*>(a.x_t_out + i * 4) = make_float4(o0.xn, o1.xn, o2.xn, o3.xn);
+    float4 xn = make_float4(o0.xn, o1.xn, o2.xn, o3.xn);
+    if (BL) {   // (cells % 4 == 0: a quad lies inside one channel plane, its four cells are consecutive mask bytes)
+      const float4 z = *reinterpret_cast<const float4*>(bl.z0 + i * 4), e = *reinterpret_cast<const float4*>(bl.eps0 + i * 4);
+      const long cell = (q * 4) % bl.cells;
+      const uchar4 m = *reinterpret_cast<const uchar4*>(bl.mask + b * bl.cells + cell);
+      xn = make_float4(blend_elem(xn.x, z.x, e.x, m.x != 0, k), blend_elem(xn.y, z.y, e.y, m.y != 0, k), blend_elem(xn.z, z.z, e.z, m.z != 0, k),
+                       blend_elem(xn.w, z.w, e.w, m.w != 0, k));
+    }
+    *reinterpret_cast<float4*>(a.x_t_out + i * 4) = xn;
     if (a.x0_out) *reinterpret_cast<float4*>(a.x0_out + i * 4) = make_float4(o0.x0, o1.x0, o2.x0, o3.x0);
     if (a.xT_out) *reinterpret_cast<float4*>(a.xT_out + i * 4) = make_float4(o0.xT, o1.xT, o2.xT, o3.xT);
   }
@@ -194,25 +224,35 @@ __global__ __launch_bounds__(256) void gather_step_rows3_kernel(const GatherSeg 
   }
 }
 
-}  // namespace
+// ---- host side of the two step launches: one body each for the plain and the blended entry point
+const MfSchedBlend kNoBlend = {nullptr, nullptr, nullptr, nullptr, 0, 0, 0};
 
-extern "C" {
+// the blend state against the step's element count: every sample is `channels` planes of `cells` values
+int check_blend(const MfSchedArgs* a, const MfSchedBlend* bl, const char* who) {
+  MF_REQUIRE(bl && bl->z0 && bl->eps0 && bl->mask && bl->coef && bl->cells > 0 && bl->channels > 0, MF_EINVAL, "%s: bad blend state", who);
+  MF_REQUIRE(a->n % (bl->cells * (int64_t)bl->channels) == 0, MF_EINVAL, "%s: n is not a whole number of samples of channels x cells", who);
+  return MF_OK;
+}
 
-int mf_sched_step_f32(const MfSchedArgs* a, void* stream) {
+int sched_step_launch(const MfSchedArgs* a, const MfSchedBlend* bl, void* stream) {
   MF_REQUIRE(a && a->x_t && a->pred && a->x_t_out && a->table && a->n > 0, MF_EINVAL, "sched_step: bad args");
   MF_REQUIRE(a->objective == 0 || a->objective == 1, MF_EINVAL, "sched_step: objective");
   MF_REQUIRE(!(a->pred_var && a->pred_uncond), MF_EUNSUPPORTED,
              "sched_step: learned variance with classifier-free guidance is unreachable in the reference (it raises)");
   hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(MF_FAM_SCHED, s, 12.0 * a->n, 4.0 * a->n * 6);
+  ProfScope ps(MF_FAM_SCHED, s, (bl ? 15.0 : 12.0) * a->n, 4.0 * a->n * (bl ? 8 : 6));
   long blocks = (a->n + 255) / 256;
   if (blocks > 1024) blocks = 1024;
-  MF_LAUNCH(sched_step_kernel, dim3((int)blocks), dim3(256), 0, s, *a);
+  if (bl) {
+    MF_LAUNCH(sched_step_kernel<true>, dim3((int)blocks), dim3(256), 0, s, *a, *bl);
+  } else {
+    MF_LAUNCH(sched_step_kernel<false>, dim3((int)blocks), dim3(256), 0, s, *a, kNoBlend);
+  }
   return check_launch("sched_step");
 }
 
-int mf_sched_step_philox_f32(const MfSchedArgs* a, uint64_t seed, int32_t draw_base, int32_t draw_stride, int64_t sample_offset, int B, int32_t* step_counter,
-                             uint32_t* ticket, void* stream) {
+int sched_step_philox_launch(const MfSchedArgs* a, uint64_t seed, int32_t draw_base, int32_t draw_stride, int64_t sample_offset, int B, int32_t* step_counter,
+                             uint32_t* ticket, const MfSchedBlend* bl, void* stream) {
   MF_REQUIRE(a && a->x_t && a->pred && a->x_t_out && a->table && a->n > 0 && step_counter && ticket && B > 0, MF_EINVAL, "sched_step_philox: bad args");
   MF_REQUIRE(a->objective == 0 || a->objective == 1, MF_EINVAL, "sched_step_philox: objective");
   MF_REQUIRE(!(a->pred_var && a->pred_uncond), MF_EUNSUPPORTED,
@@ -224,12 +264,45 @@ int mf_sched_step_philox_f32(const MfSchedArgs* a, uint64_t seed, int32_t draw_b
   MF_REQUIRE((al & 15) == 0, MF_EINVAL, "sched_step_philox: tensors must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const long quads = a->n / 4;
-  ProfScope ps(MF_FAM_SCHED, s, 12.0 * a->n + 200.0 * quads, 4.0 * a->n * 4);
+  ProfScope ps(MF_FAM_SCHED, s, (bl ? 15.0 : 12.0) * a->n + 200.0 * quads, 4.0 * a->n * (bl ? 6 : 4));
   long blocks = (quads + 255) / 256;
   if (blocks > 1024) blocks = 1024;
   const PhiloxP ph{(uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), draw_base, draw_stride, (long)sample_offset, quads / B, step_counter, ticket};
-  MF_LAUNCH(sched_step_philox_kernel, dim3((int)blocks), dim3(256), 0, s, *a, ph);
+  if (bl) {
+    MF_LAUNCH(sched_step_philox_kernel<true>, dim3((int)blocks), dim3(256), 0, s, *a, ph, *bl);
+  } else {
+    MF_LAUNCH(sched_step_philox_kernel<false>, dim3((int)blocks), dim3(256), 0, s, *a, ph, kNoBlend);
+  }
   return check_launch("sched_step_philox");
+}
+
+}  // namespace
+
+extern "C" {
+
+int mf_sched_step_f32(const MfSchedArgs* a, void* stream) { return sched_step_launch(a, nullptr, stream); }
+
+int mf_sched_step_blend_f32(const MfSchedArgs* a, const MfSchedBlend* bl, void* stream) {
+  MF_REQUIRE(a, MF_EINVAL, "sched_step_blend: bad args");
+  const int rc = check_blend(a, bl, "sched_step_blend");
+  return rc ? rc : sched_step_launch(a, bl, stream);
+}
+
+int mf_sched_step_philox_f32(const MfSchedArgs* a, uint64_t seed, int32_t draw_base, int32_t draw_stride, int64_t sample_offset, int B, int32_t* step_counter,
+                             uint32_t* ticket, void* stream) {
+  return sched_step_philox_launch(a, seed, draw_base, draw_stride, sample_offset, B, step_counter, ticket, nullptr, stream);
+}
+
+int mf_sched_step_philox_blend_f32(const MfSchedArgs* a, uint64_t seed, int32_t draw_base, int32_t draw_stride, int64_t sample_offset, int B,
+                                   int32_t* step_counter, uint32_t* ticket, const MfSchedBlend* bl, void* stream) {
+  MF_REQUIRE(a, MF_EINVAL, "sched_step_philox_blend: bad args");
+  const int rc = check_blend(a, bl, "sched_step_philox_blend");
+  if (rc) return rc;
+  MF_REQUIRE(bl->cells % 4 == 0, MF_EUNSUPPORTED, "sched_step_philox_blend: cells per sample must be a multiple of 4");
+  MF_REQUIRE(B > 0 && a->n == (int64_t)B * bl->cells * bl->channels, MF_EINVAL, "sched_step_philox_blend: n != B x channels x cells");
+  MF_REQUIRE((((uintptr_t)bl->z0 | (uintptr_t)bl->eps0) & 15) == 0 && ((uintptr_t)bl->mask & 3) == 0, MF_EINVAL,
+             "sched_step_philox_blend: z0 / eps0 must be 16-byte aligned, mask 4-byte aligned");
+  return sched_step_philox_launch(a, seed, draw_base, draw_stride, sample_offset, B, step_counter, ticket, bl, stream);
 }
 
 int mf_gather_step_rows3_f32(const float* const* tables, const int64_t* row_lens, float* const* outs, int n_tables, const int64_t* cols, const int32_t* step_dev,

@@ -1126,6 +1126,72 @@ def sched_step_philox(args: L.MfSchedArgs, seed: int, draw_base: int, draw_strid
                                               counter.data_ptr() + 4, stream()), "mf_sched_step_philox_f32")
 
 
+def image_ingress(x_nhwc: torch.Tensor) -> torch.Tensor:
+    """[N,H,W,C] uint8 -> [N,C,H,W] float in [-1,1] on the device: (x/255 - 0.5)/0.5, bit-exact vs tF.normalize(x/255, 0.5, 0.5) (mf_image_ingress_u8)."""
+    _gpu(x_nhwc)
+    if x_nhwc.dtype != torch.uint8 or x_nhwc.dim() != 4:
+        raise ValueError("image_ingress: a [N, H, W, C] uint8 tensor")
+    x = x_nhwc.contiguous()
+    n, h, w, c = x.shape
+    out = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
+    L.check(L.load().mf_image_ingress_u8(x.data_ptr(), out.data_ptr(), n, c, h, w, stream()), "mf_image_ingress_u8")
+    return out
+
+
+def mask_maxpool(mask: torch.Tensor, factors) -> torch.Tensor:
+    """[N,1,H,W] / [N,1,D,H,W] mask (bool / uint8: != 0; floating point: > 0.5) -> uint8 0 / 1 at 1 / factors of the size by max over each block
+    (mf_mask_maxpool_u8); factors: one int per spatial axis"""
+    if mask.dtype == torch.bool:
+        mask = mask.to(torch.uint8)
+    _gpu(mask)
+    if mask.dim() not in (4, 5) or mask.shape[1] != 1 or len(factors) != mask.dim() - 2:
+        raise ValueError(f"mask_maxpool: a [N, 1, ...] mask and one factor per spatial axis, got {tuple(mask.shape)} and {tuple(factors)}")
+    is_f = mask.is_floating_point()
+    m = (mask.to(torch.float32) if is_f else mask.to(torch.uint8)).contiguous()
+    sp, f = list(m.shape[2:]), [int(v) for v in factors]
+    if len(sp) == 2:
+        sp, f = [1] + sp, [1] + f
+    if any(v <= 0 or a % v for a, v in zip(sp, f)):
+        raise ValueError(f"mask_maxpool: {tuple(mask.shape[2:])} is not a whole number of {tuple(factors)} blocks")
+    out = torch.empty((m.shape[0], 1, *(a // v for a, v in zip(m.shape[2:], factors))), dtype=torch.uint8, device=m.device)
+    L.check(L.load().mf_mask_maxpool_u8(m.data_ptr(), int(is_f), out.data_ptr(), m.shape[0], *sp, *f, stream()), "mf_mask_maxpool_u8")
+    return out
+
+
+def select_cells(mask: torch.Tensor, a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = where(mask, a, b): mask uint8 [N,1,...] one byte per cell, broadcast over the channels of a, b [N,C,...] fp32 (mf_select_cells_f32).
+    `out` may be a or b."""
+    _gpu(mask, a, b, out)
+    a, b = a.contiguous(), b.contiguous()
+    n, c = a.shape[0], a.shape[1]
+    cells = a.numel() // max(1, n * c)
+    if mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.numel() != n * cells or a.shape != b.shape or a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise ValueError(f"select_cells: mask uint8 [N,1,cells...] against fp32 [N,C,cells...], got {tuple(mask.shape)} {mask.dtype} and {tuple(a.shape)}")
+    if out is None:
+        out = torch.empty_like(a)
+    else:
+        drop_split(out)
+    L.check(L.load().mf_select_cells_f32(mask.data_ptr(), a.data_ptr(), b.data_ptr(), out.data_ptr(), n, c, cells, stream()), "mf_select_cells_f32")
+    return out
+
+
+def sched_step_blend(args: L.MfSchedArgs, blend: L.MfSchedBlend, outputs=()) -> None:
+    """sched_step with the kept cells of x_t_out replaced by the known latent at the next timestep (mf_sched_step_blend_f32)"""
+    for t in outputs:
+        drop_split(t)
+    L.check(L.load().mf_sched_step_blend_f32(C.byref(args), C.byref(blend), stream()), "mf_sched_step_blend_f32")
+
+
+def sched_step_philox_blend(args: L.MfSchedArgs, blend: L.MfSchedBlend, seed: int, draw_base: int, draw_stride: int, sample_offset: int, B: int,
+                            counter: torch.Tensor, outputs=()) -> None:
+    """sched_step_philox with the same select, still one launch (mf_sched_step_philox_blend_f32)"""
+    _gpu(counter)
+    for t in outputs:
+        drop_split(t)
+    L.check(L.load().mf_sched_step_philox_blend_f32(C.byref(args), seed & 0xFFFFFFFFFFFFFFFF, draw_base, draw_stride, sample_offset, B, counter.data_ptr(),
+                                                    counter.data_ptr() + 4, C.byref(blend), stream()), "mf_sched_step_philox_blend_f32")
+
+
 def gather_step_rows_multi(tables, step, cols: torch.Tensor):
     """gather_step_rows for up to three [S, NCOL, L_i] tables that share `cols` and the step, in ONE launch -> list of [B, L_i]"""
     _gpu(cols, *tables)

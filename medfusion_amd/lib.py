@@ -39,6 +39,10 @@ class MfSchedArgs(C.Structure):
                 ("guidance_scale", C.c_float), ("n", C.c_int64)]
 
 
+class MfSchedBlend(C.Structure):
+    _fields_ = [("z0", c_fp), ("eps0", c_fp), ("mask", c_fp), ("coef", c_fp), ("cells", C.c_int64), ("channels", C.c_int32), ("reserved", C.c_int32)]
+
+
 class MfGnFuse(C.Structure):
     _fields_ = [("gamma", c_fp), ("beta", c_fp), ("residual", c_fp), ("residual_pairs", c_fp), ("res_bound", c_fp), ("res_bound_slots", c_fp),
                 ("emb", c_fp), ("emb_bound", c_fp), ("out", c_fp), ("out_split", c_fp), ("out_bound", c_fp), ("rendezvous", c_fp), ("error_flag", c_fp),
@@ -130,6 +134,11 @@ _SIGS = {
     "mf_embedding_add_f32": (_I, [c_fp, c_fp, c_fp, _I, _I, _I, c_fp]),
     "mf_sched_step_f32": (_I, [C.POINTER(MfSchedArgs), c_fp]),
     "mf_sched_step_philox_f32": (_I, [C.POINTER(MfSchedArgs), _U64, C.c_int32, C.c_int32, _I64, _I, c_fp, c_fp, c_fp]),
+    "mf_sched_step_blend_f32": (_I, [C.POINTER(MfSchedArgs), C.POINTER(MfSchedBlend), c_fp]),
+    "mf_sched_step_philox_blend_f32": (_I, [C.POINTER(MfSchedArgs), _U64, C.c_int32, C.c_int32, _I64, _I, c_fp, c_fp, C.POINTER(MfSchedBlend), c_fp]),
+    "mf_select_cells_f32": (_I, [c_fp, c_fp, c_fp, c_fp, _I, _I, _I64, c_fp]),
+    "mf_mask_maxpool_u8": (_I, [c_fp, _I, c_fp, _I, _I, _I, _I, _I, _I, _I, c_fp]),
+    "mf_image_ingress_u8": (_I, [c_fp, c_fp, _I, _I, _I, _I, c_fp]),
     "mf_gather_step_rows3_f32": (_I, [C.POINTER(c_fp), C.POINTER(_I64), C.POINTER(c_fp), _I, c_fp, c_fp, C.c_int32, _I, _I, c_fp]),
     "mf_broadcast_from_table_f32": (_I, [c_fp, c_fp, C.c_int32, c_fp, _I, c_fp]),
     "mf_gather_step_rows_f32": (_I, [c_fp, c_fp, c_fp, C.c_int32, _I, _I64, c_fp, _I, c_fp]),

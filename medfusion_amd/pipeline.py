@@ -199,6 +199,11 @@ class DiffusionPipeline(nn.Module):
         first iteration, then every max(1, total // 20) iterations; the Python loop every iteration.  The counts a caller sees are STRICTLY
         INCREASING: when the loop has to be re-run (a fused rendezvous timed out, K.with_fused_fallback) the counts already reported are not
         reported again."""
+        return self._denoise_guarded(x_t, steps, condition, use_ddim, noise, trace, decode, use_graph, loop, progress_cb, 0, None, kwargs)
+
+    def _denoise_guarded(self, x_t, steps, condition, use_ddim, noise, trace, decode, use_graph, loop, progress_cb, start, blend, kwargs):
+        """denoise() proper: the loop under K.with_fused_fallback, whose re-run rewinds the noise source to the draw count at ENTRY (sample_from
+        enters after draw #0, so a re-run keeps eps0).  start / blend: see _denoise."""
         if not x_t.is_cuda:
             raise RuntimeError("medfusion_amd.DiffusionPipeline runs on a ROCm device only (no CPU fallback)")
         with torch.cuda.device(x_t.device):   # (see sample())
@@ -225,9 +230,12 @@ class DiffusionPipeline(nn.Module):
                         user_cb(done, total)
 
             return K.with_fused_fallback(x_t.device, lambda: self._denoise(x_t, steps, condition, use_ddim, noise, trace, decode, use_graph, loop, progress_cb,
-                                                                           **dict(kwargs)), rewind)
+                                                                           _start=start, _blend=blend, **dict(kwargs)), rewind)
 
-    def _denoise(self, x_t, steps, condition, use_ddim, noise, trace, decode, use_graph, loop, progress_cb=None, **kwargs):
+    def _denoise(self, x_t, steps, condition, use_ddim, noise, trace, decode, use_graph, loop, progress_cb=None, _start=0, _blend=None, **kwargs):
+        """_start: index of the first executed iteration of the full loop (sample_from: the loop runs on rev[_start:], recs[_start:] of the FULL
+        timestep list and the embeddings of those timesteps).  _blend = (z0, eps0, mask uint8 [B,1,...]) or None: inpainting, the kept cells of
+        every iteration's next latent replaced inside the scheduler step's launch."""
         K.SyncWords.reset(x_t.device)   # (the split-K counters of the convolutions: zero by invariant, re-zeroed once per loop for robustness)
         if "eta" in kwargs:
             raise TypeError("forward() got an unexpected keyword argument 'eta'")
@@ -251,7 +259,7 @@ class DiffusionPipeline(nn.Module):
         #             kernel node dispatches ~1 us later than a stream-ordered launch -- slower than the eager loop from B ~ 6 on;
         #   "eager":  the Python loop (needed for a trace, a host noise source, cold diffusion).
         from .noise import PhiloxDeviceNoise
-        replayable = (trace is None and not cold_diffusion and (noise is None or isinstance(noise, PhiloxDeviceNoise)) and (steps is None or steps >= 4))
+        replayable = (trace is None and not cold_diffusion and (noise is None or isinstance(noise, PhiloxDeviceNoise)) and (steps is None or steps - _start >= 4))
         if loop is not None and loop not in ("cmdlist", "graph", "eager"):
             raise ValueError(f"loop={loop!r}: 'cmdlist', 'graph' or 'eager'")
         # precedence: loop= argument, use_graph= (True: graph, False: eager), MEDFUSION_LOOP in the environment, then the default
@@ -276,6 +284,18 @@ class DiffusionPipeline(nn.Module):
             noise = default_noise()
             noise.begin(B, dev)
         rev = list(reversed(timesteps))
+        blend = None
+        if _start or _blend is not None:
+            if cold_diffusion:
+                raise ValueError("cold_diffusion is not built for sample_from")
+            if _blend is not None:   # (the coefficient rows are indexed like the sliced step table below)
+                z0, eps0, cmask = _blend
+                coef = sch.blend_records(timesteps, _start).to(dev)
+                cells = z0.numel() // (z0.shape[0] * z0.shape[1])
+                blend = L.MfSchedBlend(z0.data_ptr(), eps0.data_ptr(), cmask.data_ptr(), coef.data_ptr(), cells, z0.shape[1], 0)
+                blend._keep = (z0, eps0, cmask, coef)
+            rev, recs = rev[_start:], recs[_start:]
+            table = sch.upload_records(recs, dev)
         objective = 0 if self.estimator_objective == "x_T" else 1
         x_t = x_t.contiguous().clone()
         if cold_diffusion:
@@ -302,7 +322,7 @@ class DiffusionPipeline(nn.Module):
             return x_t
         if mode in ("graph", "cmdlist"):
             self._denoise_graph(x_t, rev, recs, table, condition, guidance_scale, un_cond, use_ddim, noise, objective, cmdlist=(mode == "cmdlist"),
-                                progress_cb=progress_cb)
+                                progress_cb=progress_cb, blend=blend)
         else:
             t_all = torch.tensor(rev, dtype=torch.float32, device=dev).reshape(-1, 1).expand(-1, B).contiguous()  # t.expand(B) per iteration (Q7)
             n_post = torch.empty_like(x_t)
@@ -322,7 +342,10 @@ class DiffusionPipeline(nn.Module):
                                   None if pred_var is None else pred_var.data_ptr(), n_post.data_ptr(), n_ddim.data_ptr() if ddim else None, 0,
                                   x_t.data_ptr(), x0.data_ptr(), None, table.data_ptr(), None, i, objective, int(bool(self.clip_x0)),
                                   float(guidance_scale), x_t.numel())
-                K.sched_step(a, outputs=(x_t, x0))
+                if blend is None:
+                    K.sched_step(a, outputs=(x_t, x0))
+                else:
+                    K.sched_step_blend(a, blend, outputs=(x_t, x0))
                 self_cond = x0 if self.use_self_conditioning else None  # only None-ness matters downstream (Q11)
                 if trace is not None:
                     trace.append((x0.clone(), x_t.clone()))
@@ -346,7 +369,8 @@ class DiffusionPipeline(nn.Module):
         cc, cu = est.embedding_columns(condition if has_c else None, B, dev, tab), est.embedding_columns(un_cond if has_c else None, B, dev, tab)
         return (tab, cc, cu, torch.cat([cu, cc]))   # (the last: columns of the 2B-row classifier-free-guidance pair, un-guided rows first)
 
-    def _denoise_graph(self, x_t, rev, recs, table, condition, guidance_scale, un_cond, use_ddim, noise, objective, cmdlist=False, progress_cb=None):
+    def _denoise_graph(self, x_t, rev, recs, table, condition, guidance_scale, un_cond, use_ddim, noise, objective, cmdlist=False, progress_cb=None,
+                       blend=None):
         """The loop body as ONE captured hipGraph replayed `steps` times (BASELINE.json configs[3]) -- or, cmdlist=True, recorded by the
         library while it runs once and re-issued from C (mf_cmdlist_*: the native command list of the loop body).  Everything the
         reference reads on the host each iteration (t, alphas_cumprod[t], the t==0 test, the RNG state) is indexed by a
@@ -373,7 +397,13 @@ class DiffusionPipeline(nn.Module):
         # the tail of an iteration -- posterior draw, DDIM draw, scheduler step, counter += 1 -- as ONE launch (mf_sched_step_philox_f32: the same
         # Philox quads and the same scheduler arithmetic, bit for bit), unless MEDFUSION_LOOP_TAIL=0 (A/B) or the latent is not a whole
         # number of quads per sample
-        fused_tail = os.environ.get("MEDFUSION_LOOP_TAIL", "1") != "0" and (x_t.numel() // B) % 4 == 0
+        fused_tail = os.environ.get("MEDFUSION_LOOP_TAIL", "1") != "0" and (x_t.numel() // B) % 4 == 0 and (blend is None or blend.cells % 4 == 0)
+
+        def step(a):   # (the un-fused scheduler step, with the inpainting select when there is one)
+            if blend is None:
+                K.sched_step(a, outputs=(x_t, x0))
+            else:
+                K.sched_step_blend(a, blend, outputs=(x_t, x0))
 
         def body():
             if emb is None:   # (with the embedding rows hoisted out of the loop the estimator never reads t)
@@ -383,7 +413,10 @@ class DiffusionPipeline(nn.Module):
                 a = L.MfSchedArgs(x_t.data_ptr(), pred.data_ptr(), None if pred_uncond is None else pred_uncond.data_ptr(),
                                   None if pred_var is None else pred_var.data_ptr(), None, None, 0, x_t.data_ptr(), x0.data_ptr(), None, table.data_ptr(),
                                   step_dev.data_ptr(), 0, objective, clip, g, x_t.numel())
-                K.sched_step_philox(a, noise._seed, base, stride, noise.sample_offset, B, counter, outputs=(x_t, x0))
+                if blend is None:
+                    K.sched_step_philox(a, noise._seed, base, stride, noise.sample_offset, B, counter, outputs=(x_t, x0))
+                else:
+                    K.sched_step_philox_blend(a, blend, noise._seed, base, stride, noise.sample_offset, B, counter, outputs=(x_t, x0))
                 return pred
             noise.draw_indexed(n_post, base, stride, step_dev)
             if use_ddim:
@@ -391,7 +424,7 @@ class DiffusionPipeline(nn.Module):
             a = L.MfSchedArgs(x_t.data_ptr(), pred.data_ptr(), None if pred_uncond is None else pred_uncond.data_ptr(),
                               None if pred_var is None else pred_var.data_ptr(), n_post.data_ptr(), n_ddim.data_ptr() if use_ddim else None, 0,
                               x_t.data_ptr(), x0.data_ptr(), None, table.data_ptr(), step_dev.data_ptr(), 0, objective, clip, g, x_t.numel())
-            K.sched_step(a, outputs=(x_t, x0))
+            step(a)
             K.counter_add(step_dev, 1)
             return pred  # keep alive until the end of capture
 
@@ -407,7 +440,7 @@ class DiffusionPipeline(nn.Module):
                 a = L.MfSchedArgs(x_t.data_ptr(), pred.data_ptr(), None if pu is None else pu.data_ptr(), None if pv is None else pv.data_ptr(),
                                   n_post.data_ptr(), n_ddim.data_ptr() if use_ddim else None, 0, x_t.data_ptr(), x0.data_ptr(), None, table.data_ptr(),
                                   step_dev.data_ptr(), 0, objective, clip, g, x_t.numel())
-                K.sched_step(a, outputs=(x_t, x0))
+                step(a)
                 K.counter_add(step_dev, 1)
             else:
                 body()  # eager warm-up iteration 0: sizes every workspace / packs weights on THIS stream
@@ -529,6 +562,119 @@ class DiffusionPipeline(nn.Module):
             noise.begin(hi - lo, dev, sample_offset=lo, global_batch=num_samples)
             x_T = noise.draw((hi - lo, *img_size))  # noise_scheduler.x_final(template): draw #0 (Q3)
             return self.denoise(x_T, condition=condition, noise=noise, **kwargs)
+
+    @staticmethod
+    def _strength_span(steps: int, strength: float):
+        """-> (s, k): iterations s .. steps-1 of the full loop run, k = steps - s = min(steps, int(strength * steps + 0.5)) of them"""
+        if not (isinstance(strength, (int, float)) and 0 < strength <= 1):
+            raise ValueError(f"strength={strength!r}: 0 < strength <= 1")
+        k = min(steps, int(strength * steps + 0.5))
+        if k < 1:
+            raise ValueError(f"strength={strength} of {steps} iterations rounds to none: at least one iteration must run")
+        return steps - k, k
+
+    def _cell_mask(self, mask, latent_shape, image_shape):
+        """-> (uint8 [B,1,cells...] on the device, True when `mask` came at image resolution).  1 / True = regenerate.  A mask at latent resolution is
+        used as is (> 0.5 if floating point); one at image resolution is reduced by max over each cell's pixels (K.mask_maxpool)."""
+        lat = (latent_shape[0], 1, *latent_shape[2:])
+        img = None if image_shape is None else (image_shape[0], 1, *image_shape[2:])
+        shape = tuple(mask.shape)
+        if shape == lat:
+            m = (mask > 0.5) if mask.is_floating_point() else (mask != 0)
+            return m.to(torch.uint8).contiguous(), False
+        if img is not None and shape == img:
+            factors = [a // b for a, b in zip(img[2:], lat[2:])]
+            if any(a != b * f for a, b, f in zip(img[2:], lat[2:], factors)):
+                raise ValueError(f"mask {shape}: the image is not a whole number of latent cells")
+            return K.mask_maxpool(mask, factors), True
+        raise ValueError(f"mask of shape {shape}: expected the latent's cells {lat}" + ("" if img is None else f" or the image's pixels {img}"))
+
+    @torch.no_grad()
+    def sample_from(self, x, strength, condition=None, *, mask=None, is_latent=False, steps=None, use_ddim=True, noise: Optional[NoiseSource] = None,
+                    encode_noise: Optional[NoiseSource] = None, composite=False, shard=None, decode=True, trace=None, loop=None, use_graph=None,
+                    progress_cb=None, guidance_scale=1.0, un_cond=None, **kwargs):
+        """Image-conditioned sampling: img2img (variations of `x` at a chosen `strength`) and, with `mask`, inpainting.  A composition of the
+        reference's own functions -- the training front end (diffusion_pipeline.py:84-90), GaussianNoiseScheduler.estimate_x_t
+        (gaussian_scheduler.py:61-77) and the LAST k iterations of denoise's loop (:278-310):
+          timesteps / rev / step records as denoise builds them on the FULL list; k = min(steps, int(strength * steps + 0.5)) iterations run,
+          i = s .. steps-1 with s = steps - k;
+          z0 = x (is_latent=True), else latent_embedder.encode(x) (its draw comes from `encode_noise`, a source of its own) and 2 z0 - 1 with
+          do_input_centering;
+          draw #0 = eps0 (where sample()'s x_T draw stands), then the loop's draws unchanged: 2k draws with DDIM, 1 + k without;
+          x = estimate_x_t(z0, rev[s], eps0), then iterations s .. steps-1;
+          mask (1 / True = regenerate, 0 / False = keep; one value per latent cell, broadcast over channels; at image resolution it is reduced
+          by max over each cell's pixels): after iteration i the kept cells take estimate_x_t(z0, rev[i+1], eps0) -- the SAME eps0, no extra
+          draw -- and z0 itself after the last iteration, inside the scheduler step's launch (all three loop forms).
+        Returns the decoded latent like sample() (or the latent with decode=False); composite=True (image input and image-resolution mask only)
+        returns where(mask, decoded, x).  shard=(rank, world) slices x, mask and the conditions (global batch in, this rank's rows out), the
+        Philox source keeps the global sample index.  NB: VAE.encode begins its own noise source at row 0, so with a stochastic embedder a
+        sharded caller encodes first and passes latents (the codebook embedders draw nothing and shard as they are).
+        cold_diffusion=True raises ValueError; `eta` raises TypeError like everywhere."""
+        if "eta" in kwargs:
+            raise TypeError("forward() got an unexpected keyword argument 'eta'")
+        if kwargs.pop("cold_diffusion", False):
+            raise ValueError("cold_diffusion is not built for sample_from")
+        if kwargs:
+            raise TypeError(f"forward() got an unexpected keyword argument '{next(iter(kwargs))}'")
+        sch = self.noise_scheduler
+        timesteps, _ = sch.loop_timesteps(steps, use_ddim)
+        steps = len(timesteps)
+        s, k = self._strength_span(steps, strength)
+        if composite and (is_latent or mask is None):
+            raise ValueError("composite=True needs an image input and an image-resolution mask")
+        if not x.is_cuda:
+            raise RuntimeError("medfusion_amd.DiffusionPipeline runs on a ROCm device only (no CPU fallback)")
+        dev = x.device
+        if shard is not None:
+            from .dist import shard_rows
+
+            lo, hi = shard_rows(x.shape[0], shard[0], shard[1])
+        else:
+            lo, hi = 0, x.shape[0]
+        n_global = x.shape[0]
+        x = x[lo:hi]
+        if mask is not None:
+            if mask.shape[0] != n_global:
+                raise ValueError(f"mask of shape {tuple(mask.shape)}: one mask per sample ({n_global})")
+            mask = mask[lo:hi].to(dev)
+        if condition is not None:
+            condition = condition[lo:hi]
+        if un_cond is not None:
+            un_cond = un_cond[lo:hi]
+        if hi == lo:   # more ranks than samples: this rank's shard is empty -- no launch, like sample()
+            empty, emb = x.to(torch.float32), self.latent_embedder
+            if is_latent:
+                return emb.decode(empty) if (decode and emb is not None) else empty
+            if decode or emb is None:
+                return empty
+            f = getattr(emb, "scale3", None) or (emb.scale,) * (x.dim() - 2)
+            return empty.new_empty((0, emb.emb_channels, *(a // b for a, b in zip(x.shape[2:], f))))
+        with torch.cuda.device(dev):
+            x = x.to(torch.float32).contiguous()
+            if is_latent:
+                z0 = x
+            else:
+                z0 = x if self.latent_embedder is None else self.latent_embedder.encode(x, noise=encode_noise)
+                if self.do_input_centering:   # 2 * x_0 - 1 (diffusion_pipeline.py:90), rounded like the reference's two operations
+                    two = torch.full((z0.shape[0],), 2.0, dtype=torch.float32, device=dev)
+                    z0 = K.rows_axpby(z0, two, torch.ones_like(z0), torch.full_like(two, -1.0))
+            z0 = z0.contiguous()
+            cmask, at_image = (None, False) if mask is None else self._cell_mask(mask, z0.shape, None if is_latent else x.shape)
+            if composite and not at_image:
+                raise ValueError("composite=True needs an image input and an image-resolution mask")
+            if noise is None:
+                noise = default_noise()
+            noise.begin(hi - lo, dev, sample_offset=lo, global_batch=n_global)
+            eps0 = noise.draw(tuple(z0.shape))                                   # draw #0
+            rev = list(reversed(timesteps))
+            x_t = sch.estimate_x_t(z0, torch.full((z0.shape[0],), int(rev[s]), dtype=torch.long), noise=eps0)
+            blend = None if cmask is None else (z0, eps0, cmask)
+            out = self._denoise_guarded(x_t, steps, condition, use_ddim, noise, trace, decode, use_graph, loop, progress_cb, s, blend,
+                                        dict(guidance_scale=guidance_scale, un_cond=un_cond))
+            if composite:
+                pix = (mask > 0.5) if mask.is_floating_point() else (mask != 0)
+                out = K.select_cells(pix.to(torch.uint8).contiguous(), out, x)
+            return out
 
     @torch.no_grad()
     def interpolate(self, img1, img2, i=None, condition=None, lam=0.5, noise: Optional[NoiseSource] = None, **kwargs):

@@ -127,6 +127,22 @@ class GaussianNoiseScheduler(BasicNoiseScheduler):
             recs.append(r)
         return recs
 
+    def blend_records(self, timesteps: List[int], start: int = 0) -> torch.Tensor:
+        """The known latent's coefficients for inpainting, one (a, c) row per EXECUTED iteration i = start .. steps-1 of the loop over
+        reversed(timesteps): after iteration i the kept cells are a * z0 + c * eps0 = estimate_x_t(z0, t_next, eps0) with t_next =
+        reversed(timesteps)[i + 1] (gaussian_scheduler.py:61-77: sqrt_alphas_cumprod / sqrt_one_minus_alphas_cumprod), and (1, 0) after the
+        last iteration (t_next = -1: z0 itself).  -> CPU fp32 [steps - start, 2]."""
+        tb = self.host_tables()
+        rev = list(reversed(timesteps))
+        rows = []
+        for i in range(start, len(rev)):
+            if i + 1 < len(rev):
+                t = rev[i + 1]
+                rows.append([float(tb["sqrt_alphas_cumprod"][t]), float(tb["sqrt_one_minus_alphas_cumprod"][t])])
+            else:
+                rows.append([1.0, 0.0])
+        return torch.tensor(rows, dtype=torch.float32).reshape(-1, 2)
+
     @staticmethod
     def upload_records(recs: List[L.MfSchedStep], device) -> torch.Tensor:
         arr = (L.MfSchedStep * len(recs))(*recs)
