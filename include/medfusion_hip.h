@@ -435,6 +435,48 @@ int mf_sched_step_blend_f32(const MfSchedArgs* a, const MfSchedBlend* blend, voi
 /* mf_sched_step_philox_f32 with the select above on its x_t_out, still ONE launch: cells % 4 == 0, z0 / eps0 16-byte and mask 4-byte aligned. */
 int mf_sched_step_philox_blend_f32(const MfSchedArgs* a, uint64_t seed, int32_t draw_base, int32_t draw_stride, int64_t sample_offset, int B,
                                    int32_t* step_counter, uint32_t* ticket, const MfSchedBlend* blend, void* stream);
+/* The deterministic solver step (few-step sampling; additive to ABI 250): DDIM with eta = 0 and DPM-Solver++(2M) in data-prediction form.
+ * Front half = mf_sched_step_f32's (CFG combine, x_0 / x_T estimates by objective, clip_x0: x0_out / xT_out are bit-equal to what that entry
+ * point writes for the same inputs); back half = one MfSolverStep row, every product rounded on its own, sums left to right:
+ *   MF_SOLVER_FINAL   x_t_out = x_0                               (the loop's last iteration)
+ *   MF_SOLVER_DDIM0   x_t_out = B * x_0 + A * x_T                 (diffusion_pipeline.py:297-304 at sigma = 0: B = sqrt(a_next), A = sqrt(1 - a_next))
+ *   MF_SOLVER_ORDER1  x_t_out = A * x_t + B * x_0                 (2M, first executed transition: no history yet)
+ *   MF_SOLVER_ORDER2  x_t_out = A * x_t + B * x_0 + C * x_0_prev  (2M; x_0_prev = the previous iteration's x_0)
+ * x0_hist: caller-owned [2][n]; every launch writes its x_0 to slot (step & 1), MF_SOLVER_ORDER2 reads slot ((step + 1) & 1); no other mode
+ * loads it (it may be uninitialised).  It may be NULL when no row is MF_SOLVER_ORDER2 (such a row then yields NaN).  The step comes from
+ * *step_counter when given -- then the workgroup that finishes last advances it, with `ticket` one zero-initialised word the launch leaves
+ * zero, as in mf_sched_step_philox_f32 -- else from *step_dev, else from `step`.  No noise is drawn.  16-byte vectors when every tensor
+ * is 16-byte aligned, element by element otherwise; any n. */
+enum { MF_SOLVER_FINAL = 0, MF_SOLVER_DDIM0 = 1, MF_SOLVER_ORDER1 = 2, MF_SOLVER_ORDER2 = 3 };
+typedef struct MfSolverStep {
+  float sqrt_recip_ac;    /* sqrt_recip_alphas_cumprod[t] */
+  float sqrt_recipm1_ac;  /* sqrt_recipm1_alphas_cumprod[t] */
+  float A, B, C;          /* see the modes above; unused ones 0 */
+  int32_t t;              /* timestep value */
+  int32_t mode;           /* MF_SOLVER_* */
+  int32_t reserved;       /* 0 */
+} MfSolverStep;
+typedef struct MfSolverArgs {
+  const float* x_t;          /* [n] current latent */
+  const float* pred;         /* [n] estimator output (conditional pass when CFG) */
+  const float* pred_uncond;  /* [n] or NULL: CFG pred = pu + g*(pred - pu) */
+  float* x_t_out;            /* [n] next latent (may alias x_t) */
+  float* x0_out;             /* [n] or NULL: x_0 estimate of this step */
+  float* xT_out;             /* [n] or NULL: x_T estimate of this step */
+  float* x0_hist;            /* [2][n] or NULL: the x_0 history */
+  const MfSolverStep* table; /* device table, one entry per executed iteration */
+  int32_t* step_counter;     /* device step counter the launch advances, or NULL */
+  uint32_t* ticket;          /* with step_counter: one zero-initialised word */
+  const int32_t* step_dev;   /* device step index (read only) or NULL (then `step` is used) */
+  int32_t step;
+  int32_t objective;         /* 0: 'x_T', 1: 'x_0' */
+  int32_t clip_x0;           /* clamp x_0 to [-1, 1] */
+  float guidance_scale;
+  int64_t n;                 /* elements */
+} MfSolverArgs;
+int mf_solver_step_f32(const MfSolverArgs* a, void* stream);
+/* the same with mf_sched_step_blend_f32's select on x_t_out (coef[step] of the executed grid); x0_out / xT_out / x0_hist stay the estimates */
+int mf_solver_step_blend_f32(const MfSolverArgs* a, const MfSchedBlend* blend, void* stream);
 /* out[n][c][cell] = mask[n][cell] ? a[n][c][cell] : b[n][c][cell] on NCHW / NCDHW fp32, the per-cell mask broadcast over the C channels: the
  * pixel-space composite of inpainting and the un-fused form of the select above. */
 int mf_select_cells_f32(const uint8_t* mask, const float* a, const float* b, float* out, int N, int C, int64_t cells, void* stream);

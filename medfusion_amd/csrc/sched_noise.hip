@@ -11,27 +11,38 @@ namespace {
 // intrinsics are plain operators and would otherwise be fused into FMAs); the pragma restates it locally.
 struct SchedOut { float xn, x0, xT; };
 
-// one element of the step: every product / sum rounded on its own (see above)
-__device__ __forceinline__ SchedOut sched_elem(const MfSchedArgs& a, const MfSchedStep& S, float xt, float pred, float pu, float pv, float npost, float nddim) {
+// the front half of a step, shared by the stochastic step (sched_elem) and the deterministic solver step (solver_elem): classifier-free
+// guidance combine, then the x_0 / x_T estimates by objective
+struct Estimate { float x0, xT; };
+__device__ __forceinline__ Estimate estimate_elem(bool cfg, float g, int objective, int clip_x0, float sqrt_recip_ac, float sqrt_recipm1_ac, float xt, float pred,
+                                                  float pu) {
 #pragma clang fp contract(off)
-  if (a.pred_uncond) {  // diffusion_pipeline.py:244  pred_uncond + g * (pred_cond - pred_uncond)
+  if (cfg) {  // diffusion_pipeline.py:244  pred_uncond + g * (pred_cond - pred_uncond)
     const float dlt = pred - pu;
-    const float sc = a.guidance_scale * dlt;
+    const float sc = g * dlt;
     pred = pu + sc;
   }
   float x0, xT;
-  if (a.objective == 0) {  // 'x_T': gaussian_scheduler.py:119-124
-    const float p1 = S.sqrt_recip_ac * xt;
-    const float p2 = S.sqrt_recipm1_ac * pred;
+  if (objective == 0) {  // 'x_T': gaussian_scheduler.py:119-124
+    const float p1 = sqrt_recip_ac * xt;
+    const float p2 = sqrt_recipm1_ac * pred;
     x0 = p1 - p2;
-    if (a.clip_x0) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    if (clip_x0) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
     xT = pred;
   } else {  // 'x_0': diffusion_pipeline.py:264-267, gaussian_scheduler.py:127-131
-    x0 = a.clip_x0 ? fminf(fmaxf(pred, -1.0f), 1.0f) : pred;
-    const float p1 = S.sqrt_recip_ac * xt;
+    x0 = clip_x0 ? fminf(fmaxf(pred, -1.0f), 1.0f) : pred;
+    const float p1 = sqrt_recip_ac * xt;
     const float df = p1 - x0;
-    xT = df / S.sqrt_recipm1_ac;
+    xT = df / sqrt_recipm1_ac;
   }
+  return Estimate{x0, xT};
+}
+
+// one element of the step: every product / sum rounded on its own (see above)
+__device__ __forceinline__ SchedOut sched_elem(const MfSchedArgs& a, const MfSchedStep& S, float xt, float pred, float pu, float pv, float npost, float nddim) {
+#pragma clang fp contract(off)
+  const Estimate e = estimate_elem(a.pred_uncond != nullptr, a.guidance_scale, a.objective, a.clip_x0, S.sqrt_recip_ac, S.sqrt_recipm1_ac, xt, pred, pu);
+  const float x0 = e.x0, xT = e.xT;
   // posterior mean / std: gaussian_scheduler.py:95-100
   const float m1 = S.coef1 * x0;
   const float m2 = S.coef2 * xt;
@@ -210,6 +221,90 @@ __global__ __launch_bounds__(256) void sched_step_philox_kernel(const MfSchedArg
   }
 }
 
+// The deterministic solver step (DDIM eta = 0, DPM-Solver++(2M)): estimate_elem's front half, then one row of MfSolverStep.  No noise, so no
+// Philox; the x_0 history of the second-order rows lives in a caller-owned [2][n] buffer whose slots alternate with the step's parity.  One
+// pass of 16-byte vectors over the first `nq` quads, the remaining n - 4 nq elements one by one (nq = 0: unaligned tensors, or a blend whose
+// cells are not a multiple of 4).  a.step_counter != NULL: the counter is the step and is advanced by the workgroup that finishes last
+// (sched_step_philox_kernel's ticket).
+__device__ __forceinline__ float solver_elem(const MfSolverStep& S, float xt, Estimate e, float x0_prev) {
+#pragma clang fp contract(off)
+  if (S.mode == MF_SOLVER_DDIM0) {  // diffusion_pipeline.py:304 with sigma = 0: x_0 * sqrt(a_next) + c * x_T
+    const float d1 = e.x0 * S.B;
+    const float d2 = S.A * e.xT;
+    return d1 + d2;
+  }
+  if (S.mode == MF_SOLVER_FINAL) return e.x0;
+  const float p1 = S.A * xt;
+  const float p2 = S.B * e.x0;
+  const float s12 = p1 + p2;
+  if (S.mode == MF_SOLVER_ORDER1) return s12;
+  const float p3 = S.C * x0_prev;
+  return s12 + p3;
+}
+
+template <bool BL>
+__global__ __launch_bounds__(256) void solver_step_kernel(const MfSolverArgs a, const MfSchedBlend bl, const long nq) {
+#pragma clang fp contract(off)
+  const int step = a.step_counter ? *a.step_counter : a.step_dev ? *a.step_dev : a.step;
+  const MfSolverStep S = a.table[step];
+  const BlendCoef k = BL ? blend_coef(bl, step) : BlendCoef{0.f, 0.f};
+  const bool cfg = a.pred_uncond != nullptr;
+  // a second-order row without a history buffer cannot be computed: the output says so (NaN) instead of reading through a null pointer
+  const bool hist = S.mode == MF_SOLVER_ORDER2 && a.x0_hist;
+  const float missing = (S.mode == MF_SOLVER_ORDER2 && !a.x0_hist) ? __builtin_nanf("") : 0.f;
+  const float* hprev = a.x0_hist ? a.x0_hist + (long)((step + 1) & 1) * a.n : nullptr;
+  float* hcur = a.x0_hist ? a.x0_hist + (long)(step & 1) * a.n : nullptr;
+  const long stride = (long)gridDim.x * blockDim.x;
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long per = BL ? bl.cells * bl.channels : 1;
+  for (long i = tid; i < nq; i += stride) {
+    const float4 xt = *reinterpret_cast<const float4*>(a.x_t + i * 4), pr = *reinterpret_cast<const float4*>(a.pred + i * 4);
+    const float4 pu = cfg ? *reinterpret_cast<const float4*>(a.pred_uncond + i * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 hp = hist ? *reinterpret_cast<const float4*>(hprev + i * 4) : make_float4(missing, missing, missing, missing);
+    const Estimate e0 = estimate_elem(cfg, a.guidance_scale, a.objective, a.clip_x0, S.sqrt_recip_ac, S.sqrt_recipm1_ac, xt.x, pr.x, pu.x);
+    const Estimate e1 = estimate_elem(cfg, a.guidance_scale, a.objective, a.clip_x0, S.sqrt_recip_ac, S.sqrt_recipm1_ac, xt.y, pr.y, pu.y);
+    const Estimate e2 = estimate_elem(cfg, a.guidance_scale, a.objective, a.clip_x0, S.sqrt_recip_ac, S.sqrt_recipm1_ac, xt.z, pr.z, pu.z);
+    const Estimate e3 = estimate_elem(cfg, a.guidance_scale, a.objective, a.clip_x0, S.sqrt_recip_ac, S.sqrt_recipm1_ac, xt.w, pr.w, pu.w);
+    float4 xn = make_float4(solver_elem(S, xt.x, e0, hp.x), solver_elem(S, xt.y, e1, hp.y), solver_elem(S, xt.z, e2, hp.z), solver_elem(S, xt.w, e3, hp.w));
+    if (BL) {   // (cells % 4 == 0 here: a quad lies inside one channel plane, its four cells are consecutive mask bytes)
+      const float4 z = *reinterpret_cast<const float4*>(bl.z0 + i * 4), e = *reinterpret_cast<const float4*>(bl.eps0 + i * 4);
+      const long b = (i * 4) / per;
+      const long cell = (i * 4 - b * per) % bl.cells;
+      const uchar4 m = *reinterpret_cast<const uchar4*>(bl.mask + b * bl.cells + cell);
+      xn = make_float4(blend_elem(xn.x, z.x, e.x, m.x != 0, k), blend_elem(xn.y, z.y, e.y, m.y != 0, k), blend_elem(xn.z, z.z, e.z, m.z != 0, k),
+                       blend_elem(xn.w, z.w, e.w, m.w != 0, k));
+    }
+    const float4 x0v = make_float4(e0.x0, e1.x0, e2.x0, e3.x0);
+    *reinterpret_cast<float4*>(a.x_t_out + i * 4) = xn;
+    if (hcur) *reinterpret_cast<float4*>(hcur + i * 4) = x0v;
+    if (a.x0_out) *reinterpret_cast<float4*>(a.x0_out + i * 4) = x0v;
+    if (a.xT_out) *reinterpret_cast<float4*>(a.xT_out + i * 4) = make_float4(e0.xT, e1.xT, e2.xT, e3.xT);
+  }
+  for (long i = nq * 4 + tid; i < a.n; i += stride) {
+    const Estimate e = estimate_elem(cfg, a.guidance_scale, a.objective, a.clip_x0, S.sqrt_recip_ac, S.sqrt_recipm1_ac, a.x_t[i], a.pred[i], cfg ? a.pred_uncond[i] : 0.f);
+    float xn = solver_elem(S, a.x_t[i], e, hist ? hprev[i] : missing);
+    if (BL) {
+      const long b = i / per;
+      const long cell = (i - b * per) % bl.cells;
+      xn = blend_elem(xn, bl.z0[i], bl.eps0[i], bl.mask[b * bl.cells + cell] != 0, k);
+    }
+    a.x_t_out[i] = xn;
+    if (hcur) hcur[i] = e.x0;
+    if (a.x0_out) a.x0_out[i] = e.x0;
+    if (a.xT_out) a.xT_out[i] = e.xT;
+  }
+  if (a.step_counter) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const unsigned old = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (old + 1u == gridDim.x) {   // the last workgroup: every other one has read *step_counter (before its own ticket)
+        __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(a.step_counter, step + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+}
+
 // up to three gathers of the rows of loop iteration `step` in one launch (blockIdx.y = which): gather_step_rows_kernel's work for the
 // embedding rows, the local-embedder rows and their bounds, which share `cols` and the step
 struct GatherSeg { const float* table; float* out; long row_len; };
@@ -276,6 +371,33 @@ int sched_step_philox_launch(const MfSchedArgs* a, uint64_t seed, int32_t draw_b
   return check_launch("sched_step_philox");
 }
 
+int solver_step_launch(const MfSolverArgs* a, const MfSchedBlend* bl, void* stream) {
+  MF_REQUIRE(a && a->x_t && a->pred && a->x_t_out && a->table && a->n > 0, MF_EINVAL, "solver_step: bad args");
+  MF_REQUIRE(a->objective == 0 || a->objective == 1, MF_EINVAL, "solver_step: objective");
+  MF_REQUIRE(!a->step_counter == !a->ticket, MF_EINVAL, "solver_step: step_counter and ticket come together");
+  MF_REQUIRE(a->step_counter || a->step_dev || a->step >= 0, MF_EINVAL, "solver_step: step");
+  // the history slots must not overlap what the same launch reads or writes elsewhere
+  const float* const h0 = a->x0_hist;
+  const float* const h1 = h0 ? h0 + 2 * a->n : nullptr;
+  const float* const others[] = {a->x_t, a->pred, a->pred_uncond, a->x_t_out, a->x0_out, a->xT_out};
+  for (const float* p : others) MF_REQUIRE(!h0 || !p || p + a->n <= h0 || p >= h1, MF_EINVAL, "solver_step: x0_hist overlaps another tensor");
+  uintptr_t al = (uintptr_t)a->x_t | (uintptr_t)a->pred | (uintptr_t)a->x_t_out | (uintptr_t)a->pred_uncond | (uintptr_t)a->x0_out | (uintptr_t)a->xT_out |
+                 (uintptr_t)a->x0_hist;
+  if (a->x0_hist && (a->n & 3)) al |= 4;   // (the second history slot starts n floats in)
+  if (bl) al |= (uintptr_t)bl->z0 | (uintptr_t)bl->eps0 | ((uintptr_t)bl->mask & 3 ? 4 : 0) | (bl->cells & 3 ? 4 : 0);
+  const long nq = (al & 15) ? 0 : a->n / 4;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(MF_FAM_SCHED, s, (bl ? 12.0 : 9.0) * a->n, 4.0 * a->n * (bl ? 8 : 6));
+  long blocks = ((nq ? nq : a->n) + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  if (bl) {
+    MF_LAUNCH(solver_step_kernel<true>, dim3((int)blocks), dim3(256), 0, s, *a, *bl, nq);
+  } else {
+    MF_LAUNCH(solver_step_kernel<false>, dim3((int)blocks), dim3(256), 0, s, *a, kNoBlend, nq);
+  }
+  return check_launch("solver_step");
+}
+
 }  // namespace
 
 extern "C" {
@@ -303,6 +425,15 @@ int mf_sched_step_philox_blend_f32(const MfSchedArgs* a, uint64_t seed, int32_t 
   MF_REQUIRE((((uintptr_t)bl->z0 | (uintptr_t)bl->eps0) & 15) == 0 && ((uintptr_t)bl->mask & 3) == 0, MF_EINVAL,
              "sched_step_philox_blend: z0 / eps0 must be 16-byte aligned, mask 4-byte aligned");
   return sched_step_philox_launch(a, seed, draw_base, draw_stride, sample_offset, B, step_counter, ticket, bl, stream);
+}
+
+int mf_solver_step_f32(const MfSolverArgs* a, void* stream) { return solver_step_launch(a, nullptr, stream); }
+
+int mf_solver_step_blend_f32(const MfSolverArgs* a, const MfSchedBlend* bl, void* stream) {
+  MF_REQUIRE(a, MF_EINVAL, "solver_step_blend: bad args");
+  MF_REQUIRE(bl && bl->z0 && bl->eps0 && bl->mask && bl->coef && bl->cells > 0 && bl->channels > 0, MF_EINVAL, "solver_step_blend: bad blend state");
+  MF_REQUIRE(a->n % (bl->cells * (int64_t)bl->channels) == 0, MF_EINVAL, "solver_step_blend: n is not a whole number of samples of channels x cells");
+  return solver_step_launch(a, bl, stream);
 }
 
 int mf_gather_step_rows3_f32(const float* const* tables, const int64_t* row_lens, float* const* outs, int n_tables, const int64_t* cols, const int32_t* step_dev,

@@ -1192,6 +1192,17 @@ def sched_step_philox_blend(args: L.MfSchedArgs, blend: L.MfSchedBlend, seed: in
                                                     counter.data_ptr() + 4, C.byref(blend), stream()), "mf_sched_step_philox_blend_f32")
 
 
+def solver_step(args: L.MfSolverArgs, blend: Optional[L.MfSchedBlend] = None, outputs=()) -> None:
+    """the deterministic solver step in one launch (mf_solver_step_f32; with `blend` mf_solver_step_blend_f32: the inpainting select on x_t_out).
+    `outputs` as in sched_step."""
+    for t in outputs:
+        drop_split(t)
+    if blend is None:
+        L.check(L.load().mf_solver_step_f32(C.byref(args), stream()), "mf_solver_step_f32")
+    else:
+        L.check(L.load().mf_solver_step_blend_f32(C.byref(args), C.byref(blend), stream()), "mf_solver_step_blend_f32")
+
+
 def gather_step_rows_multi(tables, step, cols: torch.Tensor):
     """gather_step_rows for up to three [S, NCOL, L_i] tables that share `cols` and the step, in ONE launch -> list of [B, L_i]"""
     _gpu(cols, *tables)

@@ -43,6 +43,20 @@ class MfSchedBlend(C.Structure):
     _fields_ = [("z0", c_fp), ("eps0", c_fp), ("mask", c_fp), ("coef", c_fp), ("cells", C.c_int64), ("channels", C.c_int32), ("reserved", C.c_int32)]
 
 
+SOLVER_FINAL, SOLVER_DDIM0, SOLVER_ORDER1, SOLVER_ORDER2 = 0, 1, 2, 3
+
+
+class MfSolverStep(C.Structure):
+    _fields_ = [("sqrt_recip_ac", C.c_float), ("sqrt_recipm1_ac", C.c_float), ("A", C.c_float), ("B", C.c_float), ("C", C.c_float), ("t", C.c_int32),
+                ("mode", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MfSolverArgs(C.Structure):
+    _fields_ = [("x_t", c_fp), ("pred", c_fp), ("pred_uncond", c_fp), ("x_t_out", c_fp), ("x0_out", c_fp), ("xT_out", c_fp), ("x0_hist", c_fp),
+                ("table", c_fp), ("step_counter", c_fp), ("ticket", c_fp), ("step_dev", c_fp), ("step", C.c_int32), ("objective", C.c_int32),
+                ("clip_x0", C.c_int32), ("guidance_scale", C.c_float), ("n", C.c_int64)]
+
+
 class MfGnFuse(C.Structure):
     _fields_ = [("gamma", c_fp), ("beta", c_fp), ("residual", c_fp), ("residual_pairs", c_fp), ("res_bound", c_fp), ("res_bound_slots", c_fp),
                 ("emb", c_fp), ("emb_bound", c_fp), ("out", c_fp), ("out_split", c_fp), ("out_bound", c_fp), ("rendezvous", c_fp), ("error_flag", c_fp),
@@ -136,6 +150,8 @@ _SIGS = {
     "mf_sched_step_philox_f32": (_I, [C.POINTER(MfSchedArgs), _U64, C.c_int32, C.c_int32, _I64, _I, c_fp, c_fp, c_fp]),
     "mf_sched_step_blend_f32": (_I, [C.POINTER(MfSchedArgs), C.POINTER(MfSchedBlend), c_fp]),
     "mf_sched_step_philox_blend_f32": (_I, [C.POINTER(MfSchedArgs), _U64, C.c_int32, C.c_int32, _I64, _I, c_fp, c_fp, C.POINTER(MfSchedBlend), c_fp]),
+    "mf_solver_step_f32": (_I, [C.POINTER(MfSolverArgs), c_fp]),
+    "mf_solver_step_blend_f32": (_I, [C.POINTER(MfSolverArgs), C.POINTER(MfSchedBlend), c_fp]),
     "mf_select_cells_f32": (_I, [c_fp, c_fp, c_fp, c_fp, _I, _I, _I64, c_fp]),
     "mf_mask_maxpool_u8": (_I, [c_fp, _I, c_fp, _I, _I, _I, _I, _I, _I, _I, c_fp]),
     "mf_image_ingress_u8": (_I, [c_fp, c_fp, _I, _I, _I, _I, c_fp]),

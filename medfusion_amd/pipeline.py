@@ -187,18 +187,48 @@ class DiffusionPipeline(nn.Module):
         self_cond = x0 if self.estimator_objective == "x_T" else xT
         return prior, x0, xT, self_cond
 
+    # ------------------------------------------------------------------ deterministic few-step samplers
+    @staticmethod
+    def _check_sampler(sampler, spacing, use_ddim, cold_diffusion):
+        """the rules of `sampler=` / `spacing=` (denoise, sample, sample_from), checked before anything touches the device"""
+        if sampler is not None and sampler not in GaussianNoiseScheduler.SAMPLERS:
+            raise ValueError(f"sampler={sampler!r}: None or one of {GaussianNoiseScheduler.SAMPLERS}")
+        if spacing not in GaussianNoiseScheduler.SPACINGS:
+            raise ValueError(f"spacing={spacing!r}: None, 'uniform' or 'logsnr'")
+        if sampler is None:
+            if spacing not in (None, "uniform"):
+                raise ValueError(f"spacing={spacing!r} needs a sampler ('ddim0' or 'dpmpp2m'): the default loop runs on the reference's grid")
+            return
+        if not use_ddim:
+            raise ValueError(f"sampler={sampler!r} needs use_ddim=True (it replaces the DDIM update; the DDPM loop has no deterministic form)")
+        if cold_diffusion:
+            raise ValueError(f"sampler={sampler!r} with cold_diffusion=True: cold diffusion runs through the single-step API")
+
+    def _solver_args(self, x_t, pred, pred_uncond, x0, hist, table, objective, guidance_scale, step=0, counter=None):
+        """the arguments of one mf_solver_step_f32 launch, in place on x_t.  counter: int32 [2] on the device = (step, ticket word), or None
+        (then `step`, a host int)."""
+        return L.MfSolverArgs(x_t.data_ptr(), pred.data_ptr(), None if pred_uncond is None else pred_uncond.data_ptr(), x_t.data_ptr(),
+                              None if x0 is None else x0.data_ptr(), None, None if hist is None else hist.data_ptr(), table.data_ptr(),
+                              None if counter is None else counter.data_ptr(), None if counter is None else counter.data_ptr() + 4, None, int(step),
+                              objective, int(bool(self.clip_x0)), float(guidance_scale), x_t.numel())
+
     # ------------------------------------------------------------------ the loop
     @torch.no_grad()
     def denoise(self, x_t, steps=None, condition=None, use_ddim=True, noise: Optional[NoiseSource] = None, trace=None, decode=True, use_graph=None,
                 loop: Optional[str] = None, progress_cb=None, **kwargs):
         """diffusion_pipeline.py:278-310.  kwargs: guidance_scale, un_cond, cold_diffusion (forwarded to forward()
         by the reference); `eta` raises like the reference's forward() would (Q2).
+        sampler="ddim0" | "dpmpp2m": a deterministic few-step sampler in place of the stochastic update -- the reference's DDIM update at
+        sigma = 0, or DPM-Solver++(2M) in data-prediction form (GaussianNoiseScheduler.solver_records); needs use_ddim=True, draws no noise,
+        drops a learned variance head's output.  spacing="logsnr" (with a sampler): the grid uniform in log-SNR
+        (GaussianNoiseScheduler.loop_timesteps), which may run fewer than `steps` iterations.  sampler=None: the loop below, unchanged.
         progress_cb(done, total): the hook that stands where the reference drives `st.progress` and `tqdm` (diffusion_pipeline.py:289-291; SURVEY Q16:
         no streamlit import here).  Called on the host after the iterations up to `done` have been ENQUEUED -- the loop never waits for the device;
         a callback that wants finished iterations synchronises the stream itself.  The replayed loops (command list, graph) call it after the eager
         first iteration, then every max(1, total // 20) iterations; the Python loop every iteration.  The counts a caller sees are STRICTLY
         INCREASING: when the loop has to be re-run (a fused rendezvous timed out, K.with_fused_fallback) the counts already reported are not
         reported again."""
+        self._check_sampler(kwargs.get("sampler"), kwargs.get("spacing"), use_ddim, kwargs.get("cold_diffusion", False))
         return self._denoise_guarded(x_t, steps, condition, use_ddim, noise, trace, decode, use_graph, loop, progress_cb, 0, None, kwargs)
 
     def _denoise_guarded(self, x_t, steps, condition, use_ddim, noise, trace, decode, use_graph, loop, progress_cb, start, blend, kwargs):
@@ -242,8 +272,10 @@ class DiffusionPipeline(nn.Module):
         guidance_scale = kwargs.pop("guidance_scale", 1.0)
         un_cond = kwargs.pop("un_cond", None)
         cold_diffusion = bool(kwargs.pop("cold_diffusion", False))
+        sampler, spacing = kwargs.pop("sampler", None), kwargs.pop("spacing", None)
         if kwargs:
             raise TypeError(f"forward() got an unexpected keyword argument '{next(iter(kwargs))}'")
+        self._check_sampler(sampler, spacing, use_ddim, cold_diffusion)
         if self.estimator_objective not in ("x_T", "x_0"):
             raise ValueError("Unknown Objective")
         if not x_t.is_cuda:
@@ -259,7 +291,12 @@ class DiffusionPipeline(nn.Module):
         #             kernel node dispatches ~1 us later than a stream-ordered launch -- slower than the eager loop from B ~ 6 on;
         #   "eager":  the Python loop (needed for a trace, a host noise source, cold diffusion).
         from .noise import PhiloxDeviceNoise
-        replayable = (trace is None and not cold_diffusion and (noise is None or isinstance(noise, PhiloxDeviceNoise)) and (steps is None or steps - _start >= 4))
+        sch = self.noise_scheduler
+        if sampler is not None:   # (the executed count decides whether the loop is long enough to replay: the log-SNR grid may drop iterations)
+            timesteps, steps = sch.loop_timesteps(steps, use_ddim, spacing)
+        # (a deterministic sampler draws nothing inside the loop: any noise source replays)
+        replayable = (trace is None and not cold_diffusion and (sampler is not None or noise is None or isinstance(noise, PhiloxDeviceNoise))
+                      and (steps is None or steps - _start >= 4))
         if loop is not None and loop not in ("cmdlist", "graph", "eager"):
             raise ValueError(f"loop={loop!r}: 'cmdlist', 'graph' or 'eager'")
         # precedence: loop= argument, use_graph= (True: graph, False: eager), MEDFUSION_LOOP in the environment, then the default
@@ -274,12 +311,15 @@ class DiffusionPipeline(nn.Module):
         if mode == "graph" and not replayable and not explicit:
             mode = "eager"
         use_graph = mode == "graph"
-        sch = self.noise_scheduler
         dev = x_t.device
         B = x_t.shape[0]
-        timesteps, steps = sch.loop_timesteps(steps, use_ddim)
-        recs = sch.step_records(timesteps, use_ddim)
-        table = sch.upload_records(recs, dev)
+        if sampler is None:
+            timesteps, steps = sch.loop_timesteps(steps, use_ddim)
+            recs = sch.step_records(timesteps, use_ddim)
+            table = sch.upload_records(recs, dev)
+        else:   # one MfSolverStep row per EXECUTED iteration: the first one is first-order wherever it sits in the grid
+            recs = sch.solver_records(timesteps, sampler, start=_start)
+            table = sch.upload_solver_records(recs, dev)
         if noise is None:  # x_t supplied by the caller (interpolate): fresh source, draws start at 0
             noise = default_noise()
             noise.begin(B, dev)
@@ -294,8 +334,10 @@ class DiffusionPipeline(nn.Module):
                 cells = z0.numel() // (z0.shape[0] * z0.shape[1])
                 blend = L.MfSchedBlend(z0.data_ptr(), eps0.data_ptr(), cmask.data_ptr(), coef.data_ptr(), cells, z0.shape[1], 0)
                 blend._keep = (z0, eps0, cmask, coef)
-            rev, recs = rev[_start:], recs[_start:]
-            table = sch.upload_records(recs, dev)
+            rev = rev[_start:]
+            if sampler is None:
+                recs = recs[_start:]
+                table = sch.upload_records(recs, dev)
         objective = 0 if self.estimator_objective == "x_T" else 1
         x_t = x_t.contiguous().clone()
         if cold_diffusion:
@@ -320,9 +362,26 @@ class DiffusionPipeline(nn.Module):
             if decode and self.latent_embedder is not None:
                 x_t = self.latent_embedder.decode(x_t)
             return x_t
+        # the deterministic samplers: the x_0 history of the second-order rows ([2][n], slots alternate with the step), and the x_0 estimate
+        # as a tensor of its own only where something reads it (self-conditioning, a trace)
+        hist = torch.empty((2, *x_t.shape), dtype=torch.float32, device=dev) if sampler == "dpmpp2m" else None
         if mode in ("graph", "cmdlist"):
             self._denoise_graph(x_t, rev, recs, table, condition, guidance_scale, un_cond, use_ddim, noise, objective, cmdlist=(mode == "cmdlist"),
-                                progress_cb=progress_cb, blend=blend)
+                                progress_cb=progress_cb, blend=blend, solver=None if sampler is None else (hist,))
+        elif sampler is not None:
+            t_all = torch.tensor(rev, dtype=torch.float32, device=dev).reshape(-1, 1).expand(-1, B).contiguous()
+            x0 = torch.empty_like(x_t) if (self.use_self_conditioning or trace is not None) else None
+            self_cond = None
+            emb_tab = self._hoisted_embeddings(self._estimator(), t_all[:, 0].contiguous(), condition, un_cond, B, dev)
+            for i in range(len(rev)):
+                pred, pred_uncond, _ = self._predict(x_t, t_all[i], condition, self_cond, guidance_scale, un_cond,
+                                                     emb=None if emb_tab is None else (emb_tab[0], i, emb_tab[1], emb_tab[2], emb_tab[3]))
+                K.solver_step(self._solver_args(x_t, pred, pred_uncond, x0, hist, table, objective, guidance_scale, step=i), blend, outputs=(x_t, x0))
+                self_cond = x0 if self.use_self_conditioning else None
+                if trace is not None:
+                    trace.append((x0.clone(), x_t.clone()))
+                if progress_cb is not None:
+                    progress_cb(i + 1, len(rev))
         else:
             t_all = torch.tensor(rev, dtype=torch.float32, device=dev).reshape(-1, 1).expand(-1, B).contiguous()  # t.expand(B) per iteration (Q7)
             n_post = torch.empty_like(x_t)
@@ -370,24 +429,28 @@ class DiffusionPipeline(nn.Module):
         return (tab, cc, cu, torch.cat([cu, cc]))   # (the last: columns of the 2B-row classifier-free-guidance pair, un-guided rows first)
 
     def _denoise_graph(self, x_t, rev, recs, table, condition, guidance_scale, un_cond, use_ddim, noise, objective, cmdlist=False, progress_cb=None,
-                       blend=None):
+                       blend=None, solver=None):
         """The loop body as ONE captured hipGraph replayed `steps` times (BASELINE.json configs[3]) -- or, cmdlist=True, recorded by the
         library while it runs once and re-issued from C (mf_cmdlist_*: the native command list of the loop body).  Everything the
         reference reads on the host each iteration (t, alphas_cumprod[t], the t==0 test, the RNG state) is indexed by a
         DEVICE step counter: `t` is broadcast from a device table, the scheduler scalars come from the MfSchedStep table,
         the Philox draw index is draw_base + stride*step, and the graph advances the counter itself.  The last DDIM
-        iteration still fills the (unused) DDIM noise buffer: counter-based draws do not shift any other draw."""
+        iteration still fills the (unused) DDIM noise buffer: counter-based draws do not shift any other draw.
+        solver = (x_0 history or None,): `table` holds MfSolverStep rows and the tail of an iteration is mf_solver_step_f32, which reads the
+        counter, advances it and draws nothing."""
         from .noise import PhiloxDeviceNoise
 
-        if not isinstance(noise, PhiloxDeviceNoise):
+        if solver is None and not isinstance(noise, PhiloxDeviceNoise):
             raise RuntimeError("use_graph=True needs the device Philox noise source (a host generator cannot be captured)")
         dev, B = x_t.device, x_t.shape[0]
         t_table = torch.tensor(rev, dtype=torch.float32, device=dev)
         counter = torch.zeros(2, dtype=torch.int32, device=dev)    # (step, ticket word of the fused tail launch)
         step_dev = counter[:1]
         t_cur = torch.zeros(B, dtype=torch.float32, device=dev)   # (filled per iteration only when the estimator reads t: not with hoisted embeddings)
-        n_post, n_ddim, x0 = torch.empty_like(x_t), torch.empty_like(x_t), torch.empty_like(x_t)
-        stride = 2 if use_ddim else 1
+        n_post, n_ddim, x0 = (None, None, None) if solver is not None else (torch.empty_like(x_t), torch.empty_like(x_t), torch.empty_like(x_t))
+        if solver is not None and self.use_self_conditioning:
+            x0 = torch.empty_like(x_t)
+        stride = 0 if solver is not None else 2 if use_ddim else 1
         base = noise.draw_index  # draws consumed so far (x_T)
         clip, g = int(bool(self.clip_x0)), float(guidance_scale)
 
@@ -409,6 +472,9 @@ class DiffusionPipeline(nn.Module):
             if emb is None:   # (with the embedding rows hoisted out of the loop the estimator never reads t)
                 K.broadcast_from_table(t_table, step_dev, t_cur)
             pred, pred_uncond, pred_var = self._predict(x_t, t_cur, condition, None if not self.use_self_conditioning else x0, g, un_cond, emb=emb)
+            if solver is not None:
+                K.solver_step(self._solver_args(x_t, pred, pred_uncond, x0, solver[0], table, objective, g, counter=counter), blend, outputs=(x_t, x0))
+                return pred
             if fused_tail:
                 a = L.MfSchedArgs(x_t.data_ptr(), pred.data_ptr(), None if pred_uncond is None else pred_uncond.data_ptr(),
                                   None if pred_var is None else pred_var.data_ptr(), None, None, 0, x_t.data_ptr(), x0.data_ptr(), None, table.data_ptr(),
@@ -434,6 +500,9 @@ class DiffusionPipeline(nn.Module):
                 if emb is None:
                     K.broadcast_from_table(t_table, step_dev, t_cur)
                 pred, pu, pv = self._predict(x_t, t_cur, condition, None, g, un_cond, emb=emb)
+                if solver is not None:
+                    K.solver_step(self._solver_args(x_t, pred, pu, x0, solver[0], table, objective, g, counter=counter), blend, outputs=(x_t, x0))
+                    return
                 noise.draw_indexed(n_post, base, stride, step_dev)
                 if use_ddim:
                     noise.draw_indexed(n_ddim, base + 1, stride, step_dev)
@@ -539,6 +608,7 @@ class DiffusionPipeline(nn.Module):
     def sample(self, num_samples, img_size, condition=None, noise: Optional[NoiseSource] = None, shard=None, **kwargs):
         """diffusion_pipeline.py:312-317.  `shard=(rank, world)`: this process generates rows
         [rank*num_samples/world, (rank+1)*num_samples/world) of the global batch (condition/un_cond are global)."""
+        self._check_sampler(kwargs.get("sampler"), kwargs.get("spacing"), kwargs.get("use_ddim", True), kwargs.get("cold_diffusion", False))
         dev = self.device
         if dev.type != "cuda":
             raise RuntimeError("medfusion_amd.DiffusionPipeline.sample: move the pipeline to a ROCm device first (no CPU fallback)")
@@ -592,7 +662,7 @@ class DiffusionPipeline(nn.Module):
     @torch.no_grad()
     def sample_from(self, x, strength, condition=None, *, mask=None, is_latent=False, steps=None, use_ddim=True, noise: Optional[NoiseSource] = None,
                     encode_noise: Optional[NoiseSource] = None, composite=False, shard=None, decode=True, trace=None, loop=None, use_graph=None,
-                    progress_cb=None, guidance_scale=1.0, un_cond=None, **kwargs):
+                    progress_cb=None, guidance_scale=1.0, un_cond=None, sampler=None, spacing=None, **kwargs):
         """Image-conditioned sampling: img2img (variations of `x` at a chosen `strength`) and, with `mask`, inpainting.  A composition of the
         reference's own functions -- the training front end (diffusion_pipeline.py:84-90), GaussianNoiseScheduler.estimate_x_t
         (gaussian_scheduler.py:61-77) and the LAST k iterations of denoise's loop (:278-310):
@@ -609,16 +679,20 @@ class DiffusionPipeline(nn.Module):
         returns where(mask, decoded, x).  shard=(rank, world) slices x, mask and the conditions (global batch in, this rank's rows out), the
         Philox source keeps the global sample index.  NB: VAE.encode begins its own noise source at row 0, so with a stochastic embedder a
         sharded caller encodes first and passes latents (the codebook embedders draw nothing and shard as they are).
-        cold_diffusion=True raises ValueError; `eta` raises TypeError like everywhere."""
+        cold_diffusion=True raises ValueError; `eta` raises TypeError like everywhere.
+        sampler= / spacing= as in denoise(): the deterministic samplers on the EXECUTED grid -- the same strength rule picks the last k of its
+        iterations, the first of them is first-order, the kept cells take the known latent at the next timestep of that grid; eps0 is the only
+        draw."""
         if "eta" in kwargs:
             raise TypeError("forward() got an unexpected keyword argument 'eta'")
         if kwargs.pop("cold_diffusion", False):
             raise ValueError("cold_diffusion is not built for sample_from")
         if kwargs:
             raise TypeError(f"forward() got an unexpected keyword argument '{next(iter(kwargs))}'")
+        self._check_sampler(sampler, spacing, use_ddim, False)
         sch = self.noise_scheduler
-        timesteps, _ = sch.loop_timesteps(steps, use_ddim)
-        steps = len(timesteps)
+        timesteps, _ = sch.loop_timesteps(steps, use_ddim, spacing)
+        asked, steps = steps, len(timesteps)
         s, k = self._strength_span(steps, strength)
         if composite and (is_latent or mask is None):
             raise ValueError("composite=True needs an image input and an image-resolution mask")
@@ -669,8 +743,9 @@ class DiffusionPipeline(nn.Module):
             rev = list(reversed(timesteps))
             x_t = sch.estimate_x_t(z0, torch.full((z0.shape[0],), int(rev[s]), dtype=torch.long), noise=eps0)
             blend = None if cmask is None else (z0, eps0, cmask)
-            out = self._denoise_guarded(x_t, steps, condition, use_ddim, noise, trace, decode, use_graph, loop, progress_cb, s, blend,
-                                        dict(guidance_scale=guidance_scale, un_cond=un_cond))
+            # (the loop rebuilds the grid from the step count: the log-SNR grid of `asked` steps is not the one of len(timesteps) steps)
+            out = self._denoise_guarded(x_t, asked if sampler is not None else steps, condition, use_ddim, noise, trace, decode, use_graph, loop, progress_cb,
+                                        s, blend, dict(guidance_scale=guidance_scale, un_cond=un_cond, sampler=sampler, spacing=spacing))
             if composite:
                 pix = (mask > 0.5) if mask.is_floating_point() else (mask != 0)
                 out = K.select_cells(pix.to(torch.uint8).contiguous(), out, x)

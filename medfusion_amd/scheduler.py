@@ -10,6 +10,7 @@ Tensor-level methods (estimate_x_0, ...) run on the GPU through the same fused k
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import List, Optional, Tuple
 
 import torch
@@ -83,14 +84,88 @@ class GaussianNoiseScheduler(BasicNoiseScheduler):
             self._host = (key, {n: getattr(self, n).detach().to("cpu", torch.float32).clone() for n in self.TABLES})
         return self._host[1]
 
-    def loop_timesteps(self, steps: Optional[int], use_ddim: bool) -> Tuple[List[int], int]:
-        """diffusion_pipeline.py:283-287: DDIM -> truncated linspace (Q4); else the FIRST `steps` entries (Q5)."""
+    SAMPLERS = ("ddim0", "dpmpp2m")
+    SPACINGS = (None, "uniform", "logsnr")
+
+    def loop_timesteps(self, steps: Optional[int], use_ddim: bool, spacing: Optional[str] = None) -> Tuple[List[int], int]:
+        """diffusion_pipeline.py:283-287: DDIM -> truncated linspace (Q4); else the FIRST `steps` entries (Q5).
+        spacing="logsnr" (deterministic samplers only): `steps` targets uniform in lambda = 1/2 log(ac / (1 - ac)) between timestep 0 and T - 1, each
+        mapped to the nearest integer timestep, the endpoints forced to 0 and T - 1, duplicates dropped; the second value is then the EXECUTED
+        count, len(timesteps) <= steps."""
+        if spacing not in self.SPACINGS:
+            raise ValueError(f"spacing={spacing!r}: None, 'uniform' or 'logsnr'")
+        if spacing == "logsnr":
+            if not use_ddim:
+                raise ValueError("spacing='logsnr' needs use_ddim=True")
+            steps = self.timesteps if steps is None else int(steps)
+            if steps < 1:
+                raise ValueError(f"steps={steps}: at least one iteration")
+            ac = self.host_tables()["alphas_cumprod"].to(torch.float64)[: self.T]
+            lam = 0.5 * torch.log(ac / (1 - ac))
+            targets = torch.linspace(float(lam[0]), float(lam[self.T - 1]), steps, dtype=torch.float64)
+            ts = [int((lam - v).abs().argmin()) for v in targets]
+            ts[-1] = self.T - 1
+            ts[0] = 0      # (steps == 1: the one iteration is t = 0, like linspace(0, T - 1, 1))
+            ts = sorted(set(ts))
+            return ts, len(ts)
         if use_ddim:
             steps = self.timesteps if steps is None else steps
             arr = torch.linspace(0, self.T - 1, steps, dtype=torch.long)
         else:
             arr = self.timesteps_array.detach().cpu()[slice(0, steps)]
         return [int(v) for v in arr], (steps if steps is not None else len(arr))
+
+    def solver_records(self, timesteps: List[int], sampler: str, start: int = 0) -> List[L.MfSolverStep]:
+        """One MfSolverStep row per EXECUTED iteration i = start .. len - 1 of the loop over reversed(timesteps), for a deterministic sampler:
+          "ddim0"   the reference's DDIM update (diffusion_pipeline.py:297-304) at sigma = 0, x_next = B x_0 + A x_T: the scalars are the
+                    ones step_records(eta=0) computes with the reference's fp32 torch ops (B = ddim_sqrt_an, A = ddim_c);
+          "dpmpp2m" DPM-Solver++(2M), data prediction (Lu et al. 2022, Algorithm 2): alpha = sqrt(ac), sigma = sqrt(1 - ac), lambda = log(alpha / sigma),
+                    h = lambda_next - lambda_t, x_next = (sigma_next / sigma_t) x_t - alpha_next expm1(-h) D, D = x_0 on the first executed transition,
+                    else (1 + 1/(2r)) x_0 - 1/(2r) x_0_prev with r = h_prev / h.  Evaluated in fp64 from the alphas_cumprod table; the three
+                    coefficients of x_next = A x_t + B x_0 + C x_0_prev are rounded to fp32 once.
+        The last iteration (the grid's lowest timestep) returns its x_0 estimate (MF_SOLVER_FINAL), as the reference's last iteration does (Q9)."""
+        if sampler not in self.SAMPLERS:
+            raise ValueError(f"sampler={sampler!r}: one of {self.SAMPLERS}")
+        tb = self.host_tables()
+        rev = list(reversed(timesteps))
+        if not 0 <= start < max(1, len(rev)):
+            raise ValueError(f"start={start} of {len(rev)} iterations")
+        if sampler == "dpmpp2m" and any(b <= a for a, b in zip(timesteps, timesteps[1:])):
+            raise ValueError("sampler='dpmpp2m' needs strictly increasing timesteps (a repeated timestep has h = 0): steps <= T")
+        ddim = self.step_records(timesteps, True, eta=0) if sampler == "ddim0" else None
+        ac = tb["alphas_cumprod"].to(torch.float64)
+        alpha, sigma = torch.sqrt(ac), torch.sqrt(1 - ac)
+        lam = torch.log(alpha / sigma)
+        recs, h_prev = [], None
+        for i in range(start, len(rev)):
+            t = rev[i]
+            r = L.MfSolverStep()
+            r.sqrt_recip_ac = float(tb["sqrt_recip_alphas_cumprod"][t])
+            r.sqrt_recipm1_ac = float(tb["sqrt_recipm1_alphas_cumprod"][t])
+            r.t, r.reserved = int(t), 0
+            r.A = r.B = r.C = 0.0
+            if i == len(rev) - 1:
+                r.mode = L.SOLVER_FINAL
+            elif sampler == "ddim0":
+                r.A, r.B, r.mode = ddim[i].ddim_c, ddim[i].ddim_sqrt_an, L.SOLVER_DDIM0
+            else:
+                tn = rev[i + 1]
+                h = float(lam[tn] - lam[t])
+                e = -float(alpha[tn]) * math.expm1(-h)
+                r.A = float(sigma[tn] / sigma[t])
+                if h_prev is None:
+                    r.B, r.mode = e, L.SOLVER_ORDER1
+                else:
+                    k = 1.0 / (2.0 * (h_prev / h))
+                    r.B, r.C, r.mode = e * (1.0 + k), -e * k, L.SOLVER_ORDER2
+                h_prev = h
+            recs.append(r)
+        return recs
+
+    @staticmethod
+    def upload_solver_records(recs: List[L.MfSolverStep], device) -> torch.Tensor:
+        arr = (L.MfSolverStep * len(recs))(*recs)
+        return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).clone().to(device)
 
     def step_records(self, timesteps: List[int], use_ddim: bool, eta=1) -> List[L.MfSchedStep]:
         """One record per loop iteration i (t = reversed(timesteps)[i]), every scalar computed with the same

@@ -12,6 +12,7 @@ thread): one PNG per input, same file name, under --out.
 
 The mask PNG has the images' size; non-zero pixels are REGENERATED, zero pixels kept (a latent cell is regenerated if any of its pixels is).
 Draws: #0 diffuses the encoded image, then the loop's draws as in sample() (Philox key --seed; the encoder's draw uses key --seed + 1).
+--sampler ddim0 | dpmpp2m (with --spacing logsnr: fewer iterations for the same solver accuracy) runs the loop deterministically: draw #0 only.
 """
 import argparse
 import sys
@@ -56,6 +57,8 @@ if __name__ == "__main__":
     ap.add_argument("--guidance", type=float, default=1.0)
     ap.add_argument("--condition", type=int, default=None, help="class label for every image")
     ap.add_argument("--ddpm", action="store_true", help="the posterior loop instead of DDIM")
+    ap.add_argument("--sampler", default=None, choices=["ddim0", "dpmpp2m"], help="a deterministic few-step sampler in place of the stochastic update")
+    ap.add_argument("--spacing", default=None, choices=["uniform", "logsnr"], help="timestep grid of --sampler (logsnr: uniform in log-SNR)")
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--save-tensor", action="store_true", help="also write result.pt: the fp32 images behind the PNG files")
@@ -86,6 +89,7 @@ if __name__ == "__main__":
         # (one Philox key for the whole folder, the chunk's rows at their global offset: the result does not depend on --batch)
         res = pipeline.sample_from(x, args.strength, condition=cond, mask=None if mask is None else mask.expand(n, -1, -1, -1).contiguous(),
                                    steps=args.steps, use_ddim=not args.ddpm, guidance_scale=args.guidance, un_cond=None, composite=mask is not None,
+                                   sampler=args.sampler, spacing=args.spacing,
                                    noise=_ChunkNoise(args.seed, lo, len(files)), encode_noise=_ChunkNoise(args.seed + 1, lo, len(files)))
         writer.submit(res, [out / f.name for f in chunk])
         if args.save_tensor:

@@ -40,7 +40,10 @@ if __name__ == "__main__":
     ap.add_argument("--no-files", action="store_true", help="run the egress (device conversion + async copy) but skip the PNG encoder")
     ap.add_argument("--compare-no-egress", action="store_true", help="also time the same generation with the images left on the device")
     ap.add_argument("--writer-threads", type=int, default=2, help="PNG encoder threads of the asynchronous writer")
+    ap.add_argument("--sampler", default=None, choices=["ddim0", "dpmpp2m"], help="a deterministic few-step sampler (default: the reference's loop)")
+    ap.add_argument("--spacing", default=None, choices=["uniform", "logsnr"], help="timestep grid of --sampler (logsnr: uniform in log-SNR)")
     args = ap.parse_args()
+    solver = {} if args.sampler is None and args.spacing is None else dict(sampler=args.sampler, spacing=args.spacing)
 
     device = torch.device("cuda")
     if args.synthetic:
@@ -68,7 +71,7 @@ if __name__ == "__main__":
                 for chunk in chunks(list(range(args.n_samples)), args.sample_batch):
                     condition = torch.tensor([label] * len(chunk), device=device)
                     un_cond = torch.tensor([1 - label] * len(chunk), device=device)
-                    results = pipeline.sample(len(chunk), (8, 32, 32), guidance_scale=cfg, condition=condition, un_cond=un_cond, steps=steps)
+                    results = pipeline.sample(len(chunk), (8, 32, 32), guidance_scale=cfg, condition=condition, un_cond=un_cond, steps=steps, **solver)
                     if writer is not None:
                         writer.submit(results, [path_out / f"fake_{counter + i}.png" for i in range(len(chunk))])
                     counter += len(chunk)
