@@ -41,6 +41,28 @@ def _split(x: Act):
     return (x[0], x[1]) if isinstance(x, (tuple, list)) else (x, None)
 
 
+def _inputs(x: Act, in_ch: int, in_layout=L.LAYOUT_NHWC):
+    """(x1, x2, n, h, w, c1, c2) of the input x of a convolution of in_ch channels -- one tensor in `in_layout`, or the pair (x1, x2) whose channel concat it reads"""
+    x1, x2 = _split(x)
+    if in_layout == L.LAYOUT_NCHW:
+        n, c1, h, w = x1.shape
+    else:
+        n, h, w, c1 = x1.shape
+    c2 = 0 if x2 is None else x2.shape[-1]
+    if c1 + c2 != in_ch:
+        raise RuntimeError(f"conv expects {in_ch} input channels, got {c1}+{c2}")
+    return x1, x2, n, h, w, c1, c2
+
+
+def _cached(cache: dict, key, plan, *args):
+    """cache[key], made by plan(*args) on a miss: the plan of a convolution / a block for one input shape under one set of switches, or False -- the one
+    "not on this path" answer of every per-shape cache here (Conv._descs, Conv._pairs_out, BasicResBlock._group, BasicResBlock._pairs_ok)"""
+    ent = cache.get(key)
+    if ent is None:
+        ent = cache[key] = plan(*args) or False
+    return ent
+
+
 class _Packed:
     """Lazily packed device copy of a conv weight, invalidated by in-place parameter updates."""
 
@@ -198,26 +220,30 @@ class Conv(nn.Module):
         self._wino_sites = {}     # shape key -> a consumer transformed this output into the Winograd domain: write V in the tail from now on
         self._bmax = (None, 0.0)
 
+    def out_hw(self, h: int, w: int):
+        """output size for an h x w input (before any upsampling; K.conv_out_hw answers for a descriptor)"""
+        return (h + 2 * self.pad - self.k) // self.stride + 1, (w + 2 * self.pad - self.k) // self.stride + 1
+
+    def _plan_f16x2(self, n, h, w, c1, c2, gn_groups, prec, cin_pad):
+        """(descriptor, GroupNorm parts, on the fp16-pair kernel?, pinned sizes, (descriptor, parts, pinned sizes) of the Winograd form or None)"""
+        d = K.make_conv_desc(n, h, w, c1, c2, self.out_ch, self.k, self.stride, self.pad, 2 if self.upsample else 0, precision=prec)
+        ok = K.conv_f16x2_ok(d)
+        pinned = K.pin_conv_plan(d) if ok else None     # (tile, split-K) fixed in the descriptor: per-launch planning is a field read
+        wino = None
+        if ok and prec == 5 and not cin_pad and self.k == 3 and wino_wanted(d):
+            # the Winograd form is the faster one for this shape (mf_wino_preferred): 2.25x fewer matrix instructions
+            wparts = K.wino_gn_parts(d, gn_groups) if gn_groups else 0
+            if not gn_groups or wparts > 0:
+                wt, wsk = WINO_SHAPES.get((n, h, w, c1 + c2, self.out_ch), (0, 0))
+                wd = K.make_conv_desc(n, h, w, c1, c2, self.out_ch, self.k, self.stride, self.pad, 0, tile_hint=wt, splitk_hint=wsk, precision=prec)   # (hints address the component GEMM)
+                wino = (wd, wparts, K.pin_wino_plan(wd))
+        return d, K.conv_gn_parts(d, gn_groups) if (ok and gn_groups) else 0, ok, pinned, wino
+
     def _forward_f16x2(self, x1, x2, n, h, w, c1, c2, out, gn_groups, gn_eps, measure_out, prec=5, derive_out=False, cin_pad=0):
         """MF_CONV_FP32_F16X2 (prec 5) / MF_CONV_F16 (prec 6), or None when this convolution is not on that kernel.
         cin_pad: the weights zero-padded to that many input channels (the input convolution on a padded pair operand)"""
         key = ("f16x2", n, h, w, c1, c2, gn_groups, prec, WINOGRAD)
-        ent = self._descs.get(key)
-        if ent is None:
-            d = K.make_conv_desc(n, h, w, c1, c2, self.out_ch, self.k, self.stride, self.pad, 2 if self.upsample else 0, precision=prec)
-            ok = K.conv_f16x2_ok(d)
-            pinned = K.pin_conv_plan(d) if ok else None     # (tile, split-K) fixed in the descriptor: per-launch planning is a field read
-            wino = None
-            if ok and prec == 5 and not cin_pad and self.k == 3 and wino_wanted(d):
-                # the Winograd form is the faster one for this shape (mf_wino_preferred): 2.25x fewer matrix instructions
-                wparts = K.wino_gn_parts(d, gn_groups) if gn_groups else 0
-                if not gn_groups or wparts > 0:
-                    wt, wsk = WINO_SHAPES.get((n, h, w, c1 + c2, self.out_ch), (0, 0))
-                    wd = K.make_conv_desc(n, h, w, c1, c2, self.out_ch, self.k, self.stride, self.pad, 0, tile_hint=wt, splitk_hint=wsk, precision=prec)   # (hints address the component GEMM)
-                    wino = (wd, wparts, K.pin_wino_plan(wd))
-            ent = (d, K.conv_gn_parts(d, gn_groups) if (ok and gn_groups) else 0, ok, pinned, wino)
-            self._descs[key] = ent
-        d, parts, ok, pinned, wino = ent
+        d, parts, ok, pinned, wino = _cached(self._descs, key, self._plan_f16x2, n, h, w, c1, c2, gn_groups, prec, cin_pad)
         if not ok:
             return None
         if wino is not None and out is None and not measure_out and not derive_out:
@@ -234,10 +260,7 @@ class Conv(nn.Module):
                 # 23 bits down to 2^-28 of the bound) but it compounds -- derived from derived along the residual stream (conv_res ->
                 # apply -> conv_res ...) it reached 2^44 x the data after seven blocks and the pairs lost their bits (scripts/debug_derived.py,
                 # round 4).  The consumers of a down- / up-sampled tensor are a GroupNorm'd convolution and a conv_res that MEASURES: both reset.
-                po = self._pairs_out.get(key)
-                if po is None:
-                    po = self._pairs_out[key] = K.conv_pairs_out_ok(d)
-                if po:
+                if _cached(self._pairs_out, key, K.conv_pairs_out_ok, d):
                     bkey = (self.bias._version, self.bias.data_ptr())
                     if self._bmax[0] != bkey:
                         self._bmax = (bkey, float(self.bias.detach().abs().max().item()))
@@ -255,34 +278,26 @@ class Conv(nn.Module):
         return y, K.gn_finalize(partial, parts, ho * wo, self.out_ch, gn_groups, gn_eps)   # (more groups than a workgroup has threads)
 
     def wino_tail_desc(self, x: Act, G: int):
-        """(descriptor, pinned sizes) of this convolution on the Winograd form with its GroupNorm tail for the input x, or None; cached per shape"""
-        x1, x2 = _split(x)
-        n, h, w, c1 = x1.shape
-        c2 = 0 if x2 is None else x2.shape[-1]
+        """(cache key, (descriptor, pinned sizes)) of this convolution on the Winograd form with its GroupNorm tail for the input x -- (key, None) when it is
+        not on that form; cached per shape"""
+        _, _, n, h, w, c1, c2 = _inputs(x, self.in_ch)
         key = ("wino_tail", n, h, w, c1, c2, G, WINOGRAD, WINO_TAIL)
-        ent = self._descs.get(key)
-        if ent is None:
-            ent = False
-            if WINO_TAIL and CONV_PRECISION == 5 and self.k == 3 and self.stride == 1 and not self.upsample and c1 + c2 == self.in_ch:
-                d = K.make_conv_desc(n, h, w, c1, c2, self.out_ch, self.k, self.stride, self.pad, 0, precision=5)
-                if wino_wanted(d) and K.wino_tail_ok(d, G):
-                    wt, wsk = WINO_SHAPES.get((n, h, w, c1 + c2, self.out_ch), (0, 0))
-                    d.tile_hint, d.splitk_hint = wt, wsk
-                    ent = (d, K.pin_wino_plan(d))
-            self._descs[key] = ent
-        return (key, ent) if ent is not False else (key, None)
+        return key, (_cached(self._descs, key, self._plan_wino_tail, n, h, w, c1, c2, G) or None)
+
+    def _plan_wino_tail(self, n, h, w, c1, c2, G):
+        if WINO_TAIL and CONV_PRECISION == 5 and self.k == 3 and self.stride == 1 and not self.upsample:
+            d = K.make_conv_desc(n, h, w, c1, c2, self.out_ch, self.k, self.stride, self.pad, 0, precision=5)
+            if wino_wanted(d) and K.wino_tail_ok(d, G):
+                d.tile_hint, d.splitk_hint = WINO_SHAPES.get((n, h, w, c1 + c2, self.out_ch), (0, 0))
+                return d, K.pin_wino_plan(d)
 
     def forward_wino_gn_apply(self, x: Act, norm, act: int, residual, emb, emb_stride, out_fp32, bconst, guest=None):
         """conv -> GroupNorm -> Swish -> + residual -> + emb on the Winograd form, the tail in ONE launch behind the component GEMM
         (mf_conv2d_wino_gn_apply_f16x2), or None when this convolution is not on that path for this shape.  The output carries its transform-domain
         mirror as well once a Winograd convolution has asked for it (K.wino_input marks the site): the next call writes it in the tail."""
         x1, x2 = _split(x)
-        n, h, w, c1 = x1.shape
-        c2 = 0 if x2 is None else x2.shape[-1]
-        if c1 + c2 != self.in_ch:
-            raise RuntimeError(f"conv expects {self.in_ch} input channels, got {c1}+{c2}")
         G = norm.num_groups
-        key, ent = self.wino_tail_desc(x, G)
+        key, ent = self.wino_tail_desc(x, G)      # (checks the channel count)
         if ent is None:
             return None
         d, pinned = ent
@@ -293,65 +308,68 @@ class Conv(nn.Module):
             y._mf_wino_site = (self._wino_sites, key)
         return y
 
+    def _plan_wino_f32(self, n, h, w, c1, c2, G, mode, split3):
+        if self.k == 3 and self.stride == 1 and not self.upsample:
+            d = K.make_conv_desc(n, h, w, c1, c2, self.out_ch, 3, 1, 1, 0, precision=3 if split3 else 0)
+            if K.wino_f32_ok(d, G) and K.conv_is_igemm(d):
+                rule = K.make_conv_desc(n, h, w, c1, c2, self.out_ch, 3, 1, 1, 0, precision=5)   # (the shape rule of mf_wino_preferred speaks of the pair arithmetic's descriptor)
+                # (1: the pair arithmetic's rule, plus every shape up to 16 x 16 -- with six matrix terms per product the low-channel shapes the pair
+                # arithmetic leaves direct gain here too: +0.95 % on the step, profiles/r06_small_ab.txt section 7; the 32 x 32 level loses: mode 2)
+                if mode == 2 or h * w <= 256 or K.wino_preferred(rule):
+                    return d
+
     def forward_wino_gn_apply_f32(self, x: Act, norm, act: int, residual, emb, emb_stride, split3: bool = True):
         """conv -> GroupNorm -> Swish -> + residual -> + emb on the Winograd form of the exact bf16-triplet arithmetic (kernels.conv2d_wino_gn_apply_f32), or
         None when this convolution is not on that path for this shape.  Like the fp16-pair form, the output carries V for the next Winograd
         convolution once one has asked for it (the site flag is learnt on the eager first iteration)."""
-        x1, x2 = _split(x)
-        n, h, w, c1 = x1.shape
-        c2 = 0 if x2 is None else x2.shape[-1]
+        x1, x2, n, h, w, c1, c2 = _inputs(x, self.in_ch)
         G = norm.num_groups
         mode = WINOGRAD_F32 if split3 else WINOGRAD_F32_MFMA
         key = ("wino_f32", n, h, w, c1, c2, G, mode, split3)
-        ent = self._descs.get(key)
-        if ent is None:
-            ent = False
-            if self.k == 3 and self.stride == 1 and not self.upsample and c1 + c2 == self.in_ch:
-                d = K.make_conv_desc(n, h, w, c1, c2, self.out_ch, 3, 1, 1, 0, precision=3 if split3 else 0)
-                if K.wino_f32_ok(d, G) and K.conv_is_igemm(d):
-                    rule = K.make_conv_desc(n, h, w, c1, c2, self.out_ch, 3, 1, 1, 0, precision=5)   # (the shape rule of mf_wino_preferred speaks of the pair arithmetic's descriptor)
-                    # (1: the pair arithmetic's rule, plus every shape up to 16 x 16 -- with six matrix terms per product the low-channel shapes the pair
-                    # arithmetic leaves direct gain here too: +0.95 % on the step, profiles/r06_small_ab.txt section 7; the 32 x 32 level loses: mode 2)
-                    if mode == 2 or h * w <= 256 or K.wino_preferred(rule):
-                        ent = d
-            self._descs[key] = ent
-        if ent is False:
+        d = _cached(self._descs, key, self._plan_wino_f32, n, h, w, c1, c2, G, mode, split3)
+        if not d:
             return None
         K._need_f32(x1, x2, residual)
         want = self._wino_sites.get(key, False)
-        y = K.conv2d_wino_gn_apply_f32(x1, self._packed.get_wino_f32(self.weight, split3), self.bias, ent, norm.weight, norm.bias, G, norm.eps, act=act,
+        y = K.conv2d_wino_gn_apply_f32(x1, self._packed.get_wino_f32(self.weight, split3), self.bias, d, norm.weight, norm.bias, G, norm.eps, act=act,
                                        residual=residual, emb=emb, emb_stride=emb_stride, x2=x2, want_wino=want)
         if not want:
             y._mf_wino_site_f32 = (self._wino_sites, key)
         return y
 
+    def _plan_fused(self, n, h, w, c1, c2, G, prec):
+        d = K.make_conv_desc(n, h, w, c1, c2, self.out_ch, self.k, self.stride, self.pad, 2 if self.upsample else 0, precision=prec)
+        ho, wo = K.conv_out_hw(d)
+        if K.conv_f16x2_ok(d) and not self.upsample and ho * wo >= K.FUSE_MIN_HW:
+            pinned = K.pin_conv_plan(d)
+            parts, words = K.conv_gn_parts(d, G), K.conv_fuse_words(d, G)
+            if parts > 0 and words > 0:
+                return d, parts, words, pinned
+
     def forward_gn_apply(self, x: Act, norm, act: int, residual, emb, emb_stride, out_fp32, bconst):
         """conv -> GroupNorm -> Swish -> + residual -> + emb in ONE launch (mf_conv2d_f16x2_gn_apply), or None when this convolution cannot
         (not on the fp16-pair kernel, or a plan whose workgroups are not all resident at once): the caller takes the two-launch form"""
-        x1, x2 = _split(x)
-        n, h, w, c1 = x1.shape
-        c2 = 0 if x2 is None else x2.shape[-1]
-        if c1 + c2 != self.in_ch:
-            raise RuntimeError(f"conv expects {self.in_ch} input channels, got {c1}+{c2}")
+        x1, x2, n, h, w, c1, c2 = _inputs(x, self.in_ch)
         prec = CONV_PRECISION
         G = norm.num_groups
-        key = ("fused", n, h, w, c1, c2, G, prec)
-        ent = self._descs.get(key)
-        if ent is None:
-            d = K.make_conv_desc(n, h, w, c1, c2, self.out_ch, self.k, self.stride, self.pad, 2 if self.upsample else 0, precision=prec)
-            ent = (None, 0, 0, None)
-            ho, wo = K.conv_out_hw(d)
-            if K.conv_f16x2_ok(d) and not self.upsample and ho * wo >= K.FUSE_MIN_HW:
-                pinned = K.pin_conv_plan(d)
-                parts, words = K.conv_gn_parts(d, G), K.conv_fuse_words(d, G)
-                if parts > 0 and words > 0:
-                    ent = (d, parts, words, pinned)
-            self._descs[key] = ent
-        d, parts, words, pinned = ent
-        if d is None or K.Rendezvous.disabled:
+        ent = _cached(self._descs, ("fused", n, h, w, c1, c2, G, prec), self._plan_fused, n, h, w, c1, c2, G, prec)
+        if not ent or K.Rendezvous.disabled:
             return None
+        d, parts, words, pinned = ent
         return K.conv2d_f16x2_gn_apply(x1, self._packed.get_f16x2(self.weight), self.bias, d, norm.weight, norm.bias, G, norm.eps, parts, words, act=act,
                                        residual=residual, emb=emb, emb_stride=emb_stride, x2=x2, bconst=bconst, out_fp32=out_fp32, pinned=pinned)
+
+    def _plan_direct(self, n, h, w, c1, c2, cout, in_layout, out_layout, rows, gn_groups, prec):
+        """(descriptor, GroupNorm parts) of this convolution on the fp32 / exact / reduced kernels (every arithmetic but the fp16 pairs)"""
+        dp = 3 if prec == 1 else prec   # exact bf16 triplets = MF_CONV_FP32_SPLIT3_W3 (the weights are split once at load)
+        d = K.make_conv_desc(n, h, w, c1, c2, cout, self.k, self.stride, self.pad, self.upsample, in_layout, out_layout, precision=dp)
+        if self.upsample and SUBPIXEL_UPSAMPLE and rows is None:
+            d2 = K.make_conv_desc(n, h, w, c1, c2, cout, self.k, self.stride, self.pad, 2, in_layout, out_layout, precision=dp)
+            if K.subpixel_ok(d2):  # 4 phase-specific 2x2 convs on the low-res tensor: 4/9 of the MACs
+                d = d2
+        if d.precision in (3, 4) and (rows is not None or not K.conv_is_igemm(d)):
+            d.precision = 0  # the small / edge convolutions are not on the implicit-GEMM kernel (and a row slice has no converted weights): plain fp32
+        return d, K.conv_gn_parts(d, gn_groups) if gn_groups else 0
 
     def forward(self, x: Act, in_layout=L.LAYOUT_NHWC, out_layout=L.LAYOUT_NHWC, out=None, rows: Optional[slice] = None, gn_groups: int = 0,
                 gn_eps: float = 1e-5, measure_out: bool = False, derive_out: bool = False):
@@ -359,14 +377,7 @@ class Conv(nn.Module):
         measure_out: in the fp16-pair mode, also measure the per-sample max |y| (y feeds a convolution or a residual add un-normalised).
         derive_out: ... or, where the plan allows, write y's fp16-pair form in the epilogue under a bound DERIVED from the operands (see
         _forward_f16x2; only for tensors whose bound does not propagate: the outputs of down- / up-sampling)."""
-        x1, x2 = _split(x)
-        if in_layout == L.LAYOUT_NCHW:
-            n, c1, h, w = x1.shape
-        else:
-            n, h, w, c1 = x1.shape
-        c2 = 0 if x2 is None else x2.shape[-1]
-        if c1 + c2 != self.in_ch:
-            raise RuntimeError(f"conv expects {self.in_ch} input channels, got {c1}+{c2}")
+        x1, x2, n, h, w, c1, c2 = _inputs(x, self.in_ch, in_layout)
         prec = CONV_PRECISION
         if prec not in (0, 1, 4, 5, 6):
             raise RuntimeError(f"blocks.CONV_PRECISION = {prec}: 0 (fp32 MFMA), 1 (exact bf16 triplets), 5 (fp16 pairs, default), or the opt-in "
@@ -392,20 +403,8 @@ class Conv(nn.Module):
             prec = 1  # not on the fp16-pair kernel (edge convolutions, odd channel counts): the exact bf16-triplet / plain fp32 kernels
             K._need_f32(x1, x2)
         key = (n, h, w, c1, c2, in_layout, out_layout, rows.start if rows else None, gn_groups, prec)
-        ent = self._descs.get(key)
         cout = self.out_ch if rows is None else rows.stop - rows.start
-        if ent is None:
-            dp = 3 if prec == 1 else prec   # exact bf16 triplets = MF_CONV_FP32_SPLIT3_W3 (the weights are split once at load)
-            d = K.make_conv_desc(n, h, w, c1, c2, cout, self.k, self.stride, self.pad, self.upsample, in_layout, out_layout, precision=dp)
-            if self.upsample and SUBPIXEL_UPSAMPLE and rows is None:
-                d2 = K.make_conv_desc(n, h, w, c1, c2, cout, self.k, self.stride, self.pad, 2, in_layout, out_layout, precision=dp)
-                if K.subpixel_ok(d2):  # 4 phase-specific 2x2 convs on the low-res tensor: 4/9 of the MACs
-                    d = d2
-            if d.precision in (3, 4) and (rows is not None or not K.conv_is_igemm(d)):
-                d.precision = 0  # the small / edge convolutions are not on the implicit-GEMM kernel (and a row slice has no converted weights): plain fp32
-            ent = (d, K.conv_gn_parts(d, gn_groups) if gn_groups else 0)
-            self._descs[key] = ent
-        d, parts = ent
+        d, parts = _cached(self._descs, key, self._plan_direct, n, h, w, c1, c2, cout, in_layout, out_layout, rows, gn_groups, prec)
         pk = self._packed_sub if d.upsample == 2 else self._packed
         wp = pk.get_split(self.weight) if d.precision == 3 else pk.get_bf16(self.weight) if d.precision == 4 else pk.get(self.weight)
         b = self.bias
@@ -489,7 +488,7 @@ class BasicBlock(nn.Module):
                 # one launch for conv + GroupNorm + Swish + residual + embedding where the plan allows it (conv_f16x2.h: FuseP)
                 nm = self.norm
                 x1 = _split(x)[0]
-                ho, wo = (x1.shape[1] + 2 * self.conv.pad - self.conv.k) // self.conv.stride + 1, (x1.shape[2] + 2 * self.conv.pad - self.conv.k) // self.conv.stride + 1
+                ho, wo = self.conv.out_hw(x1.shape[1], x1.shape[2])
                 bc = nm.bound_const(ho * wo * (self.conv.out_ch // nm.num_groups))
                 y = self.conv.forward_gn_apply(x, nm, int(self.has_act), residual, emb, emb_stride, out_fp32, bc)
                 if y is not None:
@@ -502,23 +501,17 @@ class BasicBlock(nn.Module):
             raise RuntimeError("act/residual epilogue needs NHWC")
         return K.gn_apply(y, None, None, None, 1, int(self.has_act), residual, emb, emb_stride, out=y)
 
+    def conv_and_stats(self, x, in_layout=L.LAYOUT_NHWC):
+        """conv (+ fused GroupNorm statistics) -> (y, stats)"""
+        return self.conv(x, in_layout=in_layout, gn_groups=self.norm.num_groups, gn_eps=self.norm.eps)
 
-def _basicblock_conv_and_stats(self, x, in_layout=L.LAYOUT_NHWC):
-    """conv (+ fused GroupNorm statistics) -> (y, stats)"""
-    return self.conv(x, in_layout=in_layout, gn_groups=self.norm.num_groups, gn_eps=self.norm.eps)
-
-
-def _basicblock_finish(self, y_stats, residual=None, emb=None, emb_stride=0, out_fp32=True):
-    y, stats = y_stats
-    nm = self.norm
-    split = f16x2_mode()
-    bc = nm.bound_const(y.shape[1] * y.shape[2] * (y.shape[3] // nm.num_groups)) if split else 0.0
-    return K.gn_apply(y, stats, nm.weight, nm.bias, nm.num_groups, int(self.has_act), residual, emb, emb_stride, out=y, split=split, bconst=bc,
-                      out_fp32=out_fp32)
-
-
-BasicBlock.conv_and_stats = _basicblock_conv_and_stats
-BasicBlock.finish = _basicblock_finish
+    def finish(self, y_stats, residual=None, emb=None, emb_stride=0, out_fp32=True):
+        y, stats = y_stats
+        nm = self.norm
+        split = f16x2_mode()
+        bc = nm.bound_const(y.shape[1] * y.shape[2] * (y.shape[3] // nm.num_groups)) if split else 0.0
+        return K.gn_apply(y, stats, nm.weight, nm.bias, nm.num_groups, int(self.has_act), residual, emb, emb_stride, out=y, split=split, bconst=bc,
+                          out_fp32=out_fp32)
 
 
 class BasicResBlock(nn.Module):
@@ -530,6 +523,7 @@ class BasicResBlock(nn.Module):
         super().__init__()
         self.basic_block = BasicBlock(spatial_dims, in_channels, out_channels, kernel_size, stride, norm_name, act_name, dropout, zero_conv)
         self.conv_res = Conv(in_channels, out_channels, 1, stride, monai_padding(1, stride)) if in_channels != out_channels else nn.Identity()
+        self.in_ch = in_channels
         self._pairs_ok = {}
         self._group = {}
 
@@ -562,80 +556,66 @@ class BasicResBlock(nn.Module):
         res = self.conv_res(x, in_layout=in_layout, measure_out=f16x2_mode())
         return self.basic_block(x, residual=res, emb=emb, emb_stride=emb_stride, in_layout=in_layout, out_fp32=out_fp32)
 
+    def _guest_candidates(self, n, h, w, c1, c2, own_tile_first: bool, override: bool):
+        """conv_res as the guest of a launch it shares with the block's 3x3, for an [n, h, w, c1 | c2] input: (descriptor, pinned) of every candidate that is
+        on the fp16-pair kernel, in order of preference -- own_tile_first: the tile the planner gives it alone (a host of the same workgroup size takes
+        it as it is); then the guest tiles of the 8-wave hosts, the one whose grid is closest to one workgroup per CU first
+        (profiles/r04_conv_sweep_planner_vs_best.txt); then 53, the 4-wave guest of a 4-wave host tile (the round-6 GEMM model picks tile 54 for
+        1536 -> 512 at 8 x 8).  override: blocks.GROUP_GUEST may name the one tile (or (tile, split-K)) to try, or -1 for none."""
+        cr = self.conv_res
+        ho, wo = cr.out_hw(h, w)
+        m = n * ho * wo
+        t36, t37 = -(-m // 128) * (cr.out_ch // 64), -(-m // 64) * max(cr.out_ch // 256, 1)
+        wide = (36, 37) if abs(t36 - 256) <= abs(t37 - 256) or cr.out_ch % 256 else (37, 36)
+        # (the guest keeps the SPLIT-K of the plan it has alone: the tile only partitions pixels and output channels, but the number of
+        # K slices is the summation order -- with it fixed, the block gives the same bits whether or not the pair shares a launch)
+        nat = K.make_conv_desc(n, h, w, c1, c2, cr.out_ch, cr.k, cr.stride, cr.pad, 0, precision=5)
+        sk0 = K.conv_plan(nat)[1] if K.conv_f16x2_ok(nat) else 0
+        forced = GROUP_GUEST.get((n, h, w, c1, c2, cr.out_ch)) if override else None
+        if isinstance(forced, tuple):      # (tile, split-K): the tuner may also try another summation order (same value to fp32 rounding)
+            forced, sk0 = forced
+        for tile in (((0,) if own_tile_first else ()) + (*wide, 53) if forced is None else () if forced < 0 else (forced,)):
+            if (tile == 37 and cr.out_ch % 256) or sk0 <= 0:
+                continue
+            db = K.make_conv_desc(n, h, w, c1, c2, cr.out_ch, cr.k, cr.stride, cr.pad, 0, tile_hint=tile, splitk_hint=sk0 if tile else 0, precision=5)
+            if K.conv_f16x2_ok(db):
+                yield db, K.pin_conv_plan(db)
+
     def _wino_guest(self, x):
         """(descriptor, pinned) of conv_res as the guest of the 3x3's Winograd component GEMM for this input shape, or None; cached per shape.
         The guest keeps the split-K of the plan it has alone (the summation order: same bits as its own launch), on an 8-wave tile."""
-        x1, x2 = _split(x)
-        n, h, w, c1 = x1.shape
-        c2 = 0 if x2 is None else x2.shape[-1]
-        key = ("wino", n, h, w, c1, c2, WINOGRAD, WINO_TAIL)
-        if key in self._group:
-            return self._group[key]
-        ent = None
-        c3, cr, nm = self.basic_block.conv, self.conv_res, self.basic_block.norm
-        _, tail = c3.wino_tail_desc(x, nm.num_groups) if (c1 + c2 == c3.in_ch) else (None, None)
+        _, _, n, h, w, c1, c2 = _inputs(x, self.in_ch)
+        return _cached(self._group, ("wino", n, h, w, c1, c2, WINOGRAD, WINO_TAIL), self._plan_wino_guest, x, n, h, w, c1, c2) or None
+
+    def _plan_wino_guest(self, x, n, h, w, c1, c2):
+        cr = self.conv_res
+        tail = self.basic_block.conv.wino_tail_desc(x, self.basic_block.norm.num_groups)[1]
         if tail is not None and cr.k == 1 and cr.stride == 1:
-            nat = K.make_conv_desc(n, h, w, c1, c2, cr.out_ch, cr.k, cr.stride, cr.pad, 0, precision=5)
-            sk0 = K.conv_plan(nat)[1] if K.conv_f16x2_ok(nat) else 0
-            m = n * h * w
-            t36, t37 = -(-m // 128) * (cr.out_ch // 64), -(-m // 64) * max(cr.out_ch // 256, 1)
-            order = (36, 37) if abs(t36 - 256) <= abs(t37 - 256) or cr.out_ch % 256 else (37, 36)
-            for tile in (*order, 53):      # (53: the 4-wave guest of a 4-wave host tile -- the round-6 GEMM model picks tile 54 for 1536 -> 512 at 8 x 8)
-                if (tile == 37 and cr.out_ch % 256) or sk0 <= 0:
-                    continue
-                db = K.make_conv_desc(n, h, w, c1, c2, cr.out_ch, cr.k, cr.stride, cr.pad, 0, tile_hint=tile, splitk_hint=sk0, precision=5)
-                if K.conv_f16x2_ok(db) and K.wino_group_ok(tail[0], db):
-                    pb = K.pin_conv_plan(db)
-                    if pb[1] > 0:      # (its output is measured: the tail reads the slot maxima)
-                        ent = (db, pb)
-                        break
-        self._group[key] = ent
-        return ent
+            for db, pb in self._guest_candidates(n, h, w, c1, c2, False, False):
+                if K.wino_group_ok(tail[0], db) and pb[1] > 0:      # (its output is measured: the tail reads the slot maxima)
+                    return db, pb
 
     def _grouped(self, x):
         """(descriptor, GroupNorm parts, pinned) of the 3x3 + (descriptor, pinned) of conv_res when the two can share a launch for this input
         shape, else None; cached per shape.  conv_res keeps the planner's tile when its workgroup size equals the 3x3's, otherwise the first
         of the guest tiles of that size the pair is instantiated for (descriptor hints)."""
-        x1, x2 = _split(x)
-        n, h, w, c1 = x1.shape
-        c2 = 0 if x2 is None else x2.shape[-1]
-        key = (n, h, w, c1, c2, WINOGRAD, WINO_TAIL)
-        if key in self._group:
-            return self._group[key]
-        ent = None
-        c3, cr, nm = self.basic_block.conv, self.conv_res, self.basic_block.norm
-        G = nm.num_groups
-        if c1 + c2 == c3.in_ch and not c3.upsample and G <= 256:
-            da = K.make_conv_desc(n, h, w, c1, c2, c3.out_ch, c3.k, c3.stride, c3.pad, 0, precision=5)
-            # (a 3x3 that WILL run as Winograd component GEMM + tail has its own shared launch, _wino_guest; asked of the path that is actually taken --
-            # wino_tail_desc -- not of wino_wanted alone: a shape the tail cannot take, or MEDFUSION_WINOGRAD_TAIL=0, keeps this grouped launch.  ADVICE r05)
-            takes_wino_tail = WINO_TAIL and c3.wino_tail_desc(x, G)[1] is not None
-            if K.conv_f16x2_ok(da) and not takes_wino_tail:
-                pa = K.pin_conv_plan(da)
-                parts = K.conv_gn_parts(da, G)
-                # guest tiles of the 8-wave hosts: the one whose grid is closest to one workgroup per CU first (profiles/r04_conv_sweep_planner_vs_best.txt)
-                m = n * ((h + 2 * cr.pad - cr.k) // cr.stride + 1) * ((w + 2 * cr.pad - cr.k) // cr.stride + 1)
-                t36, t37 = -(-m // 128) * (cr.out_ch // 64), -(-m // 64) * max(cr.out_ch // 256, 1)
-                wide = (36, 37) if abs(t36 - 256) <= abs(t37 - 256) or cr.out_ch % 256 else (37, 36)
-                # (the guest keeps the SPLIT-K of the plan it has alone: the tile only partitions pixels and output channels, but the number of
-                # K slices is the summation order -- with it fixed, the block gives the same bits whether or not the pair shares a launch)
-                nat = K.make_conv_desc(n, h, w, c1, c2, cr.out_ch, cr.k, cr.stride, cr.pad, 0, precision=5)
-                sk0 = K.conv_plan(nat)[1] if K.conv_f16x2_ok(nat) else 0
-                forced = GROUP_GUEST.get((n, h, w, c1, c2, cr.out_ch))
-                if isinstance(forced, tuple):      # (tile, split-K): the tuner may also try another summation order (same value to fp32 rounding)
-                    forced, sk0 = forced
-                for tile in ((0, *wide, 53) if forced is None else () if forced < 0 else (forced,)):
-                    if (tile == 37 and cr.out_ch % 256) or sk0 <= 0:
-                        continue
-                    db = K.make_conv_desc(n, h, w, c1, c2, cr.out_ch, cr.k, cr.stride, cr.pad, 0, tile_hint=tile, splitk_hint=sk0 if tile else 0, precision=5)
-                    if not K.conv_f16x2_ok(db):
-                        continue
-                    pb = K.pin_conv_plan(db)
-                    if parts > 0 and pb[1] > 0 and K.conv_group_ok(da, G, db, 0):
-                        ent = (da, parts, pa, db, pb)
-                        break
-        self._group[key] = ent
-        return ent
+        _, _, n, h, w, c1, c2 = _inputs(x, self.in_ch)
+        return _cached(self._group, (n, h, w, c1, c2, WINOGRAD, WINO_TAIL), self._plan_grouped, x, n, h, w, c1, c2) or None
+
+    def _plan_grouped(self, x, n, h, w, c1, c2):
+        c3, G = self.basic_block.conv, self.basic_block.norm.num_groups
+        if c3.upsample or G > 256:
+            return None
+        da = K.make_conv_desc(n, h, w, c1, c2, c3.out_ch, c3.k, c3.stride, c3.pad, 0, precision=5)
+        # (a 3x3 that WILL run as Winograd component GEMM + tail has its own shared launch, _wino_guest; asked of the path that is actually taken --
+        # wino_tail_desc -- not of wino_wanted alone: a shape the tail cannot take, or MEDFUSION_WINOGRAD_TAIL=0, keeps this grouped launch.  ADVICE r05)
+        takes_wino_tail = WINO_TAIL and c3.wino_tail_desc(x, G)[1] is not None
+        if K.conv_f16x2_ok(da) and not takes_wino_tail:
+            pa = K.pin_conv_plan(da)
+            parts = K.conv_gn_parts(da, G)
+            for db, pb in self._guest_candidates(n, h, w, c1, c2, True, True):
+                if parts > 0 and pb[1] > 0 and K.conv_group_ok(da, G, db, 0):
+                    return da, parts, pa, db, pb
 
     def reads_pairs_only(self, n: int, h: int, w: int, c2: int = 0) -> bool:
         """can this block take an [n, h, w, Cin] input (c2 > 0: a fused concat whose second source has c2 channels) that exists as fp16 pairs only?
@@ -643,13 +623,11 @@ class BasicResBlock(nn.Module):
         (mf_conv2d_f16x2_ok on the real descriptor -- tensor size limits, tile fits -- not guessed from channel counts: ADVICE r03), cached per shape"""
         if not (f16x2_mode() and hasattr(self.basic_block, "norm")):
             return False
-        key = (n, h, w, c2, CONV_PRECISION)
-        ok = self._pairs_ok.get(key)
-        if ok is None:
-            convs = [self.basic_block.conv] + ([] if isinstance(self.conv_res, nn.Identity) else [self.conv_res])
-            ok = all(c.in_ch > c2 and K.conv_f16x2_ok(K.make_conv_desc(n, h, w, c.in_ch - c2, c2, c.out_ch, c.k, c.stride, c.pad, 0, precision=CONV_PRECISION)) for c in convs)
-            self._pairs_ok[key] = ok
-        return ok
+        return _cached(self._pairs_ok, (n, h, w, c2, CONV_PRECISION), self._convs_on_pairs, n, h, w, c2)
+
+    def _convs_on_pairs(self, n, h, w, c2):
+        convs = [self.basic_block.conv] + ([] if isinstance(self.conv_res, nn.Identity) else [self.conv_res])
+        return all(c.in_ch > c2 and K.conv_f16x2_ok(K.make_conv_desc(n, h, w, c.in_ch - c2, c2, c.out_ch, c.k, c.stride, c.pad, 0, precision=CONV_PRECISION)) for c in convs)
 
 
 class _EmbBlock(nn.Module):
@@ -686,8 +664,7 @@ class _EmbBlock(nn.Module):
                 if PAIRS_ONLY_BETWEEN_BLOCKS and nxt is not None:
                     x1 = _split(x)[0]
                     nn_, hh, ww = (x1.shape[0], x1.shape[2], x1.shape[3]) if lay == L.LAYOUT_NCHW else (x1.shape[0], x1.shape[1], x1.shape[2])
-                    c0 = blk.basic_block.conv
-                    ho, wo = (hh + 2 * c0.pad - c0.k) // c0.stride + 1, (ww + 2 * c0.pad - c0.k) // c0.stride + 1   # shape of THIS block's output
+                    ho, wo = blk.basic_block.conv.out_hw(hh, ww)   # shape of THIS block's output
                     pairs_next = nxt.reads_pairs_only(nn_, ho, wo)
                 x = blk(x, emb=e, emb_stride=es, in_layout=lay, out_fp32=(not pairs_next) if nxt is not None else out_fp32)
             else:

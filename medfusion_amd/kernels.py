@@ -47,44 +47,33 @@ def scratch_growth_count() -> int:
     return _growths
 
 
-class Workspace:
-    """Grow-only scratch owned by torch (the library never allocates).  One per (device, stream): launches on one
-    stream are serialised so sharing is safe.  Grown only outside graph capture (warm-up run does it)."""
-
-    _bufs = {}
-
-    @classmethod
-    def get(cls, nbytes: int, device) -> torch.Tensor:
-        key = (device.index, stream(device.index))  # per stream: concurrent streams must not share scratch
-        buf = cls._bufs.get(key)
-        if buf is None or buf.numel() < nbytes:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("medfusion_amd: workspace growth during graph capture; run one eager warm-up first")
-            buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
-            cls._bufs[key] = buf
-            global _growths
-            _growths += 1
-        return buf
-
-
-class SyncWords:
-    """Zero-initialised 32-bit counters the in-launch split-K reduction of mf_conv2d_f16x2 meets through (every launch leaves them zero).
-    One array per (device, stream), like the workspace; grown (re-zeroed) outside graph capture only."""
-
-    _bufs = {}
+class _StreamBuf:
+    """A grow-only buffer per (device, stream), owned by torch (the library never allocates): launches on one stream are serialised, so sharing is
+    safe; concurrent streams must not share scratch.  Grown -- zeroed again where `zeroed` -- outside graph capture only (the eager warm-up run does it);
+    every growth is counted (scratch_growth_count).  Subclasses: what the buffer is called in the error, its smallest size, its element type."""
+    what, floor, dtype, zeroed = "", 0, torch.uint8, False
 
     @classmethod
-    def get(cls, words: int, device) -> torch.Tensor:
+    def get(cls, size: int, device) -> torch.Tensor:
         key = (device.index, stream(device.index))
         buf = cls._bufs.get(key)
-        if buf is None or buf.numel() < words:
+        if buf is None or buf.numel() < size:
             if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("medfusion_amd: sync-counter growth during graph capture; run one eager warm-up first")
-            buf = torch.zeros(max(words, 1 << 14), dtype=torch.int32, device=device)
-            cls._bufs[key] = buf
+                raise RuntimeError(f"medfusion_amd: {cls.what} growth during graph capture; run one eager warm-up first")
+            buf = cls._bufs[key] = (torch.zeros if cls.zeroed else torch.empty)(max(size, cls.floor), dtype=cls.dtype, device=device)
             global _growths
             _growths += 1
         return buf
+
+
+class Workspace(_StreamBuf):
+    """Scratch bytes: split-K slabs and hand-off regions, the Winograd GEMM's output in the transform domain."""
+    _bufs, what, floor = {}, "workspace", 1 << 20
+
+
+class SyncWords(_StreamBuf):
+    """Zero-initialised 32-bit counters the in-launch split-K reduction of mf_conv2d_f16x2 meets through (every launch leaves them zero)."""
+    _bufs, what, floor, dtype, zeroed = {}, "sync-counter", 1 << 14, torch.int32, True
 
     @classmethod
     def reset(cls, device) -> None:
@@ -96,14 +85,14 @@ class SyncWords:
             buf.zero_()
 
 
-class Rendezvous:
+class Rendezvous(_StreamBuf):
     """Counters of the convolutions that apply their GroupNorm inside their own launch (mf_conv2d_f16x2_gn_apply): word 0 is the ERROR FLAG
     (a wait that did not complete: another process's waiting workgroups filled the device), the [N][2] arrive / depart counters start at
     word 4.  One array per (device, stream); zero before the first launch, left zero by every launch.  `failed(device)` reads the flags of
     the device (a host sync): DiffusionPipeline checks once per sampling loop, VAE once per pass, and on a hit zero everything, switch the
     fused form off for the process (`disabled`) and re-run on the two-launch form."""
 
-    _bufs = {}
+    _bufs, what, floor, dtype, zeroed = {}, "rendezvous-counter", 1 << 12, torch.int32, True
     # OPT-IN (MEDFUSION_FUSED_APPLY=1): built, bit-identical to the two-launch form, and measured NOT faster -- same-process A/B on cfg2,
     # profiles/r04_fused_gn_apply_ab.txt: -0.2 % (fused at 32 x 32 only) ... -2.2 % (everywhere); the tail costs what the boundary + the
     # apply launch cost (profiles/r04_conv_timeline_fused.txt).  So the default is the two-launch form, which also never waits in a kernel.
@@ -113,15 +102,7 @@ class Rendezvous:
 
     @classmethod
     def get(cls, words: int, device) -> torch.Tensor:
-        key = (device.index, stream(device.index))
-        buf = cls._bufs.get(key)
-        if buf is None or buf.numel() < words + 4:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("medfusion_amd: rendezvous-counter growth during graph capture; run one eager warm-up first")
-            buf = torch.zeros(max(words + 4, 1 << 12), dtype=torch.int32, device=device)
-            cls._bufs[key] = buf
-            global _growths
-            _growths += 1
+        buf = super().get(words + 4, device)
         cls.used[device.index] = True
         cls.launches += 1
         return buf
@@ -278,20 +259,43 @@ def _need_f32(*ts):
                                "its fp32 form was never written -- only the fp16-pair convolution and the apply pass (as a residual) can read it")
 
 
+# every mirror attribute a producer may attach (_attach) and a writer must drop (drop_split).  Not mirrors, and left alone by drop_split: `_mf_ver` (the
+# stamp; _fresh clears it), `_mf_wino_site` / `_mf_wino_site_f32` (where to report a wanted transform: they describe the producer, not the values);
+# `_mf_pairs_only` is a flag of the storage that drop_split clears by its own rule.  A new mirror kind goes HERE (tests/test_host_logic_cpu.py checks)
+MIRRORS = ("_mf_split", "_mf_bound", "_mf_slots", "_mf_wino", "_mf_wino_bound", "_mf_wino_f32")
+
+
 def drop_split(t: Optional[torch.Tensor]) -> None:
     if t is not None:
-        if getattr(t, "_mf_pairs_only", False):
-            t._mf_pairs_only = False   # (an fp32 writer is about to fill the storage)
-        if getattr(t, "_mf_split", None) is not None:
-            t._mf_split = None
-        if getattr(t, "_mf_bound", None) is not None:
-            t._mf_bound = None
-        if getattr(t, "_mf_slots", None) is not None:
-            t._mf_slots = None
-        if getattr(t, "_mf_wino", None) is not None:
-            t._mf_wino = t._mf_wino_bound = None
-        if getattr(t, "_mf_wino_f32", None) is not None:
-            t._mf_wino_f32 = None
+        attrs = t.__dict__   # (the tensor's Python attributes: most tensors written into carry none, and this runs per launch)
+        if attrs:
+            if attrs.get("_mf_pairs_only"):
+                attrs["_mf_pairs_only"] = False   # (an fp32 writer is about to fill the storage)
+            for name in MIRRORS:
+                if attrs.get(name) is not None:
+                    attrs[name] = None
+
+
+def _attach(t: torch.Tensor, site: Optional[str] = None, split=None, bound=None, slots=None, wino=None, wino_f32=None, pairs_only: bool = False) -> torch.Tensor:
+    """Attach the mirrors a producer has just made to its tensor `t` -- split (fp16 pairs) / bound / slots (slot maxima, a bound still to be reduced) / wino
+    = (V as pairs, its bounds) / wino_f32 (V in fp32); None: not produced -- and stamp t's version next to them.  site: the producer scaled the pairs by
+    a bound of its own: the text under which the bound-slack audit records it (None: nothing to audit).  pairs_only: t's fp32 storage was never written"""
+    if split is not None:
+        t._mf_split = split
+    if bound is not None:
+        t._mf_bound = bound
+    if slots is not None:
+        t._mf_slots = slots
+    if wino is not None:
+        t._mf_wino, t._mf_wino_bound = wino
+    if wino_f32 is not None:
+        t._mf_wino_f32 = wino_f32
+    t._mf_ver = t._version   # (_stamp)
+    if AUDIT and site is not None:
+        _audit(t, site)
+    if pairs_only:
+        t._mf_pairs_only = True
+    return t
 
 
 def maxabs_rows(x: torch.Tensor) -> torch.Tensor:
@@ -318,8 +322,7 @@ def bound_of(x: torch.Tensor) -> torch.Tensor:
             L.check(L.load().mf_bound_finalize_f32(sl.data_ptr(), b.data_ptr(), sl.shape[0], sl.shape[1], stream()), "mf_bound_finalize_f32")
         else:
             b = maxabs_rows(x)
-        x._mf_bound = b
-        _stamp(x)
+        _attach(x, bound=b)
     return b
 
 
@@ -341,6 +344,7 @@ def split_f16x2(x: torch.Tensor, bound: Optional[torch.Tensor] = None) -> torch.
 def split_of(x: torch.Tensor) -> torch.Tensor:
     s = _fresh(x, "_mf_split")
     if s is None:
+        b = None
         if _fresh(x, "_mf_bound") is None and x.dim() >= 2 and x.shape[-1] % 8 == 0 and x.is_contiguous() and x.dtype == torch.float32:
             # no bound yet: the slot maxima the producing convolution left -- or those of a measuring pass -- are reduced inside the split
             # itself (mf_split_f16x2_slots: no bound-finalize launch), which publishes the bound as well
@@ -354,13 +358,68 @@ def split_of(x: torch.Tensor) -> torch.Tensor:
             s = torch.empty(x.shape, dtype=torch.int32, device=x.device)
             b = torch.empty((n,), dtype=torch.float32, device=x.device)
             L.check(lib.mf_split_f16x2_slots(x.data_ptr(), s.data_ptr(), sl.data_ptr(), sl.shape[1], b.data_ptr(), n, per, stream()), "mf_split_f16x2_slots")
-            x._mf_bound = b
         else:
             s = split_f16x2(x, bound_of(x))
-        x._mf_split = s
-        _stamp(x)
-        _audit(x, "split of a measured tensor")
+        _attach(x, "split of a measured tensor", split=s, bound=b)
     return s
+
+
+def _pair_operands(x1: torch.Tensor, x2: Optional[torch.Tensor]):
+    """(pairs of x1, bound of x1, pairs of x2, bound of x2) -- the operands of an fp16-pair convolution of x1 | x2, made on demand; x2 may be None"""
+    if x2 is None:
+        return split_of(x1), bound_of(x1), None, None
+    return split_of(x1), bound_of(x1), split_of(x2), bound_of(x2)
+
+
+def _tail_operands(residual: Optional[torch.Tensor], emb: Optional[torch.Tensor], bounds: bool = True, slots: bool = True, pairs: bool = True):
+    """What a GroupNorm tail / apply pass reads besides its input: (fp32 pointer of the residual, its pairs, its bound, its slot maxima, the bound of the
+    embedding rows).  A residual that exists as pairs only is read from them (pairs=False: this pass cannot -- _need_f32 raises); one whose bound is
+    still the slot maxima of the convolution that measured it hands those over (slots=False: this pass cannot reduce them -- bound_of does);
+    bounds=False: the pass emits no pair mirror and needs no bound.  Call BEFORE the output may alias the residual: the bounds describe what is READ."""
+    res_pairs = rb = rslots = eb = None
+    if pairs_only(residual):
+        if not pairs:
+            _need_f32(residual)
+        res_pairs, rb = residual._mf_split, bound_of(residual)
+    elif residual is not None and bounds:
+        if slots and _fresh(residual, "_mf_bound") is None and _fresh(residual, "_mf_slots") is not None:
+            rslots = residual._mf_slots
+        else:
+            rb = bound_of(residual)
+    if emb is not None and bounds:
+        eb = _fresh(emb, "_mf_bound")
+        if eb is None:
+            eb = maxabs_rows(emb.contiguous())
+    return (None if res_pairs is not None else _ptr(residual)), res_pairs, rb, rslots, eb
+
+
+def _pair_outputs(shape, dev, wino: Optional[bool] = None):
+    """uninitialised (fp32 NHWC output, its pair mirror, its bound [N]) and -- wino given -- (V of the output for the next Winograd convolution, its bounds
+    [16 N]), both None unless wanted"""
+    n, h, w, c = shape
+    out = torch.empty(shape, dtype=torch.float32, device=dev)
+    outs = torch.empty(shape, dtype=torch.int32, device=dev)
+    ob = torch.empty((n,), dtype=torch.float32, device=dev)
+    if wino is None:
+        return out, outs, ob
+    ov = torch.empty((16, n, (h // 2) * (w // 2), c), dtype=torch.int32, device=dev) if wino else None
+    ovb = torch.empty((16 * n,), dtype=torch.float32, device=dev) if wino else None
+    return out, outs, ob, ov, ovb
+
+
+def _scratch(dev, need: int, words: int, need_g: Optional[int] = None, words_g: int = 0, wino: bool = False):
+    """Device pointers to the scratch of one launch: (workspace of `need` bytes, `words` sync counters) and -- need_g given: a guest convolution shares the
+    launch -- (the guest's workspace, the guest's counters): its region lies behind the host's at the next multiple of 256 bytes, its counters behind the
+    host's.  None where a convolution needs none.  wino: the host is a Winograd component GEMM, whose workspace is never empty (its output in the
+    transform domain) and which is handed the counter array whenever the launch has one"""
+    off = (need + 255) & ~255
+    total, wtotal = (need, words) if need_g is None else (off + need_g, words + words_g)
+    ws = Workspace.get(total, dev).data_ptr() if (wino or total) else None
+    sync = SyncWords.get(wtotal, dev).data_ptr() if wtotal else None
+    host = (ws if (wino or need) else None, sync if (wino or words) else None)
+    if need_g is None:
+        return host
+    return (*host, ws + off if need_g else None, sync + 4 * words if words_g else None)
 
 
 def split_weight_f16x2(w_packed: torch.Tensor):
@@ -409,8 +468,7 @@ def conv2d_f16x2(x1: torch.Tensor, w_split, bias: Optional[torch.Tensor], d: L.M
     wh, wmax = w_split
     _gpu(x1, x2, wh, bias)
     lib = L.load()
-    x1s, b1 = split_of(x1), bound_of(x1)
-    x2s, b2 = (split_of(x2), bound_of(x2)) if x2 is not None else (None, None)
+    x1s, b1, x2s, b2 = _pair_operands(x1, x2)
     ho, wo = conv_out_hw(d)
     if out is None:
         out = torch.empty((d.N, ho, wo, d.Cout), dtype=torch.float32, device=x1.device)
@@ -424,14 +482,12 @@ def conv2d_f16x2(x1: torch.Tensor, w_split, bias: Optional[torch.Tensor], d: L.M
         slots = 0
     yb = torch.empty((d.N, slots), dtype=torch.float32, device=x1.device) if slots else None
     partial = torch.empty((d.N, gn_parts, gn_groups, 2), dtype=torch.float64, device=x1.device) if gn_groups else None
-    ws = Workspace.get(need, x1.device) if need else None
-    sync = SyncWords.get(words, x1.device) if words else None
-    rc = lib.mf_conv2d_f16x2(x1s.data_ptr(), _ptr(x2s), wh.data_ptr(), _ptr(bias), out.data_ptr(), b1.data_ptr(), _ptr(b2), wmax, _ptr(yb), _ptr(ws), need,
-                             _ptr(sync), _ptr(partial), gn_groups, C.byref(d), stream())
+    ws, sync = _scratch(x1.device, need, words)
+    rc = lib.mf_conv2d_f16x2(x1s.data_ptr(), _ptr(x2s), wh.data_ptr(), _ptr(bias), out.data_ptr(), b1.data_ptr(), _ptr(b2), wmax, _ptr(yb), ws, need,
+                             sync, _ptr(partial), gn_groups, C.byref(d), stream())
     L.check(rc, "mf_conv2d_f16x2")
     if slots:   # per-(tile, wave) maxima: reduced to the bound of each sample by the first consumer that asks (bound_of), or inside the
-        out._mf_slots = yb   # GroupNorm-apply pass that takes this tensor as its residual (without slots a consumer measures on demand)
-        _stamp(out)
+        _attach(out, slots=yb)   # GroupNorm-apply pass that takes this tensor as its residual (without slots a consumer measures on demand)
     return (out, partial) if gn_groups else out
 
 
@@ -446,33 +502,34 @@ def conv2d_f16x2_group(x1: torch.Tensor, x2: Optional[torch.Tensor], a, b):
     dict(w_split, bias, d, pinned) -> y with its bound slots attached.  Bit for bit what conv2d_f16x2(.., gn_groups=..) and
     conv2d_f16x2(.., measure_out=True) return."""
     _gpu(x1, x2, a["w_split"][0], b["w_split"][0], a["bias"], b["bias"])
-    lib = L.load()
     dev = x1.device
-    x1s, b1 = split_of(x1), bound_of(x1)
-    x2s, b2 = (split_of(x2), bound_of(x2)) if x2 is not None else (None, None)
-    da, db = a["d"], b["d"]
-    need_a, _, words_a = a["pinned"]
-    need_b, slots_b, words_b = b["pinned"]
-    off_b = (need_a + 255) & ~255                      # b's hand-off region behind a's, its counters behind a's
-    ws = Workspace.get(off_b + need_b, dev) if (need_a or need_b) else None
-    sync = SyncWords.get(words_a + words_b, dev) if (words_a or words_b) else None
-    hoa, woa = conv_out_hw(da)
-    hob, wob = conv_out_hw(db)
-    ya = torch.empty((da.N, hoa, woa, da.Cout), dtype=torch.float32, device=dev)
-    yb = torch.empty((db.N, hob, wob, db.Cout), dtype=torch.float32, device=dev)
+    ops = _pair_operands(x1, x2)
+    (need_a, _, words_a), (need_b, _, words_b) = a["pinned"], b["pinned"]
+    ws_a, sync_a, ws_b, sync_b = _scratch(dev, need_a, words_a, need_b, words_b)   # b's hand-off region behind a's, its counters behind a's
     G, parts = a["gn_groups"], a["gn_parts"]
-    partial = torch.empty((da.N, parts, G, 2), dtype=torch.float64, device=dev)
-    slots = torch.empty((db.N, slots_b), dtype=torch.float32, device=dev) if slots_b else None
-    (wa, wmax_a), (wb, wmax_b) = a["w_split"], b["w_split"]
-    ca = L.MfConvF16x2Call(x1s.data_ptr(), _ptr(x2s), wa.data_ptr(), _ptr(a["bias"]), ya.data_ptr(), b1.data_ptr(), _ptr(b2), wmax_a, None,
-                           ws.data_ptr() if need_a else None, need_a, sync.data_ptr() if words_a else None, partial.data_ptr(), G, C.pointer(da))
-    cb = L.MfConvF16x2Call(x1s.data_ptr(), _ptr(x2s), wb.data_ptr(), _ptr(b["bias"]), yb.data_ptr(), b1.data_ptr(), _ptr(b2), wmax_b, _ptr(slots),
-                           ws.data_ptr() + off_b if need_b else None, need_b, sync.data_ptr() + 4 * words_a if words_b else None, None, 0, C.pointer(db))
-    L.check(lib.mf_conv2d_f16x2_group(C.byref(ca), C.byref(cb), stream()), "mf_conv2d_f16x2_group")
-    if slots_b:
-        yb._mf_slots = slots
-        _stamp(yb)
+    partial = torch.empty((a["d"].N, parts, G, 2), dtype=torch.float64, device=dev)
+    ca, ya = _conv_call(ops, a, ws_a, sync_a, dev, partial=partial, G=G)
+    cb, yb = _conv_call(ops, b, ws_b, sync_b, dev, measured=True)
+    L.check(L.load().mf_conv2d_f16x2_group(C.byref(ca), C.byref(cb), stream()), "mf_conv2d_f16x2_group")
     return (ya, partial), yb
+
+
+def _conv_call(ops, c, ws, sync, dev, partial=None, G: int = 0, measured: bool = False):
+    """One member of a launch that several convolutions share, as (its MfConvF16x2Call record, the output the record points at).  ops = _pair_operands
+    of the common input, c = dict(w_split, bias, d, pinned, ...) as conv2d_f16x2_group documents, ws / sync = its pointers from _scratch.
+    measured: the output carries the slot maxima of its bound (the plan permitting: pinned[1] slots), like conv2d_f16x2(measure_out=True)"""
+    x1s, b1, x2s, b2 = ops
+    wh, wmax = c["w_split"]
+    d = c["d"]
+    need, nslots, _ = c["pinned"]
+    ho, wo = conv_out_hw(d)
+    y = torch.empty((d.N, ho, wo, d.Cout), dtype=torch.float32, device=dev)
+    slots = torch.empty((d.N, nslots), dtype=torch.float32, device=dev) if measured and nslots else None
+    call = L.MfConvF16x2Call(x1s.data_ptr(), _ptr(x2s), wh.data_ptr(), _ptr(c["bias"]), y.data_ptr(), b1.data_ptr(), _ptr(b2), wmax, _ptr(slots),
+                             ws, need, sync, _ptr(partial), G, C.pointer(d))
+    if slots is not None:
+        _attach(y, slots=slots)
+    return call, y
 
 
 def pack_nchw_pairs(x_nchw: torch.Tensor, cp: int = 32) -> torch.Tensor:
@@ -481,14 +538,9 @@ def pack_nchw_pairs(x_nchw: torch.Tensor, cp: int = 32) -> torch.Tensor:
     _gpu(x_nchw)
     x = x_nchw.contiguous()
     n, c, h, w = x.shape
-    out = torch.empty((n, h, w, cp), dtype=torch.float32, device=x.device)     # (storage never written: pairs only)
-    outs = torch.empty((n, h, w, cp), dtype=torch.int32, device=x.device)
-    ob = torch.empty((n,), dtype=torch.float32, device=x.device)
+    out, outs, ob = _pair_outputs((n, h, w, cp), x.device)     # (out's storage is never written: pairs only)
     L.check(L.load().mf_pack_nchw_pairs_f32(x.data_ptr(), outs.data_ptr(), ob.data_ptr(), n, c, h * w, cp, stream()), "mf_pack_nchw_pairs_f32")
-    out._mf_split, out._mf_bound, out._mf_pairs_only = outs, ob, True
-    _stamp(out)
-    _audit(out, "pack_nchw_pairs (measured)")
-    return out
+    return _attach(out, "pack_nchw_pairs (measured)", split=outs, bound=ob, pairs_only=True)
 
 
 def conv_pairs_out_ok(d: L.MfConvDesc) -> bool:
@@ -503,24 +555,16 @@ def conv2d_f16x2_pairs_out(x1: torch.Tensor, w_split, bias: Optional[torch.Tenso
     wh, wmax = w_split
     _gpu(x1, x2, wh, bias)
     lib = L.load()
-    x1s, b1 = split_of(x1), bound_of(x1)
-    x2s, b2 = (split_of(x2), bound_of(x2)) if x2 is not None else (None, None)
-    ho, wo = conv_out_hw(d)
-    out = torch.empty((d.N, ho, wo, d.Cout), dtype=torch.float32, device=x1.device)
-    outs = torch.empty((d.N, ho, wo, d.Cout), dtype=torch.int32, device=x1.device)
-    ob = torch.empty((d.N,), dtype=torch.float32, device=x1.device)
+    x1s, b1, x2s, b2 = _pair_operands(x1, x2)
+    out, outs, ob = _pair_outputs((d.N, *conv_out_hw(d), d.Cout), x1.device)
     if pinned is None:
         pinned = (lib.mf_conv2d_workspace_bytes(C.byref(d)), 0, lib.mf_conv2d_f16x2_sync_words(C.byref(d)))
     need, _, words = pinned
-    ws = Workspace.get(need, x1.device) if need else None
-    sync = SyncWords.get(words, x1.device) if words else None
+    ws, sync = _scratch(x1.device, need, words)
     rc = lib.mf_conv2d_f16x2_pairs_out(x1s.data_ptr(), _ptr(x2s), wh.data_ptr(), _ptr(bias), out.data_ptr(), outs.data_ptr(), ob.data_ptr(), b1.data_ptr(), _ptr(b2),
-                                       wmax, float(l1[0]), float(l1[1]), float(bias_max), _ptr(ws), need, _ptr(sync), C.byref(d), stream())
+                                       wmax, float(l1[0]), float(l1[1]), float(bias_max), ws, need, sync, C.byref(d), stream())
     L.check(rc, "mf_conv2d_f16x2_pairs_out")
-    out._mf_split, out._mf_bound = outs, ob
-    _stamp(out)
-    _audit(out, "conv pairs_out (derived: bound(x) L1(w) + max|bias|)")
-    return out
+    return _attach(out, "conv pairs_out (derived: bound(x) L1(w) + max|bias|)", split=outs, bound=ob)
 
 
 # ----------------------------------------------------------------------------- Winograd F(2x2, 3x3) form of the 3x3 stride-1 convolutions
@@ -566,9 +610,13 @@ def wino_input(x: torch.Tensor):
         v = torch.empty((16, n, (h // 2) * (w // 2), c), dtype=torch.int32, device=x.device)
         vb = torch.empty((16 * n,), dtype=torch.float32, device=x.device)
         L.check(L.load().mf_wino_input_f16x2(xs.data_ptr(), xb.data_ptr(), v.data_ptr(), vb.data_ptr(), n, h, w, c, stream()), "mf_wino_input_f16x2")
-        x._mf_wino, x._mf_wino_bound = v, vb
-        _stamp(x)
+        _attach(x, wino=(v, vb))
     return v, x._mf_wino_bound
+
+
+def _wino_operands(x1: torch.Tensor, x2: Optional[torch.Tensor]):
+    """(V of x1, its bounds, V of x2, its bounds): the operands of a Winograd convolution of x1 | x2 (wino_input); x2 may be None"""
+    return (*wino_input(x1), *(wino_input(x2) if x2 is not None else (None, None)))
 
 
 def pin_wino_plan(d: L.MfConvDesc):
@@ -584,16 +632,14 @@ def conv2d_wino_f16x2(x1: torch.Tensor, u_split, bias: Optional[torch.Tensor], d
     uh, umax = u_split
     _gpu(x1, x2, uh, bias)
     lib = L.load()
-    v1, b1 = wino_input(x1)
-    v2, b2 = wino_input(x2) if x2 is not None else (None, None)
+    v1, b1, v2, b2 = _wino_operands(x1, x2)
     dev = x1.device
     out = torch.empty((d.N, d.Hin, d.Win, d.Cout), dtype=torch.float32, device=dev)
     partial = torch.empty((d.N, gn_parts, gn_groups, 2), dtype=torch.float64, device=dev) if gn_groups else None
     need, words = pinned if pinned is not None else pin_wino_plan(d)
-    ws = Workspace.get(need, dev)
-    sync = SyncWords.get(words, dev) if words else None
-    rc = lib.mf_conv2d_wino_f16x2(v1.data_ptr(), _ptr(v2), uh.data_ptr(), _ptr(bias), out.data_ptr(), b1.data_ptr(), _ptr(b2), umax, ws.data_ptr(), need,
-                                  _ptr(sync), _ptr(partial), gn_groups, C.byref(d), stream())
+    ws, sync = _scratch(dev, need, words, wino=True)
+    rc = lib.mf_conv2d_wino_f16x2(v1.data_ptr(), _ptr(v2), uh.data_ptr(), _ptr(bias), out.data_ptr(), b1.data_ptr(), _ptr(b2), umax, ws, need,
+                                  sync, _ptr(partial), gn_groups, C.byref(d), stream())
     L.check(rc, "mf_conv2d_wino_f16x2")
     return (out, partial) if gn_groups else out
 
@@ -619,65 +665,35 @@ def conv2d_wino_gn_apply(x1: torch.Tensor, u_split, bias: Optional[torch.Tensor]
     uh, umax = u_split
     _gpu(x1, x2, uh, bias, gamma, beta, residual, emb)
     lib = L.load()
-    v1, b1 = wino_input(x1)
-    v2, b2 = wino_input(x2) if x2 is not None else (None, None)
-    n, h, w, c = d.N, d.Hin, d.Win, d.Cout
+    v1, b1, v2, b2 = _wino_operands(x1, x2)
     dev = x1.device
     need, words = pinned if pinned is not None else pin_wino_plan(d)
     gcall = None
     if guest is not None:
         if residual is not None:
             raise RuntimeError("conv2d_wino_gn_apply: the guest's output is the residual")
-        dg = guest["d"]
-        need_g, slots_g, words_g = guest["pinned"]
-        off_g = (need + 255) & ~255                      # the guest's hand-off region behind the GEMM's workspace, its counters behind the GEMM's
-        ws = Workspace.get(off_g + need_g, dev)
-        sync = SyncWords.get(words + words_g, dev) if (words or words_g) else None
-        x1s, xb1 = split_of(x1), bound_of(x1)
-        x2s, xb2 = (split_of(x2), bound_of(x2)) if x2 is not None else (None, None)
-        hog, wog = conv_out_hw(dg)
-        residual = torch.empty((dg.N, hog, wog, dg.Cout), dtype=torch.float32, device=dev)
-        gslots = torch.empty((dg.N, slots_g), dtype=torch.float32, device=dev) if slots_g else None
-        wg, wgmax = guest["w_split"]
-        gcall = L.MfConvF16x2Call(x1s.data_ptr(), _ptr(x2s), wg.data_ptr(), _ptr(guest["bias"]), residual.data_ptr(), xb1.data_ptr(), _ptr(xb2), wgmax, _ptr(gslots),
-                                  ws.data_ptr() + off_g if need_g else None, need_g, sync.data_ptr() + 4 * words if words_g else None, None, 0, C.pointer(dg))
-        if slots_g:
-            residual._mf_slots = gslots
-            _stamp(residual)
+        need_g, _, words_g = guest["pinned"]
+        ws, sync, ws_g, sync_g = _scratch(dev, need, words, need_g, words_g, wino=True)   # the guest's hand-off region behind the GEMM's workspace, its counters behind the GEMM's
+        gcall, residual = _conv_call(_pair_operands(x1, x2), guest, ws_g, sync_g, dev, measured=True)
     else:
-        ws = Workspace.get(need, dev)
-        sync = SyncWords.get(words, dev) if words else None
-    res_pairs = rb = rslots = eb = None
-    if residual is not None:
-        if pairs_only(residual):
-            res_pairs, rb = residual._mf_split, residual._mf_bound
-        elif _fresh(residual, "_mf_bound") is None and _fresh(residual, "_mf_slots") is not None:
-            rslots = residual._mf_slots
-        else:
-            rb = bound_of(residual)
-    if emb is not None:
-        eb = _fresh(emb, "_mf_bound")
-        if eb is None:
-            eb = maxabs_rows(emb.contiguous())
-    out = torch.empty((n, h, w, c), dtype=torch.float32, device=dev)
-    outs = torch.empty((n, h, w, c), dtype=torch.int32, device=dev)
-    ob = torch.empty((n,), dtype=torch.float32, device=dev)
-    ov = torch.empty((16, n, (h // 2) * (w // 2), c), dtype=torch.int32, device=dev) if want_wino else None
-    ovb = torch.empty((16 * n,), dtype=torch.float32, device=dev) if want_wino else None
-    t = L.MfWinoTail(_ptr(gamma), _ptr(beta), None if res_pairs is not None else _ptr(residual), _ptr(res_pairs), _ptr(rb), _ptr(rslots), _ptr(emb), _ptr(eb),
-                     out.data_ptr() if out_fp32 else None, outs.data_ptr(), ob.data_ptr(), _ptr(ov), _ptr(ovb), int(emb_stride),
-                     0 if rslots is None else rslots.shape[1], int(act), float(bconst), float(eps))
-    rc = lib.mf_conv2d_wino_gn_apply_f16x2(v1.data_ptr(), _ptr(v2), uh.data_ptr(), _ptr(bias), b1.data_ptr(), _ptr(b2), umax, ws.data_ptr(), need, _ptr(sync), G,
+        ws, sync = _scratch(dev, need, words, wino=True)
+    tail_ops = _tail_operands(residual, emb)
+    out, outs, ob, ov, ovb = _pair_outputs((d.N, d.Hin, d.Win, d.Cout), dev, wino=want_wino)
+    t = _tail_struct(L.MfWinoTail, gamma, beta, tail_ops, emb, emb_stride, out if out_fp32 else None, outs, ob, _ptr(ov), _ptr(ovb), act, bconst, eps)
+    rc = lib.mf_conv2d_wino_gn_apply_f16x2(v1.data_ptr(), _ptr(v2), uh.data_ptr(), _ptr(bias), b1.data_ptr(), _ptr(b2), umax, ws, need, sync, G,
                                            C.byref(t), None if gcall is None else C.byref(gcall), C.byref(d), stream())
     L.check(rc, "mf_conv2d_wino_gn_apply_f16x2")
-    out._mf_split, out._mf_bound = outs, ob
-    if want_wino:
-        out._mf_wino, out._mf_wino_bound = ov, ovb
-    _stamp(out)
-    _audit(out, "Winograd tail (derived: bconst + residual + embedding)")
-    if not out_fp32:
-        out._mf_pairs_only = True
-    return out
+    return _attach(out, "Winograd tail (derived: bconst + residual + embedding)", split=outs, bound=ob, wino=(ov, ovb) if want_wino else None,
+                   pairs_only=not out_fp32)
+
+
+def _tail_struct(cls, gamma, beta, tail_ops, emb, emb_stride, out, outs, ob, p11, p12, act, bconst, eps):
+    """MfGnFuse / MfWinoTail (`cls`): what the GroupNorm tail of a convolution reads and writes.  tail_ops = _tail_operands(residual, emb); out None: the
+    fp32 form is not written (pairs only).  The two structs differ in their pointer fields 11 and 12 alone: (rendezvous counters, error flag) of the
+    convolution that waits for its sample inside its launch, (V of the output, its bounds) of the Winograd tail"""
+    rp, res_pairs, rb, rslots, eb = tail_ops
+    return cls(_ptr(gamma), _ptr(beta), rp, _ptr(res_pairs), _ptr(rb), _ptr(rslots), _ptr(emb), _ptr(eb), _ptr(out), outs.data_ptr(), ob.data_ptr(), p11, p12,
+               int(emb_stride), 0 if rslots is None else rslots.shape[1], int(act), float(bconst), float(eps))
 
 
 # ----------------------------------------------------------------------------- the Winograd form on the EXACT arithmetics (round 6, ABI 250)
@@ -699,8 +715,7 @@ def wino_input_f32(x: torch.Tensor) -> torch.Tensor:
         n, h, w, c = x.shape
         v = torch.empty((16, n, (h // 2) * (w // 2), c), dtype=torch.float32, device=x.device)
         L.check(L.load().mf_wino_input_f32(x.data_ptr(), v.data_ptr(), n, h, w, c, stream()), "mf_wino_input_f32")
-        x._mf_wino_f32 = v
-        _stamp(x)
+        _attach(x, wino_f32=v)
     return v
 
 
@@ -726,10 +741,7 @@ def conv2d_wino_gn_apply_f32(x1: torch.Tensor, u_packed: torch.Tensor, bias: Opt
     ov = torch.empty((16, n, t, co), dtype=torch.float32, device=x1.device) if want_wino else None
     L.check(lib.mf_wino_tail_f32(m.data_ptr(), _ptr(bias), _ptr(gamma), _ptr(beta), _ptr(residual), _ptr(emb), emb_stride, out.data_ptr(), _ptr(ov),
                                  n, h, w, co, G, act, eps, stream()), "mf_wino_tail_f32")
-    if want_wino:
-        out._mf_wino_f32 = ov
-        _stamp(out)
-    return out
+    return _attach(out, wino_f32=ov) if want_wino else out
 
 
 def conv_fuse_words(d: L.MfConvDesc, G: int) -> int:
@@ -747,45 +759,21 @@ def conv2d_f16x2_gn_apply(x1: torch.Tensor, w_split, bias: Optional[torch.Tensor
     wh, wmax = w_split
     _gpu(x1, x2, wh, bias, gamma, beta, residual, emb)
     lib = L.load()
-    x1s, b1 = split_of(x1), bound_of(x1)
-    x2s, b2 = (split_of(x2), bound_of(x2)) if x2 is not None else (None, None)
-    ho, wo = conv_out_hw(d)
-    n, c = d.N, d.Cout
+    x1s, b1, x2s, b2 = _pair_operands(x1, x2)
     dev = x1.device
-    res_pairs = rb = rslots = eb = None
-    if residual is not None:
-        if pairs_only(residual):
-            res_pairs, rb = residual._mf_split, residual._mf_bound
-        elif _fresh(residual, "_mf_bound") is None and _fresh(residual, "_mf_slots") is not None:
-            rslots = residual._mf_slots
-        else:
-            rb = bound_of(residual)
-    if emb is not None:
-        eb = _fresh(emb, "_mf_bound")
-        if eb is None:
-            eb = maxabs_rows(emb.contiguous())
-    out = torch.empty((n, ho, wo, c), dtype=torch.float32, device=dev)
-    outs = torch.empty((n, ho, wo, c), dtype=torch.int32, device=dev)
-    ob = torch.empty((n,), dtype=torch.float32, device=dev)
-    partial = torch.empty((n, parts, G, 2), dtype=torch.float64, device=dev)
+    tail_ops = _tail_operands(residual, emb)
+    out, outs, ob = _pair_outputs((d.N, *conv_out_hw(d), d.Cout), dev)
+    partial = torch.empty((d.N, parts, G, 2), dtype=torch.float64, device=dev)
     if pinned is None:
         pinned = (lib.mf_conv2d_workspace_bytes(C.byref(d)), 0, lib.mf_conv2d_f16x2_sync_words(C.byref(d)))
     need, _, swords = pinned
-    ws = Workspace.get(need, dev) if need else None
-    sync = SyncWords.get(swords, dev) if swords else None
+    ws, sync = _scratch(dev, need, swords)
     rv = Rendezvous.get(words, dev)
-    f = L.MfGnFuse(_ptr(gamma), _ptr(beta), None if res_pairs is not None else _ptr(residual), _ptr(res_pairs), _ptr(rb), _ptr(rslots), _ptr(emb), _ptr(eb),
-                   out.data_ptr() if out_fp32 else None, outs.data_ptr(), ob.data_ptr(), rv.data_ptr() + 16, rv.data_ptr(), int(emb_stride),
-                   0 if rslots is None else rslots.shape[1], int(act), float(bconst), float(eps))
-    rc = lib.mf_conv2d_f16x2_gn_apply(x1s.data_ptr(), _ptr(x2s), wh.data_ptr(), _ptr(bias), b1.data_ptr(), _ptr(b2), wmax, _ptr(ws), need, _ptr(sync),
+    f = _tail_struct(L.MfGnFuse, gamma, beta, tail_ops, emb, emb_stride, out if out_fp32 else None, outs, ob, rv.data_ptr() + 16, rv.data_ptr(), act, bconst, eps)
+    rc = lib.mf_conv2d_f16x2_gn_apply(x1s.data_ptr(), _ptr(x2s), wh.data_ptr(), _ptr(bias), b1.data_ptr(), _ptr(b2), wmax, ws, need, sync,
                                       partial.data_ptr(), G, C.byref(f), C.byref(d), stream())
     L.check(rc, "mf_conv2d_f16x2_gn_apply")
-    out._mf_split, out._mf_bound = outs, ob
-    _stamp(out)
-    _audit(out, "conv + GroupNorm tail in one launch (derived)")
-    if not out_fp32:
-        out._mf_pairs_only = True
-    return out
+    return _attach(out, "conv + GroupNorm tail in one launch (derived)", split=outs, bound=ob, pairs_only=not out_fp32)
 
 
 def make_conv3d_desc(N, D, H, W, C1, C2, Cout, k, stride=(1, 1, 1), pad=(0, 0, 0), upsample=(0, 0, 0), tile_hint=0, splitk_hint=0,
@@ -837,16 +825,15 @@ def conv3d_f16x2(x1: torch.Tensor, w_split, bias: Optional[torch.Tensor], d: L.M
     lib = L.load()
     if not lib.mf_conv3d_ok(C.byref(d)):
         raise RuntimeError("conv3d_f16x2: descriptor not supported (mf_conv3d_ok)")
-    x1s, b1 = split_of(x1), bound_of(x1)
-    x2s, b2 = (split_of(x2), bound_of(x2)) if x2 is not None else (None, None)
+    x1s, b1, x2s, b2 = _pair_operands(x1, x2)
     do, ho, wo = conv3d_out_dims(d)
     if out is None:
         out = torch.empty((d.N, do, ho, wo, d.Cout), dtype=torch.float32, device=x1.device)
     else:
         drop_split(out)
     need = lib.mf_conv3d_workspace_bytes(C.byref(d))
-    ws = Workspace.get(need, x1.device) if need else None
-    rc = lib.mf_conv3d_f16x2(x1s.data_ptr(), _ptr(x2s), wh.data_ptr(), _ptr(bias), out.data_ptr(), b1.data_ptr(), _ptr(b2), wmax, _ptr(ws), need,
+    ws, _ = _scratch(x1.device, need, 0)
+    rc = lib.mf_conv3d_f16x2(x1s.data_ptr(), _ptr(x2s), wh.data_ptr(), _ptr(bias), out.data_ptr(), b1.data_ptr(), _ptr(b2), wmax, ws, need,
                              C.byref(d), stream())
     L.check(rc, "mf_conv3d_f16x2")
     return out
@@ -887,8 +874,8 @@ def conv2d(x1: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor
     else:
         drop_split(out)
     need = lib.mf_conv2d_workspace_bytes(C.byref(d))
-    ws = Workspace.get(need, x1.device) if need else None
-    rc = lib.mf_conv2d_f32(x1.data_ptr(), _ptr(x2), w_packed.data_ptr(), _ptr(bias), out.data_ptr(), _ptr(ws), need, C.byref(d), stream())
+    ws, _ = _scratch(x1.device, need, 0)
+    rc = lib.mf_conv2d_f32(x1.data_ptr(), _ptr(x2), w_packed.data_ptr(), _ptr(bias), out.data_ptr(), ws, need, C.byref(d), stream())
     L.check(rc, "mf_conv2d_f32")
     return out
 
@@ -908,8 +895,8 @@ def conv2d_gn(x1: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Ten
     out = torch.empty((d.N, ho, wo, d.Cout), dtype=torch.float32, device=x1.device)
     partial = torch.empty((d.N, parts, G, 2), dtype=torch.float64, device=x1.device)
     need = lib.mf_conv2d_workspace_bytes(C.byref(d))
-    ws = Workspace.get(need, x1.device) if need else None
-    rc = lib.mf_conv2d_gn_f32(x1.data_ptr(), _ptr(x2), w_packed.data_ptr(), _ptr(bias), out.data_ptr(), _ptr(ws), need, partial.data_ptr(), G, C.byref(d),
+    ws, _ = _scratch(x1.device, need, 0)
+    rc = lib.mf_conv2d_gn_f32(x1.data_ptr(), _ptr(x2), w_packed.data_ptr(), _ptr(bias), out.data_ptr(), ws, need, partial.data_ptr(), G, C.byref(d),
                               stream())
     L.check(rc, "mf_conv2d_gn_f32")
     return out, partial
@@ -976,24 +963,12 @@ def gn_apply(x: torch.Tensor, stats, gamma, beta, G: int, act: int = 1, residual
     _need_f32(x)
     n, h, w, c = x.shape
     split = split and c % 8 == 0
-    res_pairs = None
-    if pairs_only(residual):
-        if not (split and part is not None):
-            _need_f32(residual)
-        res_pairs = residual._mf_split
     want_pairs_only = (not out_fp32) and split and part is not None
-    xb = rb = eb = ob = outs = rslots = None
-    if split:  # (before `out` may alias x or the residual: their bounds describe the values this pass READS)
-        xb = bound_of(x) if (stats is None and part is None) else None
-        if residual is not None:
-            if part is not None and _fresh(residual, "_mf_bound") is None and _fresh(residual, "_mf_slots") is not None:
-                rslots = residual._mf_slots
-            else:
-                rb = bound_of(residual)
-        if emb is not None:
-            eb = _fresh(emb, "_mf_bound")
-            if eb is None:
-                eb = maxabs_rows(emb.contiguous())
+    ob = outs = None
+    # (before `out` may alias x or the residual: their bounds describe the values this pass READS.  Only the from-partials pass reduces slot maxima
+    # itself, and only it, emitting pairs, reads a residual that exists as pairs only)
+    xb = bound_of(x) if (split and stats is None and part is None) else None
+    rp, res_pairs, rb, rslots, eb = _tail_operands(residual, emb, bounds=split, slots=part is not None, pairs=split and part is not None)
     if out is None:
         out = torch.empty_like(x)
     else:
@@ -1003,21 +978,18 @@ def gn_apply(x: torch.Tensor, stats, gamma, beta, G: int, act: int = 1, residual
         ob = torch.empty((n,), dtype=torch.float32, device=x.device)
     if part is not None:
         rc = L.load().mf_gn_apply_from_partials_pairs_f32(x.data_ptr(), part.records.data_ptr(), part.parts, float(part.eps), _ptr(gamma), _ptr(beta),
-                                                          None if res_pairs is not None else _ptr(residual), _ptr(res_pairs), _ptr(emb), emb_stride,
+                                                          rp, _ptr(res_pairs), _ptr(emb), emb_stride,
                                                           None if want_pairs_only else out.data_ptr(), _ptr(outs), _ptr(rb), _ptr(rslots),
                                                           0 if rslots is None else rslots.shape[1], _ptr(eb), float(bconst), _ptr(ob), n, h * w, c, G,
                                                           act, stream())
         L.check(rc, "mf_gn_apply_from_partials_pairs_f32")
     else:
-        rc = L.load().mf_gn_apply_split_f32(x.data_ptr(), _ptr(stats), _ptr(gamma), _ptr(beta), _ptr(residual), _ptr(emb), emb_stride, out.data_ptr(),
+        rc = L.load().mf_gn_apply_split_f32(x.data_ptr(), _ptr(stats), _ptr(gamma), _ptr(beta), rp, _ptr(emb), emb_stride, out.data_ptr(),
                                             _ptr(outs), _ptr(xb), _ptr(rb), _ptr(eb), float(bconst), _ptr(ob), n, h * w, c, G, act, stream())
         L.check(rc, "mf_gn_apply_split_f32")
     if split:
-        out._mf_split, out._mf_bound = outs, ob
-        _stamp(out)
-        _audit(out, "GroupNorm apply (derived: bconst + residual + embedding)" if (stats is not None or part is not None) else "apply without norm (bound(x) + residual + embedding)")
-        if want_pairs_only:
-            out._mf_pairs_only = True
+        _attach(out, "GroupNorm apply (derived: bconst + residual + embedding)" if (stats is not None or part is not None) else "apply without norm (bound(x) + residual + embedding)",
+                split=outs, bound=ob, pairs_only=want_pairs_only)
     return out
 
 
@@ -1109,10 +1081,15 @@ def image_to_uint8(x_nchw: torch.Tensor, normalize_each: bool = False) -> torch.
     return out
 
 
-def sched_step(args: L.MfSchedArgs, outputs=()) -> None:
-    """`outputs`: the tensors the step writes (x_t, x0, ...): the call goes by raw pointers, their fp16-pair mirrors (if any) are stale after it"""
+def _drop_outputs(outputs) -> None:
+    """the tensors a scheduler / solver step writes (x_t, x0, ...): the call goes by raw pointers, their fp16-pair mirrors (if any) are stale after it"""
     for t in outputs:
         drop_split(t)
+
+
+def sched_step(args: L.MfSchedArgs, outputs=()) -> None:
+    """`outputs`: the tensors the step writes (x_t, x0, ...): the call goes by raw pointers, their fp16-pair mirrors (if any) are stale after it"""
+    _drop_outputs(outputs)
     L.check(L.load().mf_sched_step_f32(C.byref(args), stream()), "mf_sched_step_f32")
 
 
@@ -1120,8 +1097,7 @@ def sched_step_philox(args: L.MfSchedArgs, seed: int, draw_base: int, draw_strid
     """the tail of a denoise iteration in one launch (mf_sched_step_philox_f32): both noise draws in registers, the scheduler step, the
     step counter += 1.  counter: int32 [2] on the device = (step, ticket word)."""
     _gpu(counter)
-    for t in outputs:
-        drop_split(t)
+    _drop_outputs(outputs)
     L.check(L.load().mf_sched_step_philox_f32(C.byref(args), seed & 0xFFFFFFFFFFFFFFFF, draw_base, draw_stride, sample_offset, B, counter.data_ptr(),
                                               counter.data_ptr() + 4, stream()), "mf_sched_step_philox_f32")
 
@@ -1177,8 +1153,7 @@ def select_cells(mask: torch.Tensor, a: torch.Tensor, b: torch.Tensor, out: Opti
 
 def sched_step_blend(args: L.MfSchedArgs, blend: L.MfSchedBlend, outputs=()) -> None:
     """sched_step with the kept cells of x_t_out replaced by the known latent at the next timestep (mf_sched_step_blend_f32)"""
-    for t in outputs:
-        drop_split(t)
+    _drop_outputs(outputs)
     L.check(L.load().mf_sched_step_blend_f32(C.byref(args), C.byref(blend), stream()), "mf_sched_step_blend_f32")
 
 
@@ -1186,8 +1161,7 @@ def sched_step_philox_blend(args: L.MfSchedArgs, blend: L.MfSchedBlend, seed: in
                             counter: torch.Tensor, outputs=()) -> None:
     """sched_step_philox with the same select, still one launch (mf_sched_step_philox_blend_f32)"""
     _gpu(counter)
-    for t in outputs:
-        drop_split(t)
+    _drop_outputs(outputs)
     L.check(L.load().mf_sched_step_philox_blend_f32(C.byref(args), seed & 0xFFFFFFFFFFFFFFFF, draw_base, draw_stride, sample_offset, B, counter.data_ptr(),
                                                     counter.data_ptr() + 4, C.byref(blend), stream()), "mf_sched_step_philox_blend_f32")
 
@@ -1195,8 +1169,7 @@ def sched_step_philox_blend(args: L.MfSchedArgs, blend: L.MfSchedBlend, seed: in
 def solver_step(args: L.MfSolverArgs, blend: Optional[L.MfSchedBlend] = None, outputs=()) -> None:
     """the deterministic solver step in one launch (mf_solver_step_f32; with `blend` mf_solver_step_blend_f32: the inpainting select on x_t_out).
     `outputs` as in sched_step."""
-    for t in outputs:
-        drop_split(t)
+    _drop_outputs(outputs)
     if blend is None:
         L.check(L.load().mf_solver_step_f32(C.byref(args), stream()), "mf_solver_step_f32")
     else:

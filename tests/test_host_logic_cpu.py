@@ -317,3 +317,56 @@ def test_forced_collective_on_a_one_rank_group(tmp_path):
     want = _FakePipe().sample(5, (2, 4, 4), condition=torch.arange(5) % 3, noise=noise, shard=(0, 1))
     assert torch.equal(torch.load(tmp_path / "forced.pt"), want)
     assert os.environ.get("MEDFUSION_FORCE_COLLECTIVE") is None   # the child's environment did not leak
+
+
+def test_mirror_bookkeeping_on_cpu_tensors(monkeypatch):
+    """the fp16-pair / Winograd mirrors that travel as attributes of a tensor (kernels.MIRRORS): attached through one helper, valid until a torch in-place op
+    touches the tensor, then dropped ALL at once -- or, for a tensor that exists as pairs only, refused; drop_split clears them and the pairs-only flag
+    and nothing else.  Pure attribute bookkeeping: no device."""
+    import re
+    from medfusion_amd import kernels as K
+    monkeypatch.setattr(K, "AUDIT", False)
+
+    def mirrors():
+        return dict(split=torch.zeros((2, 4, 4, 8), dtype=torch.int32), bound=torch.ones(2), slots=torch.zeros((2, 3)),
+                    wino=(torch.zeros((16, 2, 4, 8), dtype=torch.int32), torch.ones(32)), wino_f32=torch.zeros((16, 2, 4, 8)))
+
+    t, m = torch.zeros((2, 4, 4, 8)), mirrors()
+    assert K._attach(t, "a test site", **m) is t
+    assert not K.stale(t) and t._mf_ver == t._version and not K.pairs_only(t)
+    want = dict(_mf_split=m["split"], _mf_bound=m["bound"], _mf_slots=m["slots"], _mf_wino=m["wino"][0], _mf_wino_bound=m["wino"][1], _mf_wino_f32=m["wino_f32"])
+    assert set(want) == set(K.MIRRORS)                      # every mirror kind can be attached through the helper
+    for name in K.MIRRORS:
+        assert K._fresh(t, name) is want[name], name
+    t.add_(1.0)                                             # a torch in-place op: every mirror describes the old values
+    assert K.stale(t)
+    assert K._fresh(t, "_mf_bound") is None and not K.stale(t)
+    for name in K.MIRRORS:
+        assert getattr(t, name) is None and K._fresh(t, name) is None, name
+
+    p = K._attach(torch.zeros((2, 4, 4, 8)), split=m["split"], bound=m["bound"], pairs_only=True)
+    assert K.pairs_only(p) and K._fresh(p, "_mf_split") is m["split"]
+    with pytest.raises(RuntimeError, match="only as fp16 pairs"):
+        K._need_f32(p)
+    p.mul_(2.0)                                             # ... on storage that holds no values: an error, not a silent drop
+    with pytest.raises(RuntimeError, match="in-place op touched a tensor that exists only as fp16 pairs"):
+        K._fresh(p, "_mf_split")
+    with pytest.raises(RuntimeError, match="only as fp16 pairs"):
+        K._need_f32(p)
+
+    d = K._attach(torch.zeros((2, 4, 4, 8)), pairs_only=True, **mirrors())
+    site, site32 = ({}, "key"), ({}, "key32")
+    d._mf_wino_site, d._mf_wino_site_f32 = site, site32
+    K.drop_split(d)
+    assert not K.pairs_only(d) and all(getattr(d, name) is None for name in K.MIRRORS)
+    assert d._mf_wino_site is site and d._mf_wino_site_f32 is site32 and d._mf_ver == d._version
+    K._need_f32(d)
+    K.drop_split(None)
+
+    # the guard for the next mirror kind: whatever `_mf_*` attribute the wrappers, the blocks or the UNet name is a droppable mirror, or one of the three
+    # documented exceptions -- the pairs-only flag, the version stamp, the site a wanted transform is reported to (one per arithmetic)
+    exceptions = {"_mf_pairs_only", "_mf_ver", "_mf_wino_site", "_mf_wino_site_f32"}
+    named = set()
+    for f in ("kernels.py", "blocks.py", "unet.py"):
+        named |= set(re.findall(r"\b_mf_[a-z0-9_]*[a-z0-9]", (ROOT / "medfusion_amd" / f).read_text()))
+    assert set(K.MIRRORS) <= named and named - set(K.MIRRORS) == exceptions, named - set(K.MIRRORS) ^ exceptions

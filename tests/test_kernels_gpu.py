@@ -1438,7 +1438,7 @@ def test_grouped_conv_res_inside_the_blocks(dev):
         want = blk(x, emb=emb, emb_stride=512)
         BLK.GROUPED_CONV_RES = True
         got = blk(x, emb=emb, emb_stride=512)
-        assert blk._group and next(iter(blk._group.values())) is not None      # the pair shares a launch for this shape
+        assert blk._group and next(iter(blk._group.values()))      # the pair shares a launch for this shape (None / False: it does not)
         assert torch.equal(got, want) and torch.equal(got._mf_split, want._mf_split) and torch.equal(got._mf_bound, want._mf_bound)
         xo = K.nchw_to_nhwc(_rand("grpo", (2, 256, 10, 12)).to(dev))              # no instantiated pair for what the planner picks here, or it is: either way equal
         BLK.GROUPED_CONV_RES = False
@@ -1447,3 +1447,91 @@ def test_grouped_conv_res_inside_the_blocks(dev):
         assert torch.equal(blk(xo, emb=emb[:2], emb_stride=512), want_o)
     finally:
         BLK.GROUPED_CONV_RES, BLK.WINOGRAD = old, old_w
+
+
+def test_every_producer_attaches_exactly_its_mirrors(dev):
+    """Which mirror attributes (kernels.MIRRORS) each producer leaves on the tensor it returns, and which it does not -- the table below is read off the
+    wrappers as they stood before their host plumbing was factored: a slot array is not a bound, a pair mirror comes with its bound, V with its bounds, a
+    pairs-only output says so; whatever carries a mirror carries the version stamp it was made at, whatever carries none is not stamped."""
+    from medfusion_amd import blocks as BLK, kernels as K
+    rows = []      # (producer, tensor, mirrors present, pairs only)
+
+    def conv_operands(tag, n, h, w, ci, co, k):
+        x = K.nchw_to_nhwc(_rand(f"mir_x{tag}", (n, ci, h, w)).to(dev))
+        wt = _rand(f"mir_w{tag}", (co, ci, k, k), 1.0 / np.sqrt(ci * k * k)).to(dev)
+        return x, wt, _rand(f"mir_b{tag}", (co,), 0.1).to(dev)
+
+    # the plain fp16-pair convolution, measuring / deriving the bound of its output; the apply pass behind it
+    n, h, w, ci, co, G = 2, 8, 8, 64, 64, 8
+    x, wt, b = conv_operands("a", n, h, w, ci, co, 1)
+    wp = K.pack_conv_weight(wt)
+    wh = K.split_weight_f16x2(wp)
+    d = K.make_conv_desc(n, h, w, ci, 0, co, 1, 1, 0, 0, precision=5)
+    assert K.conv_f16x2_ok(d) and K.conv_pairs_out_ok(d) and K.pin_conv_plan(d)[1] > 0
+    rows.append(("conv2d_f16x2(measure_out)", K.conv2d_f16x2(x, wh, b, d, measure_out=True), {"_mf_slots"}, False))
+    rows.append(("conv2d_f16x2 (plain)", K.conv2d_f16x2(x, wh, b, d), set(), False))
+    rows.append(("conv2d_f16x2: its input", x, {"_mf_split", "_mf_bound"}, False))
+    l1 = (float(wp.abs().sum(dim=(-3, -2, -1)).max()) * (1 + 1e-5), 0.0)
+    rows.append(("conv2d_f16x2_pairs_out", K.conv2d_f16x2_pairs_out(x, wh, b, d, l1, float(b.abs().max())), {"_mf_split", "_mf_bound"}, False))
+    gamma, beta = (1.0 + _rand("mir_g", (co,), 0.1)).to(dev), _rand("mir_be", (co,), 0.1).to(dev)
+    parts = K.conv_gn_parts(d, G)
+    assert parts > 0
+    bc = float(gamma.abs().max()) * (h * w * co // G) ** 0.5 + float(beta.abs().max())
+    for out_fp32 in (True, False):
+        y, partial = K.conv2d_f16x2(x, wh, b, d, gn_groups=G, gn_parts=parts)
+        rows.append(("conv2d_f16x2(gn_groups)", y, set(), False))
+        a = K.gn_apply(y, K.GnPartials(partial, parts, 1e-5), gamma, beta, G, split=True, bconst=bc, out_fp32=out_fp32)
+        rows.append((f"gn_apply(split, out_fp32={out_fp32})", a, {"_mf_split", "_mf_bound"}, not out_fp32))
+    rows.append(("gn_apply (no split)", K.gn_apply(y, K.GnPartials(partial, parts, 1e-5), gamma, beta, G), set(), False))
+
+    # the Winograd convolution with its tail
+    n, h, w, ci, co, G = 4, 16, 16, 64, 128, 8
+    x, wt, b = conv_operands("w", n, h, w, ci, co, 3)
+    uh = K.split_weight_f16x2(K.wino_pack_weight(wt))
+    d = K.make_conv_desc(n, h, w, ci, 0, co, 3, 1, 1, 0, precision=5)
+    assert K.wino_tail_ok(d, G)
+    gamma, beta = (1.0 + _rand("mir_wg", (co,), 0.1)).to(dev), _rand("mir_wb", (co,), 0.1).to(dev)
+    bc = float(gamma.abs().max()) * (h * w * co // G) ** 0.5 + float(beta.abs().max())
+    for want in (False, True):
+        y = K.conv2d_wino_gn_apply(x, uh, b, d, gamma, beta, G, 1e-5, bconst=bc, want_wino=want)
+        rows.append((f"conv2d_wino_gn_apply(want_wino={want})", y, {"_mf_split", "_mf_bound"} | ({"_mf_wino", "_mf_wino_bound"} if want else set()), False))
+    rows.append(("wino_input (the Winograd convolution's input)", x, {"_mf_split", "_mf_bound", "_mf_wino", "_mf_wino_bound"}, False))
+
+    # conv_res as the guest of the Winograd GEMM (the smallest shape the block plans it for) and of the direct 3x3 (grouped launch)
+    old = BLK.WINOGRAD
+    try:
+        for kind, (n, h, w, ci, co), wino in (("wino guest", (16, 8, 8, 512, 1024), 1), ("group", (16, 16, 16, 256, 512), 0)):
+            BLK.WINOGRAD = wino
+            blk = BLK.BasicResBlock(2, ci, co, 3, 1, ("GROUP", {"num_groups": 32, "affine": True}), ("Swish", {})).to(dev)
+            S.synth_state_dict(blk, f"mir{kind}.")
+            c3, cr, nm = blk.basic_block.conv, blk.conv_res, blk.basic_block.norm
+            x = K.nchw_to_nhwc(_rand(f"mir_x{kind}", (n, ci, h, w)).to(dev))
+            bc = nm.bound_const(h * w * (co // 32))
+            if kind == "group":
+                g = blk._grouped(x)
+                assert g is not None
+                (ya, _), yb = K.conv2d_f16x2_group(x, None, dict(w_split=c3._packed.get_f16x2(c3.weight), bias=c3.bias, d=g[0], gn_groups=32, gn_parts=g[1], pinned=g[2]),
+                                                   dict(w_split=cr._packed.get_f16x2(cr.weight), bias=cr.bias, d=g[3], pinned=g[4]))
+                rows += [("conv2d_f16x2_group: the 3x3", ya, set(), False), ("conv2d_f16x2_group: conv_res", yb, {"_mf_slots"}, False)]
+            else:
+                g, (_, tail) = blk._wino_guest(x), c3.wino_tail_desc(x, 32)
+                assert g is not None and tail is not None
+                y = K.conv2d_wino_gn_apply(x, c3._packed.get_wino(c3.weight), c3.bias, tail[0], nm.weight, nm.bias, 32, nm.eps, bconst=bc, pinned=tail[1],
+                                           guest=dict(w_split=cr._packed.get_f16x2(cr.weight), bias=cr.bias, d=g[0], pinned=g[1]))
+                rows.append(("conv2d_wino_gn_apply(guest)", y, {"_mf_split", "_mf_bound"}, False))
+    finally:
+        BLK.WINOGRAD = old
+
+    xp = K.pack_nchw_pairs(_rand("mir_p", (2, 3, 8, 8)).to(dev), 32)
+    rows.append(("pack_nchw_pairs", xp, {"_mf_split", "_mf_bound"}, True))
+
+    torch.cuda.synchronize()
+    assert len(rows) == 16
+    for name, t, present, po in rows:
+        have = {m for m in K.MIRRORS if getattr(t, m, None) is not None}
+        assert have == present, (name, sorted(have), sorted(present))
+        assert K.pairs_only(t) == po, name
+        if present:
+            assert t._mf_ver == t._version and not K.stale(t), name
+        else:
+            assert getattr(t, "_mf_ver", None) is None, name

@@ -393,6 +393,237 @@ def test_conv_res_finds_its_place_in_the_component_gemm_launch():
         assert blk._grouped(x) is None                                # (the direct form's grouped launch steps aside)
 
 
+PLAN_SNAPSHOT_SHAPES = [(16, 16, 16, 256, 0, 512), (16, 8, 8, 512, 0, 1024), (16, 8, 8, 1024, 1024, 1024), (16, 8, 8, 1024, 512, 512), (16, 16, 16, 512, 512, 512),
+                        (16, 16, 16, 512, 256, 256), (16, 32, 32, 256, 256, 256), (8, 8, 8, 1024, 1024, 1024), (32, 8, 8, 512, 0, 1024), (2, 4, 4, 64, 0, 128),
+                        (1, 8, 8, 32, 0, 64)]
+# (N, H, W, C1, C2, Cout, WINOGRAD, WINO_TAIL) -> (_grouped, _wino_guest, Conv.wino_tail_desc, the ("f16x2", ...) entry of the 3x3 at G = 32), every descriptor as
+# the tuple of its fields.  Recorded at the commit BEFORE the wrappers' host plumbing was factored (the planner, the library and the policy in blocks.py as
+# they stood): whoever changes a plan on purpose re-records the entries that change and says why; a refactor must not.
+PLAN_SNAPSHOT = \
+{(1, 8, 8, 32, 0, 64, 0, 0): (None, None, (('wino_tail', 1, 8, 8, 32, 0, 32, 0, False), None), ((1, 8, 8, 32, 0, 64, 3, 3, 1, 1, 0, 0, 0, 54, 1, 5), 0, True, (0, 2, 0), None)),
+ (1, 8, 8, 32, 0, 64, 0, 1): (None, None, (('wino_tail', 1, 8, 8, 32, 0, 32, 0, True), None), ((1, 8, 8, 32, 0, 64, 3, 3, 1, 1, 0, 0, 0, 54, 1, 5), 0, True, (0, 2, 0), None)),
+ (1, 8, 8, 32, 0, 64, 1, 0): (None, None, (('wino_tail', 1, 8, 8, 32, 0, 32, 1, False), None), ((1, 8, 8, 32, 0, 64, 3, 3, 1, 1, 0, 0, 0, 54, 1, 5), 0, True, (0, 2, 0), None)),
+ (1, 8, 8, 32, 0, 64, 1, 1): (None, None, (('wino_tail', 1, 8, 8, 32, 0, 32, 1, True), None), ((1, 8, 8, 32, 0, 64, 3, 3, 1, 1, 0, 0, 0, 54, 1, 5), 0, True, (0, 2, 0), None)),
+ (1, 8, 8, 32, 0, 64, 2, 0): (None, None, (('wino_tail', 1, 8, 8, 32, 0, 32, 2, False), None), ((1, 8, 8, 32, 0, 64, 3, 3, 1, 1, 0, 0, 0, 54, 1, 5), 0, True, (0, 2, 0), None)),
+ (1, 8, 8, 32, 0, 64, 2, 1): (None, None, (('wino_tail', 1, 8, 8, 32, 0, 32, 2, True), None), ((1, 8, 8, 32, 0, 64, 3, 3, 1, 1, 0, 0, 0, 54, 1, 5), 0, True, (0, 2, 0), None)),
+ (2, 4, 4, 64, 0, 128, 0, 0): (None, None, (('wino_tail', 2, 4, 4, 64, 0, 32, 0, False), None), ((2, 4, 4, 64, 0, 128, 3, 3, 1, 1, 0, 0, 0, 53, 2, 5), 4, True, (65536, 0, 1), None)),
+ (2, 4, 4, 64, 0, 128, 0, 1): (None, None, (('wino_tail', 2, 4, 4, 64, 0, 32, 0, True), None), ((2, 4, 4, 64, 0, 128, 3, 3, 1, 1, 0, 0, 0, 53, 2, 5), 4, True, (65536, 0, 1), None)),
+ (2, 4, 4, 64, 0, 128, 1, 0): (None, None, (('wino_tail', 2, 4, 4, 64, 0, 32, 1, False), None), ((2, 4, 4, 64, 0, 128, 3, 3, 1, 1, 0, 0, 0, 53, 2, 5), 4, True, (65536, 0, 1), None)),
+ (2, 4, 4, 64, 0, 128, 1, 1): (None, None, (('wino_tail', 2, 4, 4, 64, 0, 32, 1, True), None), ((2, 4, 4, 64, 0, 128, 3, 3, 1, 1, 0, 0, 0, 53, 2, 5), 4, True, (65536, 0, 1), None)),
+ (2, 4, 4, 64, 0, 128, 2, 0): (None, None, (('wino_tail', 2, 4, 4, 64, 0, 32, 2, False), None), ((2, 4, 4, 64, 0, 128, 3, 3, 1, 1, 0, 0, 0, 53, 2, 5), 4, True, (65536, 0, 1), None)),
+ (2, 4, 4, 64, 0, 128, 2, 1): (None, None, (('wino_tail', 2, 4, 4, 64, 0, 32, 2, True), None), ((2, 4, 4, 64, 0, 128, 3, 3, 1, 1, 0, 0, 0, 53, 2, 5), 4, True, (65536, 0, 1), None)),
+ (8, 8, 8, 1024, 1024, 1024, 0, 0): (((8, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 34, 8, 5), 1, (29360128, 32, 224), (8, 8, 8, 1024, 1024, 1024, 1, 1, 1, 0, 0, 0, 0, 36, 4, 5),
+                                      (12582912, 64, 192)),
+                                     None, (('wino_tail', 8, 8, 8, 1024, 1024, 32, 0, False), None), ((8, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 34, 8, 5), 1, True, (29360128, 32, 224), None)),
+ (8, 8, 8, 1024, 1024, 1024, 0, 1): (((8, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 34, 8, 5), 1, (29360128, 32, 224), (8, 8, 8, 1024, 1024, 1024, 1, 1, 1, 0, 0, 0, 0, 36, 4, 5),
+                                      (12582912, 64, 192)),
+                                     None, (('wino_tail', 8, 8, 8, 1024, 1024, 32, 0, True), None), ((8, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 34, 8, 5), 1, True, (29360128, 32, 224), None)),
+ (8, 8, 8, 1024, 1024, 1024, 1, 0): (((8, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 34, 8, 5), 1, (29360128, 32, 224), (8, 8, 8, 1024, 1024, 1024, 1, 1, 1, 0, 0, 0, 0, 36, 4, 5),
+                                      (12582912, 64, 192)),
+                                     None, (('wino_tail', 8, 8, 8, 1024, 1024, 32, 1, False), None),
+                                     ((8, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 34, 8, 5), 1, True, (29360128, 32, 224),
+                                      ((8, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), 16, (8388608, 0)))),
+ (8, 8, 8, 1024, 1024, 1024, 1, 1): (None, ((8, 8, 8, 1024, 1024, 1024, 1, 1, 1, 0, 0, 0, 0, 53, 4, 5), (12582912, 32, 192)),
+                                     (('wino_tail', 8, 8, 8, 1024, 1024, 32, 1, True), ((8, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), (8388608, 0))),
+                                     ((8, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 34, 8, 5), 1, True, (29360128, 32, 224),
+                                      ((8, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), 16, (8388608, 0)))),
+ (8, 8, 8, 1024, 1024, 1024, 2, 0): (((8, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 34, 8, 5), 1, (29360128, 32, 224), (8, 8, 8, 1024, 1024, 1024, 1, 1, 1, 0, 0, 0, 0, 36, 4, 5),
+                                      (12582912, 64, 192)),
+                                     None, (('wino_tail', 8, 8, 8, 1024, 1024, 32, 2, False), None),
+                                     ((8, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 34, 8, 5), 1, True, (29360128, 32, 224),
+                                      ((8, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), 16, (8388608, 0)))),
+ (8, 8, 8, 1024, 1024, 1024, 2, 1): (None, ((8, 8, 8, 1024, 1024, 1024, 1, 1, 1, 0, 0, 0, 0, 53, 4, 5), (12582912, 32, 192)),
+                                     (('wino_tail', 8, 8, 8, 1024, 1024, 32, 2, True), ((8, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), (8388608, 0))),
+                                     ((8, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 34, 8, 5), 1, True, (29360128, 32, 224),
+                                      ((8, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), 16, (8388608, 0)))),
+ (16, 8, 8, 512, 0, 1024, 0, 0): (((16, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 53, 2, 5), 1, (8388608, 32, 128), (16, 8, 8, 512, 0, 1024, 1, 1, 1, 0, 0, 0, 0, 53, 1, 5), (0, 32, 0)), None,
+                                  (('wino_tail', 16, 8, 8, 512, 0, 32, 0, False), None), ((16, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 53, 2, 5), 1, True, (8388608, 32, 128), None)),
+ (16, 8, 8, 512, 0, 1024, 0, 1): (((16, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 53, 2, 5), 1, (8388608, 32, 128), (16, 8, 8, 512, 0, 1024, 1, 1, 1, 0, 0, 0, 0, 53, 1, 5), (0, 32, 0)), None,
+                                  (('wino_tail', 16, 8, 8, 512, 0, 32, 0, True), None), ((16, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 53, 2, 5), 1, True, (8388608, 32, 128), None)),
+ (16, 8, 8, 512, 0, 1024, 1, 0): (((16, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 53, 2, 5), 1, (8388608, 32, 128), (16, 8, 8, 512, 0, 1024, 1, 1, 1, 0, 0, 0, 0, 53, 1, 5), (0, 32, 0)), None,
+                                  (('wino_tail', 16, 8, 8, 512, 0, 32, 1, False), None),
+                                  ((16, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 53, 2, 5), 1, True, (8388608, 32, 128), ((16, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), 16, (16777216, 0)))),
+ (16, 8, 8, 512, 0, 1024, 1, 1): (None, ((16, 8, 8, 512, 0, 1024, 1, 1, 1, 0, 0, 0, 0, 36, 1, 5), (0, 64, 0)),
+                                  (('wino_tail', 16, 8, 8, 512, 0, 32, 1, True), ((16, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), (16777216, 0))),
+                                  ((16, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 53, 2, 5), 1, True, (8388608, 32, 128), ((16, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), 16, (16777216, 0)))),
+ (16, 8, 8, 512, 0, 1024, 2, 0): (((16, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 53, 2, 5), 1, (8388608, 32, 128), (16, 8, 8, 512, 0, 1024, 1, 1, 1, 0, 0, 0, 0, 53, 1, 5), (0, 32, 0)), None,
+                                  (('wino_tail', 16, 8, 8, 512, 0, 32, 2, False), None),
+                                  ((16, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 53, 2, 5), 1, True, (8388608, 32, 128), ((16, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), 16, (16777216, 0)))),
+ (16, 8, 8, 512, 0, 1024, 2, 1): (None, ((16, 8, 8, 512, 0, 1024, 1, 1, 1, 0, 0, 0, 0, 36, 1, 5), (0, 64, 0)),
+                                  (('wino_tail', 16, 8, 8, 512, 0, 32, 2, True), ((16, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), (16777216, 0))),
+                                  ((16, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 53, 2, 5), 1, True, (8388608, 32, 128), ((16, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), 16, (16777216, 0)))),
+ (16, 8, 8, 1024, 512, 512, 0, 0): (((16, 8, 8, 1024, 512, 512, 3, 3, 1, 1, 0, 0, 0, 34, 8, 5), 1, (29360128, 16, 224), (16, 8, 8, 1024, 512, 512, 1, 1, 1, 0, 0, 0, 0, 36, 4, 5), (12582912, 32, 192)),
+                                    None, (('wino_tail', 16, 8, 8, 1024, 512, 32, 0, False), None), ((16, 8, 8, 1024, 512, 512, 3, 3, 1, 1, 0, 0, 0, 34, 8, 5), 1, True, (29360128, 16, 224), None)),
+ (16, 8, 8, 1024, 512, 512, 0, 1): (((16, 8, 8, 1024, 512, 512, 3, 3, 1, 1, 0, 0, 0, 34, 8, 5), 1, (29360128, 16, 224), (16, 8, 8, 1024, 512, 512, 1, 1, 1, 0, 0, 0, 0, 36, 4, 5), (12582912, 32, 192)),
+                                    None, (('wino_tail', 16, 8, 8, 1024, 512, 32, 0, True), None), ((16, 8, 8, 1024, 512, 512, 3, 3, 1, 1, 0, 0, 0, 34, 8, 5), 1, True, (29360128, 16, 224), None)),
+ (16, 8, 8, 1024, 512, 512, 1, 0): (((16, 8, 8, 1024, 512, 512, 3, 3, 1, 1, 0, 0, 0, 34, 8, 5), 1, (29360128, 16, 224), (16, 8, 8, 1024, 512, 512, 1, 1, 1, 0, 0, 0, 0, 36, 4, 5), (12582912, 32, 192)),
+                                    None, (('wino_tail', 16, 8, 8, 1024, 512, 32, 1, False), None),
+                                    ((16, 8, 8, 1024, 512, 512, 3, 3, 1, 1, 0, 0, 0, 34, 8, 5), 1, True, (29360128, 16, 224),
+                                     ((16, 8, 8, 1024, 512, 512, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), 8, (8388608, 0)))),
+ (16, 8, 8, 1024, 512, 512, 1, 1): (None, ((16, 8, 8, 1024, 512, 512, 1, 1, 1, 0, 0, 0, 0, 53, 4, 5), (12582912, 16, 192)),
+                                    (('wino_tail', 16, 8, 8, 1024, 512, 32, 1, True), ((16, 8, 8, 1024, 512, 512, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), (8388608, 0))),
+                                    ((16, 8, 8, 1024, 512, 512, 3, 3, 1, 1, 0, 0, 0, 34, 8, 5), 1, True, (29360128, 16, 224),
+                                     ((16, 8, 8, 1024, 512, 512, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), 8, (8388608, 0)))),
+ (16, 8, 8, 1024, 512, 512, 2, 0): (((16, 8, 8, 1024, 512, 512, 3, 3, 1, 1, 0, 0, 0, 34, 8, 5), 1, (29360128, 16, 224), (16, 8, 8, 1024, 512, 512, 1, 1, 1, 0, 0, 0, 0, 36, 4, 5), (12582912, 32, 192)),
+                                    None, (('wino_tail', 16, 8, 8, 1024, 512, 32, 2, False), None),
+                                    ((16, 8, 8, 1024, 512, 512, 3, 3, 1, 1, 0, 0, 0, 34, 8, 5), 1, True, (29360128, 16, 224),
+                                     ((16, 8, 8, 1024, 512, 512, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), 8, (8388608, 0)))),
+ (16, 8, 8, 1024, 512, 512, 2, 1): (None, ((16, 8, 8, 1024, 512, 512, 1, 1, 1, 0, 0, 0, 0, 53, 4, 5), (12582912, 16, 192)),
+                                    (('wino_tail', 16, 8, 8, 1024, 512, 32, 2, True), ((16, 8, 8, 1024, 512, 512, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), (8388608, 0))),
+                                    ((16, 8, 8, 1024, 512, 512, 3, 3, 1, 1, 0, 0, 0, 34, 8, 5), 1, True, (29360128, 16, 224),
+                                     ((16, 8, 8, 1024, 512, 512, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), 8, (8388608, 0)))),
+ (16, 8, 8, 1024, 1024, 1024, 0, 0): (((16, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 62, 8, 5), 1, (58720256, 16, 224), (16, 8, 8, 1024, 1024, 1024, 1, 1, 1, 0, 0, 0, 0, 36, 2, 5),
+                                       (8388608, 64, 128)),
+                                      None, (('wino_tail', 16, 8, 8, 1024, 1024, 32, 0, False), None),
+                                      ((16, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 62, 8, 5), 1, True, (58720256, 16, 224), None)),
+ (16, 8, 8, 1024, 1024, 1024, 0, 1): (((16, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 62, 8, 5), 1, (58720256, 16, 224), (16, 8, 8, 1024, 1024, 1024, 1, 1, 1, 0, 0, 0, 0, 36, 2, 5),
+                                       (8388608, 64, 128)),
+                                      None, (('wino_tail', 16, 8, 8, 1024, 1024, 32, 0, True), None),
+                                      ((16, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 62, 8, 5), 1, True, (58720256, 16, 224), None)),
+ (16, 8, 8, 1024, 1024, 1024, 1, 0): (((16, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 62, 8, 5), 1, (58720256, 16, 224), (16, 8, 8, 1024, 1024, 1024, 1, 1, 1, 0, 0, 0, 0, 36, 2, 5),
+                                       (8388608, 64, 128)),
+                                      None, (('wino_tail', 16, 8, 8, 1024, 1024, 32, 1, False), None),
+                                      ((16, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 62, 8, 5), 1, True, (58720256, 16, 224), None)),
+ (16, 8, 8, 1024, 1024, 1024, 1, 1): (None, ((16, 8, 8, 1024, 1024, 1024, 1, 1, 1, 0, 0, 0, 0, 36, 2, 5), (8388608, 64, 128)),
+                                      (('wino_tail', 16, 8, 8, 1024, 1024, 32, 1, True), ((16, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), (16777216, 0))),
+                                      ((16, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 62, 8, 5), 1, True, (58720256, 16, 224), None)),
+ (16, 8, 8, 1024, 1024, 1024, 2, 0): (((16, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 62, 8, 5), 1, (58720256, 16, 224), (16, 8, 8, 1024, 1024, 1024, 1, 1, 1, 0, 0, 0, 0, 36, 2, 5),
+                                       (8388608, 64, 128)),
+                                      None, (('wino_tail', 16, 8, 8, 1024, 1024, 32, 2, False), None),
+                                      ((16, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 62, 8, 5), 1, True, (58720256, 16, 224), None)),
+ (16, 8, 8, 1024, 1024, 1024, 2, 1): (None, ((16, 8, 8, 1024, 1024, 1024, 1, 1, 1, 0, 0, 0, 0, 36, 2, 5), (8388608, 64, 128)),
+                                      (('wino_tail', 16, 8, 8, 1024, 1024, 32, 2, True), ((16, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), (16777216, 0))),
+                                      ((16, 8, 8, 1024, 1024, 1024, 3, 3, 1, 1, 0, 0, 0, 62, 8, 5), 1, True, (58720256, 16, 224), None)),
+ (16, 16, 16, 256, 0, 512, 0, 0): (((16, 16, 16, 256, 0, 512, 3, 3, 1, 1, 0, 0, 0, 53, 1, 5), 4, (0, 64, 0), (16, 16, 16, 256, 0, 512, 1, 1, 1, 0, 0, 0, 0, 53, 1, 5), (0, 64, 0)), None,
+                                   (('wino_tail', 16, 16, 16, 256, 0, 32, 0, False), None), ((16, 16, 16, 256, 0, 512, 3, 3, 1, 1, 0, 0, 0, 53, 1, 5), 4, True, (0, 64, 0), None)),
+ (16, 16, 16, 256, 0, 512, 0, 1): (((16, 16, 16, 256, 0, 512, 3, 3, 1, 1, 0, 0, 0, 53, 1, 5), 4, (0, 64, 0), (16, 16, 16, 256, 0, 512, 1, 1, 1, 0, 0, 0, 0, 53, 1, 5), (0, 64, 0)), None,
+                                   (('wino_tail', 16, 16, 16, 256, 0, 32, 0, True), None), ((16, 16, 16, 256, 0, 512, 3, 3, 1, 1, 0, 0, 0, 53, 1, 5), 4, True, (0, 64, 0), None)),
+ (16, 16, 16, 256, 0, 512, 1, 0): (((16, 16, 16, 256, 0, 512, 3, 3, 1, 1, 0, 0, 0, 53, 1, 5), 4, (0, 64, 0), (16, 16, 16, 256, 0, 512, 1, 1, 1, 0, 0, 0, 0, 53, 1, 5), (0, 64, 0)), None,
+                                   (('wino_tail', 16, 16, 16, 256, 0, 32, 1, False), None), ((16, 16, 16, 256, 0, 512, 3, 3, 1, 1, 0, 0, 0, 53, 1, 5), 4, True, (0, 64, 0), None)),
+ (16, 16, 16, 256, 0, 512, 1, 1): (((16, 16, 16, 256, 0, 512, 3, 3, 1, 1, 0, 0, 0, 53, 1, 5), 4, (0, 64, 0), (16, 16, 16, 256, 0, 512, 1, 1, 1, 0, 0, 0, 0, 53, 1, 5), (0, 64, 0)), None,
+                                   (('wino_tail', 16, 16, 16, 256, 0, 32, 1, True), None), ((16, 16, 16, 256, 0, 512, 3, 3, 1, 1, 0, 0, 0, 53, 1, 5), 4, True, (0, 64, 0), None)),
+ (16, 16, 16, 256, 0, 512, 2, 0): (((16, 16, 16, 256, 0, 512, 3, 3, 1, 1, 0, 0, 0, 53, 1, 5), 4, (0, 64, 0), (16, 16, 16, 256, 0, 512, 1, 1, 1, 0, 0, 0, 0, 53, 1, 5), (0, 64, 0)), None,
+                                   (('wino_tail', 16, 16, 16, 256, 0, 32, 2, False), None),
+                                   ((16, 16, 16, 256, 0, 512, 3, 3, 1, 1, 0, 0, 0, 53, 1, 5), 4, True, (0, 64, 0), ((16, 16, 16, 256, 0, 512, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), 32, (33554432, 0)))),
+ (16, 16, 16, 256, 0, 512, 2, 1): (None, ((16, 16, 16, 256, 0, 512, 1, 1, 1, 0, 0, 0, 0, 36, 1, 5), (0, 128, 0)),
+                                   (('wino_tail', 16, 16, 16, 256, 0, 32, 2, True), ((16, 16, 16, 256, 0, 512, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), (33554432, 0))),
+                                   ((16, 16, 16, 256, 0, 512, 3, 3, 1, 1, 0, 0, 0, 53, 1, 5), 4, True, (0, 64, 0), ((16, 16, 16, 256, 0, 512, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), 32, (33554432, 0)))),
+ (16, 16, 16, 512, 256, 256, 0, 0): (((16, 16, 16, 512, 256, 256, 3, 3, 1, 1, 0, 0, 0, 34, 4, 5), 2, (25165824, 32, 192), (16, 16, 16, 512, 256, 256, 1, 1, 1, 0, 0, 0, 0, 36, 1, 5), (0, 64, 0)), None,
+                                     (('wino_tail', 16, 16, 16, 512, 256, 32, 0, False), None), ((16, 16, 16, 512, 256, 256, 3, 3, 1, 1, 0, 0, 0, 34, 4, 5), 2, True, (25165824, 32, 192), None)),
+ (16, 16, 16, 512, 256, 256, 0, 1): (((16, 16, 16, 512, 256, 256, 3, 3, 1, 1, 0, 0, 0, 34, 4, 5), 2, (25165824, 32, 192), (16, 16, 16, 512, 256, 256, 1, 1, 1, 0, 0, 0, 0, 36, 1, 5), (0, 64, 0)), None,
+                                     (('wino_tail', 16, 16, 16, 512, 256, 32, 0, True), None), ((16, 16, 16, 512, 256, 256, 3, 3, 1, 1, 0, 0, 0, 34, 4, 5), 2, True, (25165824, 32, 192), None)),
+ (16, 16, 16, 512, 256, 256, 1, 0): (((16, 16, 16, 512, 256, 256, 3, 3, 1, 1, 0, 0, 0, 34, 4, 5), 2, (25165824, 32, 192), (16, 16, 16, 512, 256, 256, 1, 1, 1, 0, 0, 0, 0, 36, 1, 5), (0, 64, 0)), None,
+                                     (('wino_tail', 16, 16, 16, 512, 256, 32, 1, False), None),
+                                     ((16, 16, 16, 512, 256, 256, 3, 3, 1, 1, 0, 0, 0, 34, 4, 5), 2, True, (25165824, 32, 192),
+                                      ((16, 16, 16, 512, 256, 256, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), 16, (16777216, 0)))),
+ (16, 16, 16, 512, 256, 256, 1, 1): (None, ((16, 16, 16, 512, 256, 256, 1, 1, 1, 0, 0, 0, 0, 36, 1, 5), (0, 64, 0)),
+                                     (('wino_tail', 16, 16, 16, 512, 256, 32, 1, True), ((16, 16, 16, 512, 256, 256, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), (16777216, 0))),
+                                     ((16, 16, 16, 512, 256, 256, 3, 3, 1, 1, 0, 0, 0, 34, 4, 5), 2, True, (25165824, 32, 192),
+                                      ((16, 16, 16, 512, 256, 256, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), 16, (16777216, 0)))),
+ (16, 16, 16, 512, 256, 256, 2, 0): (((16, 16, 16, 512, 256, 256, 3, 3, 1, 1, 0, 0, 0, 34, 4, 5), 2, (25165824, 32, 192), (16, 16, 16, 512, 256, 256, 1, 1, 1, 0, 0, 0, 0, 36, 1, 5), (0, 64, 0)), None,
+                                     (('wino_tail', 16, 16, 16, 512, 256, 32, 2, False), None),
+                                     ((16, 16, 16, 512, 256, 256, 3, 3, 1, 1, 0, 0, 0, 34, 4, 5), 2, True, (25165824, 32, 192),
+                                      ((16, 16, 16, 512, 256, 256, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), 16, (16777216, 0)))),
+ (16, 16, 16, 512, 256, 256, 2, 1): (None, ((16, 16, 16, 512, 256, 256, 1, 1, 1, 0, 0, 0, 0, 36, 1, 5), (0, 64, 0)),
+                                     (('wino_tail', 16, 16, 16, 512, 256, 32, 2, True), ((16, 16, 16, 512, 256, 256, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), (16777216, 0))),
+                                     ((16, 16, 16, 512, 256, 256, 3, 3, 1, 1, 0, 0, 0, 34, 4, 5), 2, True, (25165824, 32, 192),
+                                      ((16, 16, 16, 512, 256, 256, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), 16, (16777216, 0)))),
+ (16, 16, 16, 512, 512, 512, 0, 0): (((16, 16, 16, 512, 512, 512, 3, 3, 1, 1, 0, 0, 0, 62, 4, 5), 1, (50331648, 32, 192), (16, 16, 16, 512, 512, 512, 1, 1, 1, 0, 0, 0, 0, 36, 1, 5), (0, 128, 0)),
+                                     None, (('wino_tail', 16, 16, 16, 512, 512, 32, 0, False), None),
+                                     ((16, 16, 16, 512, 512, 512, 3, 3, 1, 1, 0, 0, 0, 62, 4, 5), 1, True, (50331648, 32, 192), None)),
+ (16, 16, 16, 512, 512, 512, 0, 1): (((16, 16, 16, 512, 512, 512, 3, 3, 1, 1, 0, 0, 0, 62, 4, 5), 1, (50331648, 32, 192), (16, 16, 16, 512, 512, 512, 1, 1, 1, 0, 0, 0, 0, 36, 1, 5), (0, 128, 0)),
+                                     None, (('wino_tail', 16, 16, 16, 512, 512, 32, 0, True), None), ((16, 16, 16, 512, 512, 512, 3, 3, 1, 1, 0, 0, 0, 62, 4, 5), 1, True, (50331648, 32, 192), None)),
+ (16, 16, 16, 512, 512, 512, 1, 0): (((16, 16, 16, 512, 512, 512, 3, 3, 1, 1, 0, 0, 0, 62, 4, 5), 1, (50331648, 32, 192), (16, 16, 16, 512, 512, 512, 1, 1, 1, 0, 0, 0, 0, 36, 1, 5), (0, 128, 0)),
+                                     None, (('wino_tail', 16, 16, 16, 512, 512, 32, 1, False), None),
+                                     ((16, 16, 16, 512, 512, 512, 3, 3, 1, 1, 0, 0, 0, 62, 4, 5), 1, True, (50331648, 32, 192), None)),
+ (16, 16, 16, 512, 512, 512, 1, 1): (None, ((16, 16, 16, 512, 512, 512, 1, 1, 1, 0, 0, 0, 0, 36, 1, 5), (0, 128, 0)),
+                                     (('wino_tail', 16, 16, 16, 512, 512, 32, 1, True), ((16, 16, 16, 512, 512, 512, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), (33554432, 0))),
+                                     ((16, 16, 16, 512, 512, 512, 3, 3, 1, 1, 0, 0, 0, 62, 4, 5), 1, True, (50331648, 32, 192), None)),
+ (16, 16, 16, 512, 512, 512, 2, 0): (((16, 16, 16, 512, 512, 512, 3, 3, 1, 1, 0, 0, 0, 62, 4, 5), 1, (50331648, 32, 192), (16, 16, 16, 512, 512, 512, 1, 1, 1, 0, 0, 0, 0, 36, 1, 5), (0, 128, 0)),
+                                     None, (('wino_tail', 16, 16, 16, 512, 512, 32, 2, False), None),
+                                     ((16, 16, 16, 512, 512, 512, 3, 3, 1, 1, 0, 0, 0, 62, 4, 5), 1, True, (50331648, 32, 192), None)),
+ (16, 16, 16, 512, 512, 512, 2, 1): (None, ((16, 16, 16, 512, 512, 512, 1, 1, 1, 0, 0, 0, 0, 36, 1, 5), (0, 128, 0)),
+                                     (('wino_tail', 16, 16, 16, 512, 512, 32, 2, True), ((16, 16, 16, 512, 512, 512, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), (33554432, 0))),
+                                     ((16, 16, 16, 512, 512, 512, 3, 3, 1, 1, 0, 0, 0, 62, 4, 5), 1, True, (50331648, 32, 192), None)),
+ (16, 32, 32, 256, 256, 256, 0, 0): (((16, 32, 32, 256, 256, 256, 3, 3, 1, 1, 0, 0, 0, 62, 2, 5), 4, (33554432, 64, 128), (16, 32, 32, 256, 256, 256, 1, 1, 1, 0, 0, 0, 0, 37, 1, 5), (0, 128, 0)),
+                                     None, (('wino_tail', 16, 32, 32, 256, 256, 32, 0, False), None),
+                                     ((16, 32, 32, 256, 256, 256, 3, 3, 1, 1, 0, 0, 0, 62, 2, 5), 4, True, (33554432, 64, 128), None)),
+ (16, 32, 32, 256, 256, 256, 0, 1): (((16, 32, 32, 256, 256, 256, 3, 3, 1, 1, 0, 0, 0, 62, 2, 5), 4, (33554432, 64, 128), (16, 32, 32, 256, 256, 256, 1, 1, 1, 0, 0, 0, 0, 37, 1, 5), (0, 128, 0)),
+                                     None, (('wino_tail', 16, 32, 32, 256, 256, 32, 0, True), None), ((16, 32, 32, 256, 256, 256, 3, 3, 1, 1, 0, 0, 0, 62, 2, 5), 4, True, (33554432, 64, 128), None)),
+ (16, 32, 32, 256, 256, 256, 1, 0): (((16, 32, 32, 256, 256, 256, 3, 3, 1, 1, 0, 0, 0, 62, 2, 5), 4, (33554432, 64, 128), (16, 32, 32, 256, 256, 256, 1, 1, 1, 0, 0, 0, 0, 37, 1, 5), (0, 128, 0)),
+                                     None, (('wino_tail', 16, 32, 32, 256, 256, 32, 1, False), None),
+                                     ((16, 32, 32, 256, 256, 256, 3, 3, 1, 1, 0, 0, 0, 62, 2, 5), 4, True, (33554432, 64, 128), None)),
+ (16, 32, 32, 256, 256, 256, 1, 1): (((16, 32, 32, 256, 256, 256, 3, 3, 1, 1, 0, 0, 0, 62, 2, 5), 4, (33554432, 64, 128), (16, 32, 32, 256, 256, 256, 1, 1, 1, 0, 0, 0, 0, 37, 1, 5), (0, 128, 0)),
+                                     None, (('wino_tail', 16, 32, 32, 256, 256, 32, 1, True), None), ((16, 32, 32, 256, 256, 256, 3, 3, 1, 1, 0, 0, 0, 62, 2, 5), 4, True, (33554432, 64, 128), None)),
+ (16, 32, 32, 256, 256, 256, 2, 0): (((16, 32, 32, 256, 256, 256, 3, 3, 1, 1, 0, 0, 0, 62, 2, 5), 4, (33554432, 64, 128), (16, 32, 32, 256, 256, 256, 1, 1, 1, 0, 0, 0, 0, 37, 1, 5), (0, 128, 0)),
+                                     None, (('wino_tail', 16, 32, 32, 256, 256, 32, 2, False), None),
+                                     ((16, 32, 32, 256, 256, 256, 3, 3, 1, 1, 0, 0, 0, 62, 2, 5), 4, True, (33554432, 64, 128), None)),
+ (16, 32, 32, 256, 256, 256, 2, 1): (None, ((16, 32, 32, 256, 256, 256, 1, 1, 1, 0, 0, 0, 0, 37, 1, 5), (0, 128, 0)),
+                                     (('wino_tail', 16, 32, 32, 256, 256, 32, 2, True), ((16, 32, 32, 256, 256, 256, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), (67108864, 0))),
+                                     ((16, 32, 32, 256, 256, 256, 3, 3, 1, 1, 0, 0, 0, 62, 2, 5), 4, True, (33554432, 64, 128), None)),
+ (32, 8, 8, 512, 0, 1024, 0, 0): (((32, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 34, 2, 5), 1, (16777216, 32, 128), (32, 8, 8, 512, 0, 1024, 1, 1, 1, 0, 0, 0, 0, 36, 1, 5), (0, 64, 0)), None,
+                                  (('wino_tail', 32, 8, 8, 512, 0, 32, 0, False), None), ((32, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 34, 2, 5), 1, True, (16777216, 32, 128), None)),
+ (32, 8, 8, 512, 0, 1024, 0, 1): (((32, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 34, 2, 5), 1, (16777216, 32, 128), (32, 8, 8, 512, 0, 1024, 1, 1, 1, 0, 0, 0, 0, 36, 1, 5), (0, 64, 0)), None,
+                                  (('wino_tail', 32, 8, 8, 512, 0, 32, 0, True), None), ((32, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 34, 2, 5), 1, True, (16777216, 32, 128), None)),
+ (32, 8, 8, 512, 0, 1024, 1, 0): (((32, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 34, 2, 5), 1, (16777216, 32, 128), (32, 8, 8, 512, 0, 1024, 1, 1, 1, 0, 0, 0, 0, 36, 1, 5), (0, 64, 0)), None,
+                                  (('wino_tail', 32, 8, 8, 512, 0, 32, 1, False), None),
+                                  ((32, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 34, 2, 5), 1, True, (16777216, 32, 128), ((32, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), 16, (33554432, 0)))),
+ (32, 8, 8, 512, 0, 1024, 1, 1): (None, ((32, 8, 8, 512, 0, 1024, 1, 1, 1, 0, 0, 0, 0, 36, 1, 5), (0, 64, 0)),
+                                  (('wino_tail', 32, 8, 8, 512, 0, 32, 1, True), ((32, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), (33554432, 0))),
+                                  ((32, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 34, 2, 5), 1, True, (16777216, 32, 128), ((32, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), 16, (33554432, 0)))),
+ (32, 8, 8, 512, 0, 1024, 2, 0): (((32, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 34, 2, 5), 1, (16777216, 32, 128), (32, 8, 8, 512, 0, 1024, 1, 1, 1, 0, 0, 0, 0, 36, 1, 5), (0, 64, 0)), None,
+                                  (('wino_tail', 32, 8, 8, 512, 0, 32, 2, False), None),
+                                  ((32, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 34, 2, 5), 1, True, (16777216, 32, 128), ((32, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), 16, (33554432, 0)))),
+ (32, 8, 8, 512, 0, 1024, 2, 1): (None, ((32, 8, 8, 512, 0, 1024, 1, 1, 1, 0, 0, 0, 0, 36, 1, 5), (0, 64, 0)),
+                                  (('wino_tail', 32, 8, 8, 512, 0, 32, 2, True), ((32, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), (33554432, 0))),
+                                  ((32, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 34, 2, 5), 1, True, (16777216, 32, 128), ((32, 8, 8, 512, 0, 1024, 3, 3, 1, 1, 0, 0, 0, 0, 0, 5), 16, (33554432, 0))))}
+
+
+def _flat(v):
+    """a planner result with every descriptor replaced by the tuple of its fields"""
+    if isinstance(v, C.Structure):
+        return tuple(getattr(v, f[0]) for f in v._fields_)
+    if isinstance(v, (tuple, list)):
+        return tuple(_flat(e) for e in v)
+    return v
+
+
+def test_the_plans_of_the_resblocks_are_what_they_were():
+    """what blocks.py plans for a channel-changing ResBlock -- the grouped launch, the guest of the Winograd GEMM, the Winograd tail, the 3x3's own entry --
+    under WINOGRAD 0 / 1 / 2 with and without the tail, against the literal above: the seven blocks of cfg2, two other batches, two small shapes"""
+    from medfusion_amd import blocks as BLK
+    import torch
+    old = BLK.WINOGRAD, BLK.WINO_TAIL, BLK.CONV_PRECISION
+    got = {}
+    try:
+        BLK.CONV_PRECISION = 5
+        for n, h, w, c1, c2, co in PLAN_SNAPSHOT_SHAPES:
+            blk = BLK.BasicResBlock(2, c1 + c2, co, 3, 1, ("GROUP", {"num_groups": 32, "affine": True}), ("Swish", {}))
+            x1 = torch.empty((n, h, w, c1), device="meta")
+            x2 = torch.empty((n, h, w, c2), device="meta") if c2 else None
+            x = x1 if x2 is None else (x1, x2)
+            c3 = blk.basic_block.conv
+            for wg in (0, 1, 2):
+                for tail in (True, False):
+                    BLK.WINOGRAD, BLK.WINO_TAIL = wg, tail
+                    try:       # (plans and caches the entry, then refuses the launch: the tensors are not on a device)
+                        c3._forward_f16x2(x1, x2, n, h, w, c1, c2, None, 32, 1e-5, False)
+                    except RuntimeError:
+                        pass
+                    got[(n, h, w, c1, c2, co, wg, int(tail))] = _flat((blk._grouped(x), blk._wino_guest(x), c3.wino_tail_desc(x, 32),
+                                                                        c3._descs[("f16x2", n, h, w, c1, c2, 32, 5, wg)]))
+    finally:
+        BLK.WINOGRAD, BLK.WINO_TAIL, BLK.CONV_PRECISION = old
+    assert set(got) == set(PLAN_SNAPSHOT)
+    for key in sorted(got):
+        assert got[key] == PLAN_SNAPSHOT[key], key
+    # (the two entries the record of this snapshot quotes: one block on the Winograd GEMM's launch, one on the direct form's grouped launch)
+    g, wg_, tl, _ = PLAN_SNAPSHOT[(16, 8, 8, 1024, 512, 512, 1, 1)]
+    assert g is None and (wg_[0][13], wg_[0][14], wg_[1]) == (53, 4, (12582912, 16, 192)) and tl[1][1] == (8388608, 0)
+    g = PLAN_SNAPSHOT[(16, 32, 32, 256, 256, 256, 1, 1)][0]
+    assert (g[0][13], g[0][14], g[3][13], g[3][14]) == (62, 2, 37, 1)
+
+
 def _sweep_tools():
     import importlib.util
     from pathlib import Path
