@@ -477,6 +477,31 @@ typedef struct MfSolverArgs {
 int mf_solver_step_f32(const MfSolverArgs* a, void* stream);
 /* the same with mf_sched_step_blend_f32's select on x_t_out (coef[step] of the executed grid); x0_out / xT_out / x0_hist stay the estimates */
 int mf_solver_step_blend_f32(const MfSolverArgs* a, const MfSchedBlend* blend, void* stream);
+/* The trajectory of an inversion inside the solver step's launch (DDIM inversion / counterfactual editing; additive to ABI 250).  `traj` is a
+ * caller-owned [slots][n] buffer; the launch touches slot = slot0 + slot_stride * step, `step` being the index mf_solver_step_f32 resolves
+ * (*step_counter, *step_dev or a->step), so a replayed loop walks the buffer up (record) or down (keep) with no per-iteration pointer:
+ *   MF_TRAJ_RECORD  x_t_out[i] and traj[slot][i] receive the same value (mf_solver_step_f32's x_t_out, bit for bit);
+ *   MF_TRAJ_KEEP    x_t_out[i] = mask[sample][cell] ? mf_solver_step_f32's value : traj[slot][i]  (the mask of MfSchedBlend: != 0 regenerate).
+ * x0_out / xT_out / x0_hist stay the estimates.  A slot outside [0, slots) is refused with MF_EINVAL when the step is known on the host; a
+ * device-resolved step that lands outside touches no slot (nothing recorded; the kept cells become NaN).  traj must not overlap another tensor
+ * of the launch.  16-byte vectors when every tensor is 16-byte aligned, n % 4 == 0 and (KEEP) cells % 4 == 0 with a 4-byte aligned mask;
+ * element by element otherwise; any n. */
+enum { MF_TRAJ_RECORD = 0, MF_TRAJ_KEEP = 1 };
+typedef struct MfSolverTraj {
+  float* traj;          /* [slots][n], caller-owned */
+  const uint8_t* mask;  /* KEEP: [B][cells], != 0 regenerate, 0 keep; RECORD: NULL */
+  int64_t cells;        /* KEEP: spatial cells per sample */
+  int32_t channels;     /* KEEP: latent channels (the mask is broadcast over them) */
+  int32_t mode;         /* MF_TRAJ_* */
+  int32_t slot0;
+  int32_t slot_stride;  /* slot = slot0 + slot_stride * step */
+  int32_t slots;
+  int32_t reserved;     /* 0 */
+} MfSolverTraj;
+int mf_solver_step_traj_f32(const MfSolverArgs* a, const MfSolverTraj* tr, void* stream);
+/* out[n][cell] = (1 / C) * sum_c |a[n][c][cell] - b[n][c][cell]| on NCHW / NCDHW fp32, the channels summed in index order: the change map of
+ * an edit (out is [N][1][cells]). */
+int mf_absdiff_mean_c_f32(const float* a, const float* b, float* out, int N, int C, int64_t cells, void* stream);
 /* out[n][c][cell] = mask[n][cell] ? a[n][c][cell] : b[n][c][cell] on NCHW / NCDHW fp32, the per-cell mask broadcast over the C channels: the
  * pixel-space composite of inpainting and the un-fused form of the select above. */
 int mf_select_cells_f32(const uint8_t* mask, const float* a, const float* b, float* out, int N, int C, int64_t cells, void* stream);

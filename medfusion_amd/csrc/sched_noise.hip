@@ -129,6 +129,21 @@ __global__ void counter_add_kernel(int32_t* c, int32_t inc) {
   if (threadIdx.x == 0 && blockIdx.x == 0) *c += inc;
 }
 
+// out[n][cell] = (1 / C) * sum_c |a[n][c][cell] - b[n][c][cell]|, channels summed in index order: the change map of an edit
+__global__ __launch_bounds__(256) void absdiff_mean_c_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, long total, int C,
+                                                             long cells) {
+#pragma clang fp contract(off)
+  const float inv = 1.0f / (float)C;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long n = i / cells, cell = i - n * cells;
+    const float* pa = a + n * C * cells + cell;
+    const float* pb = b + n * C * cells + cell;
+    float s = 0.f;
+    for (int c = 0; c < C; ++c) s = s + fabsf(pa[c * cells] - pb[c * cells]);
+    out[i] = inv * s;
+  }
+}
+
 __device__ __forceinline__ void philox_round(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, uint32_t k0, uint32_t k1) {
   const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
   const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
@@ -242,11 +257,19 @@ __device__ __forceinline__ float solver_elem(const MfSolverStep& S, float xt, Es
   return s12 + p3;
 }
 
-template <bool BL>
-__global__ __launch_bounds__(256) void solver_step_kernel(const MfSolverArgs a, const MfSchedBlend bl, const long nq) {
+// The trajectory of an inversion (MfSolverTraj): slot = slot0 + slot_stride * step of a caller-owned [slots][n] buffer.  TR == MF_TRAJ_RECORD + 1:
+// the slot receives what x_t_out receives; TR == MF_TRAJ_KEEP + 1: the kept cells of x_t_out take the slot's values.  A slot outside [0, slots)
+// (only a device-resolved step can get here: the host refuses one it knows) is never touched: nothing is recorded, the kept cells say so (NaN).
+// TR == 0 compiles all of it away.
+template <bool BL, int TR>
+__global__ __launch_bounds__(256) void solver_step_kernel(const MfSolverArgs a, const MfSchedBlend bl, const MfSolverTraj tr, const long nq) {
 #pragma clang fp contract(off)
   const int step = a.step_counter ? *a.step_counter : a.step_dev ? *a.step_dev : a.step;
   const MfSolverStep S = a.table[step];
+  const long slot = TR ? (long)tr.slot0 + (long)tr.slot_stride * step : 0;
+  float* const tj = (TR && slot >= 0 && slot < tr.slots) ? tr.traj + slot * a.n : nullptr;
+  const long tper = TR == 2 ? tr.cells * tr.channels : 1;
+  const float lost = __builtin_nanf("");
   const BlendCoef k = BL ? blend_coef(bl, step) : BlendCoef{0.f, 0.f};
   const bool cfg = a.pred_uncond != nullptr;
   // a second-order row without a history buffer cannot be computed: the output says so (NaN) instead of reading through a null pointer
@@ -274,8 +297,16 @@ __global__ __launch_bounds__(256) void solver_step_kernel(const MfSolverArgs a, 
       xn = make_float4(blend_elem(xn.x, z.x, e.x, m.x != 0, k), blend_elem(xn.y, z.y, e.y, m.y != 0, k), blend_elem(xn.z, z.z, e.z, m.z != 0, k),
                        blend_elem(xn.w, z.w, e.w, m.w != 0, k));
     }
+    if (TR == 2) {   // (cells % 4 == 0 here, as for the blend)
+      const float4 kp = tj ? *reinterpret_cast<const float4*>(tj + i * 4) : make_float4(lost, lost, lost, lost);
+      const long b = (i * 4) / tper;
+      const long cell = (i * 4 - b * tper) % tr.cells;
+      const uchar4 m = *reinterpret_cast<const uchar4*>(tr.mask + b * tr.cells + cell);
+      xn = make_float4(m.x ? xn.x : kp.x, m.y ? xn.y : kp.y, m.z ? xn.z : kp.z, m.w ? xn.w : kp.w);
+    }
     const float4 x0v = make_float4(e0.x0, e1.x0, e2.x0, e3.x0);
     *reinterpret_cast<float4*>(a.x_t_out + i * 4) = xn;
+    if (TR == 1 && tj) *reinterpret_cast<float4*>(tj + i * 4) = xn;
     if (hcur) *reinterpret_cast<float4*>(hcur + i * 4) = x0v;
     if (a.x0_out) *reinterpret_cast<float4*>(a.x0_out + i * 4) = x0v;
     if (a.xT_out) *reinterpret_cast<float4*>(a.xT_out + i * 4) = make_float4(e0.xT, e1.xT, e2.xT, e3.xT);
@@ -288,7 +319,13 @@ __global__ __launch_bounds__(256) void solver_step_kernel(const MfSolverArgs a, 
       const long cell = (i - b * per) % bl.cells;
       xn = blend_elem(xn, bl.z0[i], bl.eps0[i], bl.mask[b * bl.cells + cell] != 0, k);
     }
+    if (TR == 2) {
+      const long b = i / tper;
+      const long cell = (i - b * tper) % tr.cells;
+      if (tr.mask[b * tr.cells + cell] == 0) xn = tj ? tj[i] : lost;
+    }
     a.x_t_out[i] = xn;
+    if (TR == 1 && tj) tj[i] = xn;
     if (hcur) hcur[i] = e.x0;
     if (a.x0_out) a.x0_out[i] = e.x0;
     if (a.xT_out) a.xT_out[i] = e.xT;
@@ -371,7 +408,9 @@ int sched_step_philox_launch(const MfSchedArgs* a, uint64_t seed, int32_t draw_b
   return check_launch("sched_step_philox");
 }
 
-int solver_step_launch(const MfSolverArgs* a, const MfSchedBlend* bl, void* stream) {
+const MfSolverTraj kNoTraj = {nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0};
+
+int solver_step_launch(const MfSolverArgs* a, const MfSchedBlend* bl, const MfSolverTraj* tr, void* stream) {
   MF_REQUIRE(a && a->x_t && a->pred && a->x_t_out && a->table && a->n > 0, MF_EINVAL, "solver_step: bad args");
   MF_REQUIRE(a->objective == 0 || a->objective == 1, MF_EINVAL, "solver_step: objective");
   MF_REQUIRE(!a->step_counter == !a->ticket, MF_EINVAL, "solver_step: step_counter and ticket come together");
@@ -385,17 +424,40 @@ int solver_step_launch(const MfSolverArgs* a, const MfSchedBlend* bl, void* stre
                  (uintptr_t)a->x0_hist;
   if (a->x0_hist && (a->n & 3)) al |= 4;   // (the second history slot starts n floats in)
   if (bl) al |= (uintptr_t)bl->z0 | (uintptr_t)bl->eps0 | ((uintptr_t)bl->mask & 3 ? 4 : 0) | (bl->cells & 3 ? 4 : 0);
+  if (tr) {
+    MF_REQUIRE(!bl, MF_EINVAL, "solver_step_traj: the trajectory and the blend do not combine");
+    MF_REQUIRE(tr->traj && tr->slots > 0 && (tr->mode == MF_TRAJ_RECORD || tr->mode == MF_TRAJ_KEEP), MF_EINVAL, "solver_step_traj: bad trajectory state");
+    if (tr->mode == MF_TRAJ_KEEP) {
+      MF_REQUIRE(tr->mask && tr->cells > 0 && tr->channels > 0, MF_EINVAL, "solver_step_traj: MF_TRAJ_KEEP needs mask, cells and channels");
+      MF_REQUIRE(a->n % (tr->cells * (int64_t)tr->channels) == 0, MF_EINVAL, "solver_step_traj: n is not a whole number of samples of channels x cells");
+      al |= ((uintptr_t)tr->mask & 3 ? 4 : 0) | (tr->cells & 3 ? 4 : 0);
+    }
+    if (!a->step_counter && !a->step_dev) {   // a host-known step: its slot is checked here (a device-resolved one inside the launch)
+      const int64_t slot = (int64_t)tr->slot0 + (int64_t)tr->slot_stride * a->step;
+      MF_REQUIRE(slot >= 0 && slot < tr->slots, MF_EINVAL, "solver_step_traj: slot %lld outside [0, %d)", (long long)slot, tr->slots);
+    }
+    // the trajectory must not overlap what the same launch reads or writes elsewhere
+    const float* const t0 = tr->traj;
+    const float* const t1 = t0 + (int64_t)tr->slots * a->n;
+    for (const float* p : others) MF_REQUIRE(!p || p + a->n <= t0 || p >= t1, MF_EINVAL, "solver_step_traj: traj overlaps another tensor");
+    MF_REQUIRE(!h0 || h1 <= t0 || h0 >= t1, MF_EINVAL, "solver_step_traj: traj overlaps x0_hist");
+    al |= (uintptr_t)tr->traj | ((a->n & 3) ? 4 : 0);   // (slot s starts s * n floats in)
+  }
   const long nq = (al & 15) ? 0 : a->n / 4;
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(MF_FAM_SCHED, s, (bl ? 12.0 : 9.0) * a->n, 4.0 * a->n * (bl ? 8 : 6));
   long blocks = ((nq ? nq : a->n) + 255) / 256;
   if (blocks > 1024) blocks = 1024;
-  if (bl) {
-    MF_LAUNCH(solver_step_kernel<true>, dim3((int)blocks), dim3(256), 0, s, *a, *bl, nq);
+  if (tr && tr->mode == MF_TRAJ_RECORD) {
+    MF_LAUNCH((solver_step_kernel<false, 1>), dim3((int)blocks), dim3(256), 0, s, *a, kNoBlend, *tr, nq);
+  } else if (tr) {
+    MF_LAUNCH((solver_step_kernel<false, 2>), dim3((int)blocks), dim3(256), 0, s, *a, kNoBlend, *tr, nq);
+  } else if (bl) {
+    MF_LAUNCH((solver_step_kernel<true, 0>), dim3((int)blocks), dim3(256), 0, s, *a, *bl, kNoTraj, nq);
   } else {
-    MF_LAUNCH(solver_step_kernel<false>, dim3((int)blocks), dim3(256), 0, s, *a, kNoBlend, nq);
+    MF_LAUNCH((solver_step_kernel<false, 0>), dim3((int)blocks), dim3(256), 0, s, *a, kNoBlend, kNoTraj, nq);
   }
-  return check_launch("solver_step");
+  return check_launch(tr ? "solver_step_traj" : "solver_step");
 }
 
 }  // namespace
@@ -427,13 +489,27 @@ int mf_sched_step_philox_blend_f32(const MfSchedArgs* a, uint64_t seed, int32_t 
   return sched_step_philox_launch(a, seed, draw_base, draw_stride, sample_offset, B, step_counter, ticket, bl, stream);
 }
 
-int mf_solver_step_f32(const MfSolverArgs* a, void* stream) { return solver_step_launch(a, nullptr, stream); }
+int mf_solver_step_f32(const MfSolverArgs* a, void* stream) { return solver_step_launch(a, nullptr, nullptr, stream); }
+
+int mf_solver_step_traj_f32(const MfSolverArgs* a, const MfSolverTraj* tr, void* stream) {
+  MF_REQUIRE(a && tr, MF_EINVAL, "solver_step_traj: bad args");
+  return solver_step_launch(a, nullptr, tr, stream);
+}
+
+int mf_absdiff_mean_c_f32(const float* a, const float* b, float* out, int N, int C, int64_t cells, void* stream) {
+  MF_REQUIRE(a && b && out && N > 0 && C > 0 && cells > 0, MF_EINVAL, "absdiff_mean_c: bad args");
+  const long total = (long)N * cells;
+  long blocks = (total + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  MF_LAUNCH(absdiff_mean_c_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, a, b, out, total, C, (long)cells);
+  return check_launch("absdiff_mean_c");
+}
 
 int mf_solver_step_blend_f32(const MfSolverArgs* a, const MfSchedBlend* bl, void* stream) {
   MF_REQUIRE(a, MF_EINVAL, "solver_step_blend: bad args");
   MF_REQUIRE(bl && bl->z0 && bl->eps0 && bl->mask && bl->coef && bl->cells > 0 && bl->channels > 0, MF_EINVAL, "solver_step_blend: bad blend state");
   MF_REQUIRE(a->n % (bl->cells * (int64_t)bl->channels) == 0, MF_EINVAL, "solver_step_blend: n is not a whole number of samples of channels x cells");
-  return solver_step_launch(a, bl, stream);
+  return solver_step_launch(a, bl, nullptr, stream);
 }
 
 int mf_gather_step_rows3_f32(const float* const* tables, const int64_t* row_lens, float* const* outs, int n_tables, const int64_t* cols, const int32_t* step_dev,

@@ -1176,6 +1176,25 @@ def solver_step(args: L.MfSolverArgs, blend: Optional[L.MfSchedBlend] = None, ou
         L.check(L.load().mf_solver_step_blend_f32(C.byref(args), C.byref(blend), stream()), "mf_solver_step_blend_f32")
 
 
+def solver_step_traj(args: L.MfSolverArgs, traj: L.MfSolverTraj, outputs=()) -> None:
+    """the solver step that records its x_t_out into, or takes its kept cells from, a slot of a trajectory buffer indexed by the step
+    (mf_solver_step_traj_f32).  `outputs` as in sched_step."""
+    _drop_outputs(outputs)
+    L.check(L.load().mf_solver_step_traj_f32(C.byref(args), C.byref(traj), stream()), "mf_solver_step_traj_f32")
+
+
+def absdiff_mean_c(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """[N,C,...] fp32 x 2 -> [N,1,...]: the mean over the channels of |a - b| (mf_absdiff_mean_c_f32)"""
+    _gpu(a, b)
+    if a.shape != b.shape or a.dim() < 3 or a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise ValueError(f"absdiff_mean_c: two fp32 [N,C,cells...] tensors of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    a, b = a.contiguous(), b.contiguous()
+    n, c = a.shape[0], a.shape[1]
+    out = torch.empty((n, 1, *a.shape[2:]), dtype=torch.float32, device=a.device)
+    L.check(L.load().mf_absdiff_mean_c_f32(a.data_ptr(), b.data_ptr(), out.data_ptr(), n, c, a.numel() // max(1, n * c), stream()), "mf_absdiff_mean_c_f32")
+    return out
+
+
 def gather_step_rows_multi(tables, step, cols: torch.Tensor):
     """gather_step_rows for up to three [S, NCOL, L_i] tables that share `cols` and the step, in ONE launch -> list of [B, L_i]"""
     _gpu(cols, *tables)

@@ -57,6 +57,14 @@ class MfSolverArgs(C.Structure):
                 ("clip_x0", C.c_int32), ("guidance_scale", C.c_float), ("n", C.c_int64)]
 
 
+TRAJ_RECORD, TRAJ_KEEP = 0, 1
+
+
+class MfSolverTraj(C.Structure):
+    _fields_ = [("traj", c_fp), ("mask", c_fp), ("cells", C.c_int64), ("channels", C.c_int32), ("mode", C.c_int32), ("slot0", C.c_int32),
+                ("slot_stride", C.c_int32), ("slots", C.c_int32), ("reserved", C.c_int32)]
+
+
 class MfGnFuse(C.Structure):
     _fields_ = [("gamma", c_fp), ("beta", c_fp), ("residual", c_fp), ("residual_pairs", c_fp), ("res_bound", c_fp), ("res_bound_slots", c_fp),
                 ("emb", c_fp), ("emb_bound", c_fp), ("out", c_fp), ("out_split", c_fp), ("out_bound", c_fp), ("rendezvous", c_fp), ("error_flag", c_fp),
@@ -152,6 +160,8 @@ _SIGS = {
     "mf_sched_step_philox_blend_f32": (_I, [C.POINTER(MfSchedArgs), _U64, C.c_int32, C.c_int32, _I64, _I, c_fp, c_fp, C.POINTER(MfSchedBlend), c_fp]),
     "mf_solver_step_f32": (_I, [C.POINTER(MfSolverArgs), c_fp]),
     "mf_solver_step_blend_f32": (_I, [C.POINTER(MfSolverArgs), C.POINTER(MfSchedBlend), c_fp]),
+    "mf_solver_step_traj_f32": (_I, [C.POINTER(MfSolverArgs), C.POINTER(MfSolverTraj), c_fp]),
+    "mf_absdiff_mean_c_f32": (_I, [c_fp, c_fp, c_fp, _I, _I, _I64, c_fp]),
     "mf_select_cells_f32": (_I, [c_fp, c_fp, c_fp, c_fp, _I, _I, _I64, c_fp]),
     "mf_mask_maxpool_u8": (_I, [c_fp, _I, c_fp, _I, _I, _I, _I, _I, _I, _I, c_fp]),
     "mf_image_ingress_u8": (_I, [c_fp, c_fp, _I, _I, _I, _I, c_fp]),

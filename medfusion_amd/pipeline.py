@@ -212,6 +212,14 @@ class DiffusionPipeline(nn.Module):
                               None if counter is None else counter.data_ptr(), None if counter is None else counter.data_ptr() + 4, None, int(step),
                               objective, int(bool(self.clip_x0)), float(guidance_scale), x_t.numel())
 
+    @staticmethod
+    def _solver_launch(args, blend, traj, outputs):
+        """one solver step: plain, with the inpainting blend, or (traj: an MfSolverTraj) recording / keeping a slot of an inversion's trajectory"""
+        if traj is None:
+            K.solver_step(args, blend, outputs=outputs)
+        else:
+            K.solver_step_traj(args, traj, outputs=outputs)
+
     # ------------------------------------------------------------------ the loop
     @torch.no_grad()
     def denoise(self, x_t, steps=None, condition=None, use_ddim=True, noise: Optional[NoiseSource] = None, trace=None, decode=True, use_graph=None,
@@ -231,9 +239,9 @@ class DiffusionPipeline(nn.Module):
         self._check_sampler(kwargs.get("sampler"), kwargs.get("spacing"), use_ddim, kwargs.get("cold_diffusion", False))
         return self._denoise_guarded(x_t, steps, condition, use_ddim, noise, trace, decode, use_graph, loop, progress_cb, 0, None, kwargs)
 
-    def _denoise_guarded(self, x_t, steps, condition, use_ddim, noise, trace, decode, use_graph, loop, progress_cb, start, blend, kwargs):
+    def _denoise_guarded(self, x_t, steps, condition, use_ddim, noise, trace, decode, use_graph, loop, progress_cb, start, blend, kwargs, traj=None, up=None):
         """denoise() proper: the loop under K.with_fused_fallback, whose re-run rewinds the noise source to the draw count at ENTRY (sample_from
-        enters after draw #0, so a re-run keeps eps0).  start / blend: see _denoise."""
+        enters after draw #0, so a re-run keeps eps0).  start / blend / traj / up: see _denoise."""
         if not x_t.is_cuda:
             raise RuntimeError("medfusion_amd.DiffusionPipeline runs on a ROCm device only (no CPU fallback)")
         with torch.cuda.device(x_t.device):   # (see sample())
@@ -260,12 +268,16 @@ class DiffusionPipeline(nn.Module):
                         user_cb(done, total)
 
             return K.with_fused_fallback(x_t.device, lambda: self._denoise(x_t, steps, condition, use_ddim, noise, trace, decode, use_graph, loop, progress_cb,
-                                                                           _start=start, _blend=blend, **dict(kwargs)), rewind)
+                                                                           _start=start, _blend=blend, _traj=traj, _up=up, **dict(kwargs)), rewind)
 
-    def _denoise(self, x_t, steps, condition, use_ddim, noise, trace, decode, use_graph, loop, progress_cb=None, _start=0, _blend=None, **kwargs):
+    def _denoise(self, x_t, steps, condition, use_ddim, noise, trace, decode, use_graph, loop, progress_cb=None, _start=0, _blend=None, _traj=None, _up=None,
+                 **kwargs):
         """_start: index of the first executed iteration of the full loop (sample_from: the loop runs on rev[_start:], recs[_start:] of the FULL
         timestep list and the embeddings of those timesteps).  _blend = (z0, eps0, mask uint8 [B,1,...]) or None: inpainting, the kept cells of
-        every iteration's next latent replaced inside the scheduler step's launch."""
+        every iteration's next latent replaced inside the scheduler step's launch.
+        _up = k (invert; a sampler, _start = 0, no blend): the loop runs UPWARD over timesteps[:k] -- iteration j evaluates the estimator at
+        timesteps[j] and takes row j of GaussianNoiseScheduler.inversion_records, k - 1 iterations.  _traj: an MfSolverTraj (a sampler, no blend):
+        every solver step records into / keeps from the slot its step indexes (mf_solver_step_traj_f32)."""
         K.SyncWords.reset(x_t.device)   # (the split-K counters of the convolutions: zero by invariant, re-zeroed once per loop for robustness)
         if "eta" in kwargs:
             raise TypeError("forward() got an unexpected keyword argument 'eta'")
@@ -296,7 +308,7 @@ class DiffusionPipeline(nn.Module):
             timesteps, steps = sch.loop_timesteps(steps, use_ddim, spacing)
         # (a deterministic sampler draws nothing inside the loop: any noise source replays)
         replayable = (trace is None and not cold_diffusion and (sampler is not None or noise is None or isinstance(noise, PhiloxDeviceNoise))
-                      and (steps is None or steps - _start >= 4))
+                      and (steps is None or (steps - _start if _up is None else _up - 1) >= 4))
         if loop is not None and loop not in ("cmdlist", "graph", "eager"):
             raise ValueError(f"loop={loop!r}: 'cmdlist', 'graph' or 'eager'")
         # precedence: loop= argument, use_graph= (True: graph, False: eager), MEDFUSION_LOOP in the environment, then the default
@@ -318,13 +330,15 @@ class DiffusionPipeline(nn.Module):
             recs = sch.step_records(timesteps, use_ddim)
             table = sch.upload_records(recs, dev)
         else:   # one MfSolverStep row per EXECUTED iteration: the first one is first-order wherever it sits in the grid
-            recs = sch.solver_records(timesteps, sampler, start=_start)
+            recs = sch.solver_records(timesteps, sampler, start=_start) if _up is None else sch.inversion_records(timesteps, sampler, stop=_up)
             table = sch.upload_solver_records(recs, dev)
         if noise is None:  # x_t supplied by the caller (interpolate): fresh source, draws start at 0
             noise = default_noise()
             noise.begin(B, dev)
-        rev = list(reversed(timesteps))
+        rev = list(reversed(timesteps)) if _up is None else list(timesteps[:_up - 1])   # (the loop's timesteps in execution order)
         blend = None
+        if (_traj is not None or _up is not None) and (sampler is None or _blend is not None or (_up is not None and _start)):
+            raise ValueError("a trajectory / an upward loop runs on a deterministic sampler, without a blend")
         if _start or _blend is not None:
             if cold_diffusion:
                 raise ValueError("cold_diffusion is not built for sample_from")
@@ -367,7 +381,7 @@ class DiffusionPipeline(nn.Module):
         hist = torch.empty((2, *x_t.shape), dtype=torch.float32, device=dev) if sampler == "dpmpp2m" else None
         if mode in ("graph", "cmdlist"):
             self._denoise_graph(x_t, rev, recs, table, condition, guidance_scale, un_cond, use_ddim, noise, objective, cmdlist=(mode == "cmdlist"),
-                                progress_cb=progress_cb, blend=blend, solver=None if sampler is None else (hist,))
+                                progress_cb=progress_cb, blend=blend, solver=None if sampler is None else (hist, _traj))
         elif sampler is not None:
             t_all = torch.tensor(rev, dtype=torch.float32, device=dev).reshape(-1, 1).expand(-1, B).contiguous()
             x0 = torch.empty_like(x_t) if (self.use_self_conditioning or trace is not None) else None
@@ -376,7 +390,7 @@ class DiffusionPipeline(nn.Module):
             for i in range(len(rev)):
                 pred, pred_uncond, _ = self._predict(x_t, t_all[i], condition, self_cond, guidance_scale, un_cond,
                                                      emb=None if emb_tab is None else (emb_tab[0], i, emb_tab[1], emb_tab[2], emb_tab[3]))
-                K.solver_step(self._solver_args(x_t, pred, pred_uncond, x0, hist, table, objective, guidance_scale, step=i), blend, outputs=(x_t, x0))
+                self._solver_launch(self._solver_args(x_t, pred, pred_uncond, x0, hist, table, objective, guidance_scale, step=i), blend, _traj, (x_t, x0))
                 self_cond = x0 if self.use_self_conditioning else None
                 if trace is not None:
                     trace.append((x0.clone(), x_t.clone()))
@@ -436,8 +450,8 @@ class DiffusionPipeline(nn.Module):
         DEVICE step counter: `t` is broadcast from a device table, the scheduler scalars come from the MfSchedStep table,
         the Philox draw index is draw_base + stride*step, and the graph advances the counter itself.  The last DDIM
         iteration still fills the (unused) DDIM noise buffer: counter-based draws do not shift any other draw.
-        solver = (x_0 history or None,): `table` holds MfSolverStep rows and the tail of an iteration is mf_solver_step_f32, which reads the
-        counter, advances it and draws nothing."""
+        solver = (x_0 history or None, MfSolverTraj or None): `table` holds MfSolverStep rows and the tail of an iteration is mf_solver_step_f32
+        (mf_solver_step_traj_f32 with a trajectory, whose slot the same counter indexes), which reads the counter, advances it and draws nothing."""
         from .noise import PhiloxDeviceNoise
 
         if solver is None and not isinstance(noise, PhiloxDeviceNoise):
@@ -473,7 +487,7 @@ class DiffusionPipeline(nn.Module):
                 K.broadcast_from_table(t_table, step_dev, t_cur)
             pred, pred_uncond, pred_var = self._predict(x_t, t_cur, condition, None if not self.use_self_conditioning else x0, g, un_cond, emb=emb)
             if solver is not None:
-                K.solver_step(self._solver_args(x_t, pred, pred_uncond, x0, solver[0], table, objective, g, counter=counter), blend, outputs=(x_t, x0))
+                self._solver_launch(self._solver_args(x_t, pred, pred_uncond, x0, solver[0], table, objective, g, counter=counter), blend, solver[1], (x_t, x0))
                 return pred
             if fused_tail:
                 a = L.MfSchedArgs(x_t.data_ptr(), pred.data_ptr(), None if pred_uncond is None else pred_uncond.data_ptr(),
@@ -501,7 +515,7 @@ class DiffusionPipeline(nn.Module):
                     K.broadcast_from_table(t_table, step_dev, t_cur)
                 pred, pu, pv = self._predict(x_t, t_cur, condition, None, g, un_cond, emb=emb)
                 if solver is not None:
-                    K.solver_step(self._solver_args(x_t, pred, pu, x0, solver[0], table, objective, g, counter=counter), blend, outputs=(x_t, x0))
+                    self._solver_launch(self._solver_args(x_t, pred, pu, x0, solver[0], table, objective, g, counter=counter), blend, solver[1], (x_t, x0))
                     return
                 noise.draw_indexed(n_post, base, stride, step_dev)
                 if use_ddim:
@@ -750,6 +764,129 @@ class DiffusionPipeline(nn.Module):
                 pix = (mask > 0.5) if mask.is_floating_point() else (mask != 0)
                 out = K.select_cells(pix.to(torch.uint8).contiguous(), out, x)
             return out
+
+    # ------------------------------------------------------------------ inversion and counterfactual editing
+    def _input_latent(self, x, is_latent, encode_noise):
+        """x -> z0 as sample_from makes it: the latent itself, or latent_embedder.encode(x) and 2 z0 - 1 with do_input_centering"""
+        x = x.to(torch.float32).contiguous()
+        if is_latent:
+            return x
+        z0 = x if self.latent_embedder is None else self.latent_embedder.encode(x, noise=encode_noise)
+        if self.do_input_centering:   # 2 * x_0 - 1 (diffusion_pipeline.py:90), rounded like the reference's two operations
+            two = torch.full((z0.shape[0],), 2.0, dtype=torch.float32, device=x.device)
+            z0 = K.rows_axpby(z0, two, torch.ones_like(z0), torch.full_like(two, -1.0))
+        return z0.contiguous()
+
+    def _inversion_args(self, who, steps, sampler, spacing, strength, kwargs):
+        """the argument rules invert() and edit() share, checked before anything touches the device -> (timesteps, k)"""
+        if "eta" in kwargs:
+            raise TypeError("forward() got an unexpected keyword argument 'eta'")
+        if kwargs.pop("cold_diffusion", False):
+            raise ValueError(f"cold_diffusion is not built for {who}")
+        if kwargs:
+            raise TypeError(f"forward() got an unexpected keyword argument '{next(iter(kwargs))}'")
+        if sampler is None:
+            raise ValueError(f"{who} needs a deterministic sampler ('ddim0' or 'dpmpp2m'): the stochastic loop has no upward form")
+        self._check_sampler(sampler, spacing, True, False)
+        timesteps, _ = self.noise_scheduler.loop_timesteps(steps, True, spacing)
+        _, k = self._strength_span(len(timesteps), strength)
+        if k < 2:
+            raise ValueError(f"strength={strength} of {len(timesteps)} iterations spans one grid point: an inversion runs at least one upward iteration")
+        return timesteps, k
+
+    @staticmethod
+    def _quiet_noise(noise, B, dev):
+        """the source the solver loops carry and never draw from: the caller's, or a fixed-key one (taking no key from torch's generator)"""
+        if noise is None:
+            from .noise import PhiloxDeviceNoise
+            noise = PhiloxDeviceNoise(0)
+            noise.begin(B, dev)
+        elif not hasattr(noise, "draw_index"):
+            noise.begin(B, dev)
+        return noise
+
+    def _invert_latent(self, z0, k, steps, sampler, spacing, condition, guidance_scale, un_cond, noise, trace, loop, use_graph, progress_cb):
+        """the k - 1 upward iterations from z0 -> (latent at ts[k-1], trajectory buffer [k + 1][...]).  The buffer's slots 0 AND 1 hold z0, slot
+        j + 1 the latent at ts[j]: the upward step j records slot 2 + j, and the downward loop of edit() -- whose step i produces the latent at
+        ts[k-2-i], and z0 once more on its last iteration -- keeps from slot k - 1 - i, both linear in the device step counter."""
+        traj = torch.empty((k + 1, *z0.shape), dtype=torch.float32, device=z0.device)
+        traj[0].copy_(z0)
+        traj[1].copy_(z0)
+        tr = L.MfSolverTraj(traj.data_ptr(), None, 0, 0, L.TRAJ_RECORD, 2, 1, k + 1, 0)
+        top = self._denoise_guarded(z0, steps, condition, True, noise, trace, False, use_graph, loop, progress_cb, 0, None,
+                                    dict(guidance_scale=guidance_scale, un_cond=un_cond, sampler=sampler, spacing=spacing), traj=tr, up=k)
+        return top, traj
+
+    @torch.no_grad()
+    def invert(self, x, condition=None, *, steps=None, sampler="ddim0", spacing=None, strength=1.0, is_latent=False, guidance_scale=1.0, un_cond=None,
+               loop=None, use_graph=None, progress_cb=None, trace=None, return_trajectory=False, encode_noise: Optional[NoiseSource] = None,
+               noise: Optional[NoiseSource] = None, **kwargs):
+        """DDIM inversion: the probability-flow ODE of a deterministic sampler carried UPWARD from a given image (or latent) to its noise code.
+        A composition of the reference's own functions: the training front end (diffusion_pipeline.py:84-90) for z0, then per iteration
+        forward()'s x_0 / x_T estimates at ts[j] and, for "ddim0", GaussianNoiseScheduler.estimate_x_t(x_0_est, ts[j+1], x_T=x_T_est)
+        (gaussian_scheduler.py:61-77); "dpmpp2m" takes the 2M rows with negative h (GaussianNoiseScheduler.inversion_records).
+          ts = the EXECUTED grid of (steps, spacing), ascending; k = min(len, int(strength * len + 0.5)) grid points are covered (the strength
+          rule of sample_from), k - 1 iterations run, z0 is taken as the state at ts[0]; the result is the latent at ts[k-1].
+          return_trajectory=True: also [k][...], the latents at ts[0] .. ts[k-1] (slot 0 is z0).
+        All three loop forms (the replayed ones from 4 iterations on), hoisted embeddings of the ascending timesteps, guidance as in denoise().
+        Nothing is drawn: `noise` (optional) is carried, its draw_index unchanged; without it torch's generator is not advanced either (the
+        encoder's draw comes from `encode_noise`, as in sample_from).  sampler=None and cold_diffusion=True raise ValueError, `eta` TypeError."""
+        timesteps, k = self._inversion_args("invert", steps, sampler, spacing, strength, kwargs)
+        if not x.is_cuda:
+            raise RuntimeError("medfusion_amd.DiffusionPipeline runs on a ROCm device only (no CPU fallback)")
+        with torch.cuda.device(x.device):
+            z0 = self._input_latent(x, is_latent, encode_noise)
+            noise = self._quiet_noise(noise, z0.shape[0], z0.device)
+            top, traj = self._invert_latent(z0, k, steps, sampler, spacing, condition, guidance_scale, un_cond, noise, trace, loop, use_graph, progress_cb)
+            return (top, traj[1:]) if return_trajectory else top
+
+    @torch.no_grad()
+    def edit(self, x, target_condition, *, source_condition=None, strength=1.0, steps=None, sampler="ddim0", spacing=None, guidance_scale=1.0,
+             source_guidance_scale=1.0, un_cond=None, mask=None, composite=False, is_latent=False, decode=True, return_map=False, loop=None, use_graph=None,
+             progress_cb=None, encode_noise: Optional[NoiseSource] = None, noise: Optional[NoiseSource] = None, **kwargs):
+        """Counterfactual editing: "this image, as the model would draw it under `target_condition`".  invert() under `source_condition` /
+        `source_guidance_scale`, recording the trajectory; then the LAST k iterations of the deterministic sampler's loop (denoise's, from
+        iteration len - k) from the inverted latent under `target_condition` / `guidance_scale`.  Nothing is drawn.
+          mask (the conventions of sample_from: 1 / True = regenerate, per latent cell or at image resolution): after every downward iteration
+          the kept cells take the RECORDED latent at the timestep just produced -- the trajectory the regenerated cells left from, not a
+          re-noised copy -- and z0 after the last one, inside the solver step's launch: the kept cells of the final latent are z0 bit for bit.
+          composite=True (image input, image-resolution mask): where(mask, decoded, x).
+          return_map=True (image input, decode=True): also [B, 1, ...], the mean over the channels of |result - x|.
+        progress_cb(done, total) counts both passes: total = 2 k - 1."""
+        timesteps, k = self._inversion_args("edit", steps, sampler, spacing, strength, kwargs)
+        if composite and (is_latent or mask is None):
+            raise ValueError("composite=True needs an image input and an image-resolution mask")
+        if return_map and (is_latent or not decode):
+            raise ValueError("return_map=True compares the decoded result with the input image: an image input and decode=True")
+        if not x.is_cuda:
+            raise RuntimeError("medfusion_amd.DiffusionPipeline runs on a ROCm device only (no CPU fallback)")
+        dev = x.device
+        with torch.cuda.device(dev):
+            x = x.to(torch.float32).contiguous()
+            if mask is not None:
+                if mask.shape[0] != x.shape[0]:
+                    raise ValueError(f"mask of shape {tuple(mask.shape)}: one mask per sample ({x.shape[0]})")
+                mask = mask.to(dev)
+            z0 = self._input_latent(x, is_latent, encode_noise)
+            cmask, at_image = (None, False) if mask is None else self._cell_mask(mask, z0.shape, None if is_latent else x.shape)
+            if composite and not at_image:
+                raise ValueError("composite=True needs an image input and an image-resolution mask")
+            noise = self._quiet_noise(noise, z0.shape[0], dev)
+            total = 2 * k - 1
+            up_cb = None if progress_cb is None else (lambda done, _t: progress_cb(done, total))
+            down_cb = None if progress_cb is None else (lambda done, _t: progress_cb(k - 1 + done, total))
+            top, traj = self._invert_latent(z0, k, steps, sampler, spacing, source_condition, source_guidance_scale, un_cond, noise, None, loop, use_graph, up_cb)
+            keep = None
+            if cmask is not None:
+                cells = z0.numel() // (z0.shape[0] * z0.shape[1])
+                keep = L.MfSolverTraj(traj.data_ptr(), cmask.data_ptr(), cells, z0.shape[1], L.TRAJ_KEEP, k - 1, -1, k + 1, 0)
+                keep._keep = (traj, cmask)
+            out = self._denoise_guarded(top, steps, target_condition, True, noise, None, decode, use_graph, loop, down_cb, len(timesteps) - k, None,
+                                        dict(guidance_scale=guidance_scale, un_cond=un_cond, sampler=sampler, spacing=spacing), traj=keep)
+            if composite:
+                pix = (mask > 0.5) if mask.is_floating_point() else (mask != 0)
+                out = K.select_cells(pix.to(torch.uint8).contiguous(), out, x)
+            return (out, K.absdiff_mean_c(out, x)) if return_map else out
 
     @torch.no_grad()
     def interpolate(self, img1, img2, i=None, condition=None, lam=0.5, noise: Optional[NoiseSource] = None, **kwargs):

@@ -162,6 +162,50 @@ class GaussianNoiseScheduler(BasicNoiseScheduler):
             recs.append(r)
         return recs
 
+    def inversion_records(self, timesteps: List[int], sampler: str, stop: Optional[int] = None) -> List[L.MfSolverStep]:
+        """The UPWARD rows of a deterministic sampler (DDIM inversion): the probability-flow ODE carried from the grid's lowest timestep towards
+        noise.  k = stop or len(timesteps); ts = timesteps[:k] ascending; one row per executed iteration j = 0 .. k-2: the estimator is evaluated
+        at t = ts[j] (sqrt_recip_ac / sqrt_recipm1_ac at t, as in solver_records) and the row produces the latent at tn = ts[j+1].  The clean latent
+        is taken as the state at ts[0].  No MF_SOLVER_FINAL row.
+          "ddim0"   MF_SOLVER_DDIM0 with B = sqrt_alphas_cumprod[tn], A = sqrt_one_minus_alphas_cumprod[tn] (the fp32 tables): the reference's
+                    estimate_x_t(x_0_est, tn, x_T=x_T_est), gaussian_scheduler.py:61-77;
+          "dpmpp2m" solver_records' exponential-integrator formulas with h = lambda[tn] - lambda[t] < 0; the first row MF_SOLVER_ORDER1, the rest
+                    MF_SOLVER_ORDER2 with r = h_prev / h; fp64, rounded to fp32 once."""
+        if sampler not in self.SAMPLERS:
+            raise ValueError(f"sampler={sampler!r}: one of {self.SAMPLERS}")
+        k = len(timesteps) if stop is None else int(stop)
+        if not 2 <= k <= len(timesteps):
+            raise ValueError(f"stop={k} of {len(timesteps)} timesteps: an inversion runs at least one iteration (two grid points)")
+        ts = [int(t) for t in timesteps[:k]]
+        if any(b <= a for a, b in zip(ts, ts[1:])):
+            raise ValueError("inversion needs strictly increasing timesteps (a repeated timestep has h = 0): steps <= T")
+        tb = self.host_tables()
+        ac = tb["alphas_cumprod"].to(torch.float64)
+        alpha, sigma = torch.sqrt(ac), torch.sqrt(1 - ac)
+        lam = torch.log(alpha / sigma)
+        recs, h_prev = [], None
+        for j in range(k - 1):
+            t, tn = ts[j], ts[j + 1]
+            r = L.MfSolverStep()
+            r.sqrt_recip_ac = float(tb["sqrt_recip_alphas_cumprod"][t])
+            r.sqrt_recipm1_ac = float(tb["sqrt_recipm1_alphas_cumprod"][t])
+            r.t, r.reserved = t, 0
+            r.A = r.B = r.C = 0.0
+            if sampler == "ddim0":
+                r.B, r.A, r.mode = float(tb["sqrt_alphas_cumprod"][tn]), float(tb["sqrt_one_minus_alphas_cumprod"][tn]), L.SOLVER_DDIM0
+            else:
+                h = float(lam[tn] - lam[t])
+                e = -float(alpha[tn]) * math.expm1(-h)
+                r.A = float(sigma[tn] / sigma[t])
+                if h_prev is None:
+                    r.B, r.mode = e, L.SOLVER_ORDER1
+                else:
+                    c = 1.0 / (2.0 * (h_prev / h))
+                    r.B, r.C, r.mode = e * (1.0 + c), -e * c, L.SOLVER_ORDER2
+                h_prev = h
+            recs.append(r)
+        return recs
+
     @staticmethod
     def upload_solver_records(recs: List[L.MfSolverStep], device) -> torch.Tensor:
         arr = (L.MfSolverStep * len(recs))(*recs)
