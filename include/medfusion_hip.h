@@ -477,6 +477,30 @@ typedef struct MfSolverArgs {
 int mf_solver_step_f32(const MfSolverArgs* a, void* stream);
 /* the same with mf_sched_step_blend_f32's select on x_t_out (coef[step] of the executed grid); x0_out / xT_out / x0_hist stay the estimates */
 int mf_solver_step_blend_f32(const MfSolverArgs* a, const MfSchedBlend* blend, void* stream);
+/* The stochastic solver step (few-step stochastic sampling; additive to ABI 250): DDIM at eta = 1 on any grid and SDE-DPM-Solver++(2M) in
+ * data-prediction form.  Front half and deterministic back half are mf_solver_step_f32's exactly (same rounding, same history slots, same three
+ * sources of the step index, same ticket); then
+ *   x_t_out = det + scale[step] * eps      (the product rounded on its own, then one add; an MF_SOLVER_FINAL row draws and adds nothing)
+ * and, with `blend`, mf_solver_step_blend_f32's select AFTER the noise.  eps is either
+ *   noise != NULL  the caller's draw: element i of the launch reads noise[step * noise_step_stride + i] (stride 0: one [n] buffer; n: a bank); any n,
+ *                  16-byte vectors when everything is aligned (noise and a stride that is a multiple of 4 included), element by element otherwise;
+ *   noise == NULL  generated in registers: the values mf_philox_normal_f32 writes for (seed, draw = draw_base + draw_stride * step, rows
+ *                  sample_offset .. + B).  Refused (MF_EUNSUPPORTED) where that function refuses -- elements per sample not a multiple of 4 -- and
+ *                  where the launch could not run on 16-byte vectors (an unaligned tensor; a blend whose cells are not a multiple of 4).
+ * `step` is the index the deterministic part resolves, so a replayed command list or graph needs no per-iteration argument.  No host
+ * synchronisation, no allocation, capture-safe, one launch. */
+typedef struct MfSolverNoise {
+  const float* scale;        /* device table of fp32 noise scales, one per executed iteration */
+  const float* noise;        /* the caller's draw, or NULL: Philox inside the launch */
+  int64_t noise_step_stride; /* elements between consecutive steps in `noise` (0: the same buffer each step) */
+  uint64_t seed;             /* Philox form: the key of mf_philox_normal_f32 */
+  int64_t sample_offset;     /* Philox form: global index of row 0 */
+  int32_t draw_base;
+  int32_t draw_stride;       /* draw = draw_base + draw_stride * step */
+  int32_t B;                 /* Philox form: samples in the launch (n / B elements each) */
+  int32_t reserved;          /* 0 */
+} MfSolverNoise;
+int mf_solver_step_noise_f32(const MfSolverArgs* a, const MfSolverNoise* nz, const MfSchedBlend* blend_or_null, void* stream);
 /* The trajectory of an inversion inside the solver step's launch (DDIM inversion / counterfactual editing; additive to ABI 250).  `traj` is a
  * caller-owned [slots][n] buffer; the launch touches slot = slot0 + slot_stride * step, `step` being the index mf_solver_step_f32 resolves
  * (*step_counter, *step_dev or a->step), so a replayed loop walks the buffer up (record) or down (keep) with no per-iteration pointer:

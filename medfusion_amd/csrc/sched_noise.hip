@@ -342,6 +342,97 @@ __global__ __launch_bounds__(256) void solver_step_kernel(const MfSolverArgs a, 
   }
 }
 
+// The stochastic solver step (DDIM eta = 1 on any grid, SDE-DPM-Solver++(2M)): solver_step_kernel's front half and deterministic back half, then
+// x_t_out = det + scale[step] * eps with the product rounded on its own.  eps is a caller-supplied draw (slot step * eps_step_stride of a bank) or,
+// PH, the Philox quad of philox_normal_kernel for draw = draw_base + draw_stride * step, generated in registers (then nq == n / 4: the host refuses
+// anything else).  An MF_SOLVER_FINAL row draws nothing and adds nothing.  No trajectory.
+struct SolverNoiseP { const float* scale; const float* eps; long eps_step_stride; uint32_t seed_lo, seed_hi; int draw_base, draw_stride; long sample_offset, quads_per_sample; };
+
+__device__ __forceinline__ float noise_elem(float det, float sc, float eps) {
+#pragma clang fp contract(off)
+  const float p = sc * eps;
+  return det + p;
+}
+
+template <bool BL, bool PH>
+__global__ __launch_bounds__(256) void solver_step_noise_kernel(const MfSolverArgs a, const MfSchedBlend bl, const SolverNoiseP nz, const long nq) {
+#pragma clang fp contract(off)
+  const int step = a.step_counter ? *a.step_counter : a.step_dev ? *a.step_dev : a.step;
+  const MfSolverStep S = a.table[step];
+  const bool draws = S.mode != MF_SOLVER_FINAL;
+  const float sc = draws ? nz.scale[step] : 0.f;
+  const uint32_t draw = (uint32_t)(nz.draw_base + nz.draw_stride * step);
+  const float* eps = (!PH && draws) ? nz.eps + (long)step * nz.eps_step_stride : nullptr;
+  const BlendCoef k = BL ? blend_coef(bl, step) : BlendCoef{0.f, 0.f};
+  const bool cfg = a.pred_uncond != nullptr;
+  const bool hist = S.mode == MF_SOLVER_ORDER2 && a.x0_hist;
+  const float missing = (S.mode == MF_SOLVER_ORDER2 && !a.x0_hist) ? __builtin_nanf("") : 0.f;
+  const float* hprev = a.x0_hist ? a.x0_hist + (long)((step + 1) & 1) * a.n : nullptr;
+  float* hcur = a.x0_hist ? a.x0_hist + (long)(step & 1) * a.n : nullptr;
+  const long stride = (long)gridDim.x * blockDim.x;
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long per = BL ? bl.cells * bl.channels : 1;
+  for (long i = tid; i < nq; i += stride) {
+    const float4 xt = *reinterpret_cast<const float4*>(a.x_t + i * 4), pr = *reinterpret_cast<const float4*>(a.pred + i * 4);
+    const float4 pu = cfg ? *reinterpret_cast<const float4*>(a.pred_uncond + i * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 hp = hist ? *reinterpret_cast<const float4*>(hprev + i * 4) : make_float4(missing, missing, missing, missing);
+    const Estimate e0 = estimate_elem(cfg, a.guidance_scale, a.objective, a.clip_x0, S.sqrt_recip_ac, S.sqrt_recipm1_ac, xt.x, pr.x, pu.x);
+    const Estimate e1 = estimate_elem(cfg, a.guidance_scale, a.objective, a.clip_x0, S.sqrt_recip_ac, S.sqrt_recipm1_ac, xt.y, pr.y, pu.y);
+    const Estimate e2 = estimate_elem(cfg, a.guidance_scale, a.objective, a.clip_x0, S.sqrt_recip_ac, S.sqrt_recipm1_ac, xt.z, pr.z, pu.z);
+    const Estimate e3 = estimate_elem(cfg, a.guidance_scale, a.objective, a.clip_x0, S.sqrt_recip_ac, S.sqrt_recipm1_ac, xt.w, pr.w, pu.w);
+    float4 xn = make_float4(solver_elem(S, xt.x, e0, hp.x), solver_elem(S, xt.y, e1, hp.y), solver_elem(S, xt.z, e2, hp.z), solver_elem(S, xt.w, e3, hp.w));
+    if (draws) {
+      float4 ep;
+      if (PH) {
+        const long b = i / nz.quads_per_sample;
+        ep = philox_quad((uint32_t)(i - b * nz.quads_per_sample), (uint32_t)(nz.sample_offset + b), draw, nz.seed_lo, nz.seed_hi);
+      } else {
+        ep = *reinterpret_cast<const float4*>(eps + i * 4);
+      }
+      xn = make_float4(noise_elem(xn.x, sc, ep.x), noise_elem(xn.y, sc, ep.y), noise_elem(xn.z, sc, ep.z), noise_elem(xn.w, sc, ep.w));
+    }
+    if (BL) {   // (cells % 4 == 0 here: a quad lies inside one channel plane, its four cells are consecutive mask bytes)
+      const float4 z = *reinterpret_cast<const float4*>(bl.z0 + i * 4), e = *reinterpret_cast<const float4*>(bl.eps0 + i * 4);
+      const long b = (i * 4) / per;
+      const long cell = (i * 4 - b * per) % bl.cells;
+      const uchar4 m = *reinterpret_cast<const uchar4*>(bl.mask + b * bl.cells + cell);
+      xn = make_float4(blend_elem(xn.x, z.x, e.x, m.x != 0, k), blend_elem(xn.y, z.y, e.y, m.y != 0, k), blend_elem(xn.z, z.z, e.z, m.z != 0, k),
+                       blend_elem(xn.w, z.w, e.w, m.w != 0, k));
+    }
+    const float4 x0v = make_float4(e0.x0, e1.x0, e2.x0, e3.x0);
+    *reinterpret_cast<float4*>(a.x_t_out + i * 4) = xn;
+    if (hcur) *reinterpret_cast<float4*>(hcur + i * 4) = x0v;
+    if (a.x0_out) *reinterpret_cast<float4*>(a.x0_out + i * 4) = x0v;
+    if (a.xT_out) *reinterpret_cast<float4*>(a.xT_out + i * 4) = make_float4(e0.xT, e1.xT, e2.xT, e3.xT);
+  }
+  if (!PH) {   // (the Philox form runs on whole quads only)
+    for (long i = nq * 4 + tid; i < a.n; i += stride) {
+      const Estimate e = estimate_elem(cfg, a.guidance_scale, a.objective, a.clip_x0, S.sqrt_recip_ac, S.sqrt_recipm1_ac, a.x_t[i], a.pred[i], cfg ? a.pred_uncond[i] : 0.f);
+      float xn = solver_elem(S, a.x_t[i], e, hist ? hprev[i] : missing);
+      if (draws) xn = noise_elem(xn, sc, eps[i]);
+      if (BL) {
+        const long b = i / per;
+        const long cell = (i - b * per) % bl.cells;
+        xn = blend_elem(xn, bl.z0[i], bl.eps0[i], bl.mask[b * bl.cells + cell] != 0, k);
+      }
+      a.x_t_out[i] = xn;
+      if (hcur) hcur[i] = e.x0;
+      if (a.x0_out) a.x0_out[i] = e.x0;
+      if (a.xT_out) a.xT_out[i] = e.xT;
+    }
+  }
+  if (a.step_counter) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const unsigned old = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (old + 1u == gridDim.x) {   // the last workgroup: every other one has read *step_counter (before its own ticket)
+        __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(a.step_counter, step + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+}
+
 // up to three gathers of the rows of loop iteration `step` in one launch (blockIdx.y = which): gather_step_rows_kernel's work for the
 // embedding rows, the local-embedder rows and their bounds, which share `cols` and the step
 struct GatherSeg { const float* table; float* out; long row_len; };
@@ -410,7 +501,8 @@ int sched_step_philox_launch(const MfSchedArgs* a, uint64_t seed, int32_t draw_b
 
 const MfSolverTraj kNoTraj = {nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0};
 
-int solver_step_launch(const MfSolverArgs* a, const MfSchedBlend* bl, const MfSolverTraj* tr, void* stream) {
+// the argument rules every solver step shares; *al_out: the OR of everything that must be 16-byte aligned for the vector path
+int solver_args_check(const MfSolverArgs* a, const MfSchedBlend* bl, uintptr_t* al_out) {
   MF_REQUIRE(a && a->x_t && a->pred && a->x_t_out && a->table && a->n > 0, MF_EINVAL, "solver_step: bad args");
   MF_REQUIRE(a->objective == 0 || a->objective == 1, MF_EINVAL, "solver_step: objective");
   MF_REQUIRE(!a->step_counter == !a->ticket, MF_EINVAL, "solver_step: step_counter and ticket come together");
@@ -424,6 +516,17 @@ int solver_step_launch(const MfSolverArgs* a, const MfSchedBlend* bl, const MfSo
                  (uintptr_t)a->x0_hist;
   if (a->x0_hist && (a->n & 3)) al |= 4;   // (the second history slot starts n floats in)
   if (bl) al |= (uintptr_t)bl->z0 | (uintptr_t)bl->eps0 | ((uintptr_t)bl->mask & 3 ? 4 : 0) | (bl->cells & 3 ? 4 : 0);
+  *al_out = al;
+  return MF_OK;
+}
+
+int solver_step_launch(const MfSolverArgs* a, const MfSchedBlend* bl, const MfSolverTraj* tr, void* stream) {
+  uintptr_t al = 0;
+  const int rc = solver_args_check(a, bl, &al);
+  if (rc) return rc;
+  const float* const h0 = a->x0_hist;
+  const float* const h1 = h0 ? h0 + 2 * a->n : nullptr;
+  const float* const others[] = {a->x_t, a->pred, a->pred_uncond, a->x_t_out, a->x0_out, a->xT_out};
   if (tr) {
     MF_REQUIRE(!bl, MF_EINVAL, "solver_step_traj: the trajectory and the blend do not combine");
     MF_REQUIRE(tr->traj && tr->slots > 0 && (tr->mode == MF_TRAJ_RECORD || tr->mode == MF_TRAJ_KEEP), MF_EINVAL, "solver_step_traj: bad trajectory state");
@@ -458,6 +561,42 @@ int solver_step_launch(const MfSolverArgs* a, const MfSchedBlend* bl, const MfSo
     MF_LAUNCH((solver_step_kernel<false, 0>), dim3((int)blocks), dim3(256), 0, s, *a, kNoBlend, kNoTraj, nq);
   }
   return check_launch(tr ? "solver_step_traj" : "solver_step");
+}
+
+int solver_step_noise_launch(const MfSolverArgs* a, const MfSolverNoise* nz, const MfSchedBlend* bl, void* stream) {
+  uintptr_t al = 0;
+  const int rc = solver_args_check(a, bl, &al);
+  if (rc) return rc;
+  MF_REQUIRE(nz->scale, MF_EINVAL, "solver_step_noise: the table of noise scales is missing");
+  const bool philox = nz->noise == nullptr;
+  long qps = 0;
+  if (philox) {
+    MF_REQUIRE(nz->B > 0 && a->n % nz->B == 0, MF_EINVAL, "solver_step_noise: n is not B whole samples");
+    MF_REQUIRE(a->n % (4L * nz->B) == 0, MF_EUNSUPPORTED, "solver_step_noise: elements per sample must be a multiple of 4 for the draw inside the launch");
+    MF_REQUIRE((al & 15) == 0, MF_EUNSUPPORTED,
+               "solver_step_noise: the draw inside the launch needs 16-byte aligned tensors (with a blend: cells a multiple of 4, a 4-byte aligned mask)");
+    qps = a->n / 4 / nz->B;
+  } else {
+    MF_REQUIRE(nz->noise_step_stride >= 0, MF_EINVAL, "solver_step_noise: noise_step_stride");
+    al |= (uintptr_t)nz->noise | (nz->noise_step_stride & 3 ? 4 : 0);
+  }
+  const long nq = (al & 15) ? 0 : a->n / 4;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(MF_FAM_SCHED, s, (bl ? 14.0 : 11.0) * a->n + (philox ? 50.0 * a->n : 0.0), 4.0 * a->n * ((bl ? 8 : 6) + (philox ? 0 : 1)));
+  long blocks = ((nq ? nq : a->n) + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  const SolverNoiseP p{nz->scale, nz->noise, (long)nz->noise_step_stride, (uint32_t)(nz->seed & 0xFFFFFFFFu), (uint32_t)(nz->seed >> 32), nz->draw_base, nz->draw_stride,
+                       (long)nz->sample_offset, qps};
+  if (philox && bl) {
+    MF_LAUNCH((solver_step_noise_kernel<true, true>), dim3((int)blocks), dim3(256), 0, s, *a, *bl, p, nq);
+  } else if (philox) {
+    MF_LAUNCH((solver_step_noise_kernel<false, true>), dim3((int)blocks), dim3(256), 0, s, *a, kNoBlend, p, nq);
+  } else if (bl) {
+    MF_LAUNCH((solver_step_noise_kernel<true, false>), dim3((int)blocks), dim3(256), 0, s, *a, *bl, p, nq);
+  } else {
+    MF_LAUNCH((solver_step_noise_kernel<false, false>), dim3((int)blocks), dim3(256), 0, s, *a, kNoBlend, p, nq);
+  }
+  return check_launch("solver_step_noise");
 }
 
 }  // namespace
@@ -510,6 +649,15 @@ int mf_solver_step_blend_f32(const MfSolverArgs* a, const MfSchedBlend* bl, void
   MF_REQUIRE(bl && bl->z0 && bl->eps0 && bl->mask && bl->coef && bl->cells > 0 && bl->channels > 0, MF_EINVAL, "solver_step_blend: bad blend state");
   MF_REQUIRE(a->n % (bl->cells * (int64_t)bl->channels) == 0, MF_EINVAL, "solver_step_blend: n is not a whole number of samples of channels x cells");
   return solver_step_launch(a, bl, nullptr, stream);
+}
+
+int mf_solver_step_noise_f32(const MfSolverArgs* a, const MfSolverNoise* nz, const MfSchedBlend* bl, void* stream) {
+  MF_REQUIRE(a && nz, MF_EINVAL, "solver_step_noise: bad args");
+  if (bl) {
+    MF_REQUIRE(bl->z0 && bl->eps0 && bl->mask && bl->coef && bl->cells > 0 && bl->channels > 0, MF_EINVAL, "solver_step_noise: bad blend state");
+    MF_REQUIRE(a->n % (bl->cells * (int64_t)bl->channels) == 0, MF_EINVAL, "solver_step_noise: n is not a whole number of samples of channels x cells");
+  }
+  return solver_step_noise_launch(a, nz, bl, stream);
 }
 
 int mf_gather_step_rows3_f32(const float* const* tables, const int64_t* row_lens, float* const* outs, int n_tables, const int64_t* cols, const int32_t* step_dev,

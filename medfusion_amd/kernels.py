@@ -1183,6 +1183,13 @@ def solver_step_traj(args: L.MfSolverArgs, traj: L.MfSolverTraj, outputs=()) -> 
     L.check(L.load().mf_solver_step_traj_f32(C.byref(args), C.byref(traj), stream()), "mf_solver_step_traj_f32")
 
 
+def solver_step_noise(args: L.MfSolverArgs, nz: L.MfSolverNoise, blend: Optional[L.MfSchedBlend] = None, outputs=()) -> None:
+    """the stochastic solver step in one launch (mf_solver_step_noise_f32): solver_step, then x_t_out += scale[step] * eps, eps the caller's draw
+    or Philox inside the launch (nz.noise None), then the inpainting select when `blend` is given.  `outputs` as in sched_step."""
+    _drop_outputs(outputs)
+    L.check(L.load().mf_solver_step_noise_f32(C.byref(args), C.byref(nz), None if blend is None else C.byref(blend), stream()), "mf_solver_step_noise_f32")
+
+
 def absdiff_mean_c(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """[N,C,...] fp32 x 2 -> [N,1,...]: the mean over the channels of |a - b| (mf_absdiff_mean_c_f32)"""
     _gpu(a, b)

@@ -57,6 +57,11 @@ class MfSolverArgs(C.Structure):
                 ("clip_x0", C.c_int32), ("guidance_scale", C.c_float), ("n", C.c_int64)]
 
 
+class MfSolverNoise(C.Structure):
+    _fields_ = [("scale", c_fp), ("noise", c_fp), ("noise_step_stride", C.c_int64), ("seed", C.c_uint64), ("sample_offset", C.c_int64),
+                ("draw_base", C.c_int32), ("draw_stride", C.c_int32), ("B", C.c_int32), ("reserved", C.c_int32)]
+
+
 TRAJ_RECORD, TRAJ_KEEP = 0, 1
 
 
@@ -161,6 +166,7 @@ _SIGS = {
     "mf_solver_step_f32": (_I, [C.POINTER(MfSolverArgs), c_fp]),
     "mf_solver_step_blend_f32": (_I, [C.POINTER(MfSolverArgs), C.POINTER(MfSchedBlend), c_fp]),
     "mf_solver_step_traj_f32": (_I, [C.POINTER(MfSolverArgs), C.POINTER(MfSolverTraj), c_fp]),
+    "mf_solver_step_noise_f32": (_I, [C.POINTER(MfSolverArgs), C.POINTER(MfSolverNoise), C.POINTER(MfSchedBlend), c_fp]),
     "mf_absdiff_mean_c_f32": (_I, [c_fp, c_fp, c_fp, _I, _I, _I64, c_fp]),
     "mf_select_cells_f32": (_I, [c_fp, c_fp, c_fp, c_fp, _I, _I, _I64, c_fp]),
     "mf_mask_maxpool_u8": (_I, [c_fp, _I, c_fp, _I, _I, _I, _I, _I, _I, _I, c_fp]),

@@ -187,12 +187,13 @@ class DiffusionPipeline(nn.Module):
         self_cond = x0 if self.estimator_objective == "x_T" else xT
         return prior, x0, xT, self_cond
 
-    # ------------------------------------------------------------------ deterministic few-step samplers
+    # ------------------------------------------------------------------ few-step samplers (deterministic and stochastic)
     @staticmethod
     def _check_sampler(sampler, spacing, use_ddim, cold_diffusion):
         """the rules of `sampler=` / `spacing=` (denoise, sample, sample_from), checked before anything touches the device"""
-        if sampler is not None and sampler not in GaussianNoiseScheduler.SAMPLERS:
-            raise ValueError(f"sampler={sampler!r}: None or one of {GaussianNoiseScheduler.SAMPLERS}")
+        known = GaussianNoiseScheduler.SAMPLERS + GaussianNoiseScheduler.STOCHASTIC_SAMPLERS
+        if sampler is not None and sampler not in known:
+            raise ValueError(f"sampler={sampler!r}: None or one of {known}")
         if spacing not in GaussianNoiseScheduler.SPACINGS:
             raise ValueError(f"spacing={spacing!r}: None, 'uniform' or 'logsnr'")
         if sampler is None:
@@ -213,12 +214,30 @@ class DiffusionPipeline(nn.Module):
                               objective, int(bool(self.clip_x0)), float(guidance_scale), x_t.numel())
 
     @staticmethod
-    def _solver_launch(args, blend, traj, outputs):
-        """one solver step: plain, with the inpainting blend, or (traj: an MfSolverTraj) recording / keeping a slot of an inversion's trajectory"""
-        if traj is None:
+    def _solver_launch(args, blend, traj, outputs, nz=None):
+        """one solver step: plain, with the inpainting blend, (traj: an MfSolverTraj) recording / keeping a slot of an inversion's trajectory, or
+        (nz: an MfSolverNoise; a stochastic sampler) adding the iteration's draw, with or without the blend"""
+        if nz is not None:
+            K.solver_step_noise(args, nz, blend, outputs=outputs)
+        elif traj is None:
             K.solver_step(args, blend, outputs=outputs)
         else:
             K.solver_step_traj(args, traj, outputs=outputs)
+
+    @staticmethod
+    def _solver_noise(noise, scales, x_t, blend, base):
+        """the MfSolverNoise of a stochastic sampler's loop -> (nz, buffer or None).  A device Philox source draws inside the step's launch (draw
+        base + step); where that form does not apply (a blend whose cells are not a multiple of 4) and for a host source the draw goes through
+        `buffer`, filled before the launch."""
+        from .noise import PhiloxDeviceNoise
+        dev, B = x_t.device, x_t.shape[0]
+        scale = torch.tensor(scales, dtype=torch.float32, device=dev)
+        inside = isinstance(noise, PhiloxDeviceNoise) and (x_t.numel() // B) % 4 == 0 and (blend is None or blend.cells % 4 == 0)
+        buf = None if inside else torch.empty_like(x_t)
+        nz = L.MfSolverNoise(scale.data_ptr(), None if inside else buf.data_ptr(), 0, (noise._seed & 0xFFFFFFFFFFFFFFFF) if inside else 0,
+                             noise.sample_offset if inside else 0, base, 1, B, 0)
+        nz._keep = (scale, buf)
+        return nz, buf
 
     # ------------------------------------------------------------------ the loop
     @torch.no_grad()
@@ -228,7 +247,10 @@ class DiffusionPipeline(nn.Module):
         by the reference); `eta` raises like the reference's forward() would (Q2).
         sampler="ddim0" | "dpmpp2m": a deterministic few-step sampler in place of the stochastic update -- the reference's DDIM update at
         sigma = 0, or DPM-Solver++(2M) in data-prediction form (GaussianNoiseScheduler.solver_records); needs use_ddim=True, draws no noise,
-        drops a learned variance head's output.  spacing="logsnr" (with a sampler): the grid uniform in log-SNR
+        drops a learned variance head's output.  sampler="ddim1" | "dpmpp2m_sde": a stochastic few-step sampler -- the reference's DDIM update
+        at its own eta = 1 on any grid, or SDE-DPM-Solver++(2M) (GaussianNoiseScheduler.stochastic_records; meant for spacing="logsnr"); one draw
+        per non-final iteration, taken inside the solver step's launch from a device Philox source (a host source is uploaded: eager loop only).
+        spacing="logsnr" (with a sampler): the grid uniform in log-SNR
         (GaussianNoiseScheduler.loop_timesteps), which may run fewer than `steps` iterations.  sampler=None: the loop below, unchanged.
         progress_cb(done, total): the hook that stands where the reference drives `st.progress` and `tqdm` (diffusion_pipeline.py:289-291; SURVEY Q16:
         no streamlit import here).  Called on the host after the iterations up to `done` have been ENQUEUED -- the loop never waits for the device;
@@ -306,8 +328,9 @@ class DiffusionPipeline(nn.Module):
         sch = self.noise_scheduler
         if sampler is not None:   # (the executed count decides whether the loop is long enough to replay: the log-SNR grid may drop iterations)
             timesteps, steps = sch.loop_timesteps(steps, use_ddim, spacing)
+        stochastic = sampler in GaussianNoiseScheduler.STOCHASTIC_SAMPLERS
         # (a deterministic sampler draws nothing inside the loop: any noise source replays)
-        replayable = (trace is None and not cold_diffusion and (sampler is not None or noise is None or isinstance(noise, PhiloxDeviceNoise))
+        replayable = (trace is None and not cold_diffusion and ((sampler is not None and not stochastic) or noise is None or isinstance(noise, PhiloxDeviceNoise))
                       and (steps is None or (steps - _start if _up is None else _up - 1) >= 4))
         if loop is not None and loop not in ("cmdlist", "graph", "eager"):
             raise ValueError(f"loop={loop!r}: 'cmdlist', 'graph' or 'eager'")
@@ -330,7 +353,13 @@ class DiffusionPipeline(nn.Module):
             recs = sch.step_records(timesteps, use_ddim)
             table = sch.upload_records(recs, dev)
         else:   # one MfSolverStep row per EXECUTED iteration: the first one is first-order wherever it sits in the grid
-            recs = sch.solver_records(timesteps, sampler, start=_start) if _up is None else sch.inversion_records(timesteps, sampler, stop=_up)
+            scales = None
+            if _up is not None:
+                recs = sch.inversion_records(timesteps, sampler, stop=_up)
+            elif stochastic:
+                recs, scales = sch.stochastic_records(timesteps, sampler, start=_start)
+            else:
+                recs = sch.solver_records(timesteps, sampler, start=_start)
             table = sch.upload_solver_records(recs, dev)
         if noise is None:  # x_t supplied by the caller (interpolate): fresh source, draws start at 0
             noise = default_noise()
@@ -378,10 +407,12 @@ class DiffusionPipeline(nn.Module):
             return x_t
         # the deterministic samplers: the x_0 history of the second-order rows ([2][n], slots alternate with the step), and the x_0 estimate
         # as a tensor of its own only where something reads it (self-conditioning, a trace)
-        hist = torch.empty((2, *x_t.shape), dtype=torch.float32, device=dev) if sampler == "dpmpp2m" else None
+        hist = torch.empty((2, *x_t.shape), dtype=torch.float32, device=dev) if sampler in ("dpmpp2m", "dpmpp2m_sde") else None
+        # a stochastic sampler: draw number noise.draw_index + i for executed iteration i (the last one draws nothing)
+        nz, n_buf = self._solver_noise(noise, scales, x_t, blend, noise.draw_index) if stochastic else (None, None)
         if mode in ("graph", "cmdlist"):
             self._denoise_graph(x_t, rev, recs, table, condition, guidance_scale, un_cond, use_ddim, noise, objective, cmdlist=(mode == "cmdlist"),
-                                progress_cb=progress_cb, blend=blend, solver=None if sampler is None else (hist, _traj))
+                                progress_cb=progress_cb, blend=blend, solver=None if sampler is None else (hist, _traj, nz, n_buf))
         elif sampler is not None:
             t_all = torch.tensor(rev, dtype=torch.float32, device=dev).reshape(-1, 1).expand(-1, B).contiguous()
             x0 = torch.empty_like(x_t) if (self.use_self_conditioning or trace is not None) else None
@@ -390,7 +421,12 @@ class DiffusionPipeline(nn.Module):
             for i in range(len(rev)):
                 pred, pred_uncond, _ = self._predict(x_t, t_all[i], condition, self_cond, guidance_scale, un_cond,
                                                      emb=None if emb_tab is None else (emb_tab[0], i, emb_tab[1], emb_tab[2], emb_tab[3]))
-                self._solver_launch(self._solver_args(x_t, pred, pred_uncond, x0, hist, table, objective, guidance_scale, step=i), blend, _traj, (x_t, x0))
+                if stochastic and i < len(rev) - 1:
+                    if n_buf is None:
+                        noise.draw_index += 1                          # (draw nz.draw_base + i, generated inside the launch)
+                    else:
+                        noise.draw(tuple(x_t.shape), out=n_buf)
+                self._solver_launch(self._solver_args(x_t, pred, pred_uncond, x0, hist, table, objective, guidance_scale, step=i), blend, _traj, (x_t, x0), nz)
                 self_cond = x0 if self.use_self_conditioning else None
                 if trace is not None:
                     trace.append((x0.clone(), x_t.clone()))
@@ -450,11 +486,13 @@ class DiffusionPipeline(nn.Module):
         DEVICE step counter: `t` is broadcast from a device table, the scheduler scalars come from the MfSchedStep table,
         the Philox draw index is draw_base + stride*step, and the graph advances the counter itself.  The last DDIM
         iteration still fills the (unused) DDIM noise buffer: counter-based draws do not shift any other draw.
-        solver = (x_0 history or None, MfSolverTraj or None): `table` holds MfSolverStep rows and the tail of an iteration is mf_solver_step_f32
-        (mf_solver_step_traj_f32 with a trajectory, whose slot the same counter indexes), which reads the counter, advances it and draws nothing."""
+        solver = (x_0 history or None, MfSolverTraj or None, MfSolverNoise or None, its draw buffer or None): `table` holds MfSolverStep rows and the
+        tail of an iteration is mf_solver_step_f32 (mf_solver_step_traj_f32 with a trajectory, whose slot the same counter indexes), which reads
+        the counter, advances it and draws nothing -- or, for a stochastic sampler, mf_solver_step_noise_f32, whose draw index the same counter
+        advances (draw base + step, inside the launch; through the buffer and one more launch where the in-launch form does not apply)."""
         from .noise import PhiloxDeviceNoise
 
-        if solver is None and not isinstance(noise, PhiloxDeviceNoise):
+        if (solver is None or solver[2] is not None) and not isinstance(noise, PhiloxDeviceNoise):
             raise RuntimeError("use_graph=True needs the device Philox noise source (a host generator cannot be captured)")
         dev, B = x_t.device, x_t.shape[0]
         t_table = torch.tensor(rev, dtype=torch.float32, device=dev)
@@ -466,6 +504,7 @@ class DiffusionPipeline(nn.Module):
             x0 = torch.empty_like(x_t)
         stride = 0 if solver is not None else 2 if use_ddim else 1
         base = noise.draw_index  # draws consumed so far (x_T)
+        drawn = stride * len(rev) if solver is None else (len(rev) - 1 if solver[2] is not None else 0)   # (a stochastic sampler: all but the last iteration)
         clip, g = int(bool(self.clip_x0)), float(guidance_scale)
 
         emb_tab = self._hoisted_embeddings(self._estimator(), t_table, condition, un_cond, B, dev)
@@ -482,12 +521,17 @@ class DiffusionPipeline(nn.Module):
             else:
                 K.sched_step_blend(a, blend, outputs=(x_t, x0))
 
+        def solver_tail(pred, pred_uncond):
+            if solver[3] is not None:   # (a stochastic sampler whose draw cannot be made inside the step's launch)
+                noise.draw_indexed(solver[3], base, 1, step_dev)
+            self._solver_launch(self._solver_args(x_t, pred, pred_uncond, x0, solver[0], table, objective, g, counter=counter), blend, solver[1], (x_t, x0), solver[2])
+
         def body():
             if emb is None:   # (with the embedding rows hoisted out of the loop the estimator never reads t)
                 K.broadcast_from_table(t_table, step_dev, t_cur)
             pred, pred_uncond, pred_var = self._predict(x_t, t_cur, condition, None if not self.use_self_conditioning else x0, g, un_cond, emb=emb)
             if solver is not None:
-                self._solver_launch(self._solver_args(x_t, pred, pred_uncond, x0, solver[0], table, objective, g, counter=counter), blend, solver[1], (x_t, x0))
+                solver_tail(pred, pred_uncond)
                 return pred
             if fused_tail:
                 a = L.MfSchedArgs(x_t.data_ptr(), pred.data_ptr(), None if pred_uncond is None else pred_uncond.data_ptr(),
@@ -515,7 +559,7 @@ class DiffusionPipeline(nn.Module):
                     K.broadcast_from_table(t_table, step_dev, t_cur)
                 pred, pu, pv = self._predict(x_t, t_cur, condition, None, g, un_cond, emb=emb)
                 if solver is not None:
-                    self._solver_launch(self._solver_args(x_t, pred, pu, x0, solver[0], table, objective, g, counter=counter), blend, solver[1], (x_t, x0))
+                    solver_tail(pred, pu)
                     return
                 noise.draw_indexed(n_post, base, stride, step_dev)
                 if use_ddim:
@@ -593,7 +637,7 @@ class DiffusionPipeline(nn.Module):
                 finally:
                     lib.mf_cmdlist_free(handle)    # (the kernarg bytes were copied at every launch)
                 del keep
-            noise.draw_index = base + stride * len(rev)
+            noise.draw_index = base + drawn
             return
         side = _GRAPH_STREAMS.get(dev.index)      # ONE capture stream per device (per-stream workspaces / split-K counters stay bounded)
         if side is None:
@@ -616,7 +660,7 @@ class DiffusionPipeline(nn.Module):
                         progress_cb(k + 1, len(rev))
                 del keep
         torch.cuda.current_stream(dev).wait_stream(side)
-        noise.draw_index = base + stride * len(rev)
+        noise.draw_index = base + drawn
 
     @torch.no_grad()
     def sample(self, num_samples, img_size, condition=None, noise: Optional[NoiseSource] = None, shard=None, **kwargs):
@@ -694,9 +738,9 @@ class DiffusionPipeline(nn.Module):
         Philox source keeps the global sample index.  NB: VAE.encode begins its own noise source at row 0, so with a stochastic embedder a
         sharded caller encodes first and passes latents (the codebook embedders draw nothing and shard as they are).
         cold_diffusion=True raises ValueError; `eta` raises TypeError like everywhere.
-        sampler= / spacing= as in denoise(): the deterministic samplers on the EXECUTED grid -- the same strength rule picks the last k of its
+        sampler= / spacing= as in denoise(): the few-step samplers on the EXECUTED grid -- the same strength rule picks the last k of its
         iterations, the first of them is first-order, the kept cells take the known latent at the next timestep of that grid; eps0 is the only
-        draw."""
+        draw of a deterministic sampler, a stochastic one ("ddim1", "dpmpp2m_sde") adds one draw per non-final iteration (k draws in all)."""
         if "eta" in kwargs:
             raise TypeError("forward() got an unexpected keyword argument 'eta'")
         if kwargs.pop("cold_diffusion", False):
@@ -785,7 +829,7 @@ class DiffusionPipeline(nn.Module):
             raise ValueError(f"cold_diffusion is not built for {who}")
         if kwargs:
             raise TypeError(f"forward() got an unexpected keyword argument '{next(iter(kwargs))}'")
-        if sampler is None:
+        if sampler is None or sampler in GaussianNoiseScheduler.STOCHASTIC_SAMPLERS:
             raise ValueError(f"{who} needs a deterministic sampler ('ddim0' or 'dpmpp2m'): the stochastic loop has no upward form")
         self._check_sampler(sampler, spacing, True, False)
         timesteps, _ = self.noise_scheduler.loop_timesteps(steps, True, spacing)

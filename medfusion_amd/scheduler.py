@@ -84,12 +84,13 @@ class GaussianNoiseScheduler(BasicNoiseScheduler):
             self._host = (key, {n: getattr(self, n).detach().to("cpu", torch.float32).clone() for n in self.TABLES})
         return self._host[1]
 
-    SAMPLERS = ("ddim0", "dpmpp2m")
+    SAMPLERS = ("ddim0", "dpmpp2m")                     # deterministic: the ones invert() / edit() accept
+    STOCHASTIC_SAMPLERS = ("ddim1", "dpmpp2m_sde")      # one draw per non-final iteration (stochastic_records)
     SPACINGS = (None, "uniform", "logsnr")
 
     def loop_timesteps(self, steps: Optional[int], use_ddim: bool, spacing: Optional[str] = None) -> Tuple[List[int], int]:
         """diffusion_pipeline.py:283-287: DDIM -> truncated linspace (Q4); else the FIRST `steps` entries (Q5).
-        spacing="logsnr" (deterministic samplers only): `steps` targets uniform in lambda = 1/2 log(ac / (1 - ac)) between timestep 0 and T - 1, each
+        spacing="logsnr" (with a sampler only): `steps` targets uniform in lambda = 1/2 log(ac / (1 - ac)) between timestep 0 and T - 1, each
         mapped to the nearest integer timestep, the endpoints forced to 0 and T - 1, duplicates dropped; the second value is then the EXECUTED
         count, len(timesteps) <= steps."""
         if spacing not in self.SPACINGS:
@@ -161,6 +162,60 @@ class GaussianNoiseScheduler(BasicNoiseScheduler):
                 h_prev = h
             recs.append(r)
         return recs
+
+    def stochastic_records(self, timesteps: List[int], sampler: str, start: int = 0) -> Tuple[List[L.MfSolverStep], List[float]]:
+        """solver_records for a stochastic sampler: per EXECUTED iteration i = start .. len - 1 one MfSolverStep row and the fp32 scale S of the
+        draw the iteration adds, x_next = (the row's deterministic update) + S eps:
+          "ddim1"        the reference's DDIM update (diffusion_pipeline.py:297-304) at its own eta = 1, on any grid: MF_SOLVER_DDIM0 rows with the
+                         scalars step_records(timesteps, True) computes with the reference's fp32 torch ops, B = ddim_sqrt_an, A = ddim_c,
+                         S = ddim_sigma -- given the same draws the latents equal the default loop's bit for bit;
+          "dpmpp2m_sde"  SDE-DPM-Solver++(2M), data prediction, midpoint form (Lu et al. 2022), in solver_records' conventions (alpha, sigma,
+                         lambda, h = lambda_next - lambda_t): x_next = A x_t + B x_0 + C x_0_prev + S eps with A = (sigma_next / sigma_t) e^-h,
+                         E = alpha_next (-expm1(-2h)), B = E and C = 0 on the first executed transition, then B = E (1 + 1/(2r)), C = -E / (2r),
+                         r = h_prev / h, and S = sigma_next sqrt(-expm1(-2h)) (so that A^2 sigma_t^2 + S^2 = sigma_next^2).  fp64 from the
+                         alphas_cumprod table, every coefficient rounded to fp32 once.  Meant for the log-SNR grid: on the reference's grid the
+                         first transitions span most of the log-SNR range and the solver is far less accurate (README).
+        The last iteration is MF_SOLVER_FINAL: it returns its x_0, draws nothing, S = 0."""
+        if sampler not in self.STOCHASTIC_SAMPLERS:
+            raise ValueError(f"sampler={sampler!r}: one of {self.STOCHASTIC_SAMPLERS}")
+        tb = self.host_tables()
+        rev = list(reversed(timesteps))
+        if not 0 <= start < max(1, len(rev)):
+            raise ValueError(f"start={start} of {len(rev)} iterations")
+        if sampler == "dpmpp2m_sde" and any(b <= a for a, b in zip(timesteps, timesteps[1:])):
+            raise ValueError("sampler='dpmpp2m_sde' needs strictly increasing timesteps (a repeated timestep has h = 0): steps <= T")
+        ddim = self.step_records(timesteps, True) if sampler == "ddim1" else None
+        ac = tb["alphas_cumprod"].to(torch.float64)
+        alpha, sigma = torch.sqrt(ac), torch.sqrt(1 - ac)
+        lam = torch.log(alpha / sigma)
+        recs, scales, h_prev = [], [], None
+        for i in range(start, len(rev)):
+            t = rev[i]
+            r = L.MfSolverStep()
+            r.sqrt_recip_ac = float(tb["sqrt_recip_alphas_cumprod"][t])
+            r.sqrt_recipm1_ac = float(tb["sqrt_recipm1_alphas_cumprod"][t])
+            r.t, r.reserved = int(t), 0
+            r.A = r.B = r.C = 0.0
+            scale = 0.0
+            if i == len(rev) - 1:
+                r.mode = L.SOLVER_FINAL
+            elif sampler == "ddim1":
+                r.A, r.B, r.mode, scale = ddim[i].ddim_c, ddim[i].ddim_sqrt_an, L.SOLVER_DDIM0, ddim[i].ddim_sigma
+            else:
+                tn = rev[i + 1]
+                h = float(lam[tn] - lam[t])
+                e = -float(alpha[tn]) * math.expm1(-2.0 * h)
+                r.A = float(sigma[tn] / sigma[t]) * math.exp(-h)
+                if h_prev is None:
+                    r.B, r.mode = e, L.SOLVER_ORDER1
+                else:
+                    k = 1.0 / (2.0 * (h_prev / h))
+                    r.B, r.C, r.mode = e * (1.0 + k), -e * k, L.SOLVER_ORDER2
+                scale = float(sigma[tn]) * math.sqrt(-math.expm1(-2.0 * h))
+                h_prev = h
+            recs.append(r)
+            scales.append(C.c_float(scale).value)     # (rounded to fp32 once, like the row's fields)
+        return recs, scales
 
     def inversion_records(self, timesteps: List[int], sampler: str, stop: Optional[int] = None) -> List[L.MfSolverStep]:
         """The UPWARD rows of a deterministic sampler (DDIM inversion): the probability-flow ODE carried from the grid's lowest timestep towards

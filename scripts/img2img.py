@@ -13,6 +13,7 @@ thread): one PNG per input, same file name, under --out.
 The mask PNG has the images' size; non-zero pixels are REGENERATED, zero pixels kept (a latent cell is regenerated if any of its pixels is).
 Draws: #0 diffuses the encoded image, then the loop's draws as in sample() (Philox key --seed; the encoder's draw uses key --seed + 1).
 --sampler ddim0 | dpmpp2m (with --spacing logsnr: fewer iterations for the same solver accuracy) runs the loop deterministically: draw #0 only.
+--sampler ddim1 | dpmpp2m_sde (the latter meant for --spacing logsnr) keeps the loop stochastic at few steps: one more draw per non-final iteration.
 """
 import argparse
 import sys
@@ -57,7 +58,8 @@ if __name__ == "__main__":
     ap.add_argument("--guidance", type=float, default=1.0)
     ap.add_argument("--condition", type=int, default=None, help="class label for every image")
     ap.add_argument("--ddpm", action="store_true", help="the posterior loop instead of DDIM")
-    ap.add_argument("--sampler", default=None, choices=["ddim0", "dpmpp2m"], help="a deterministic few-step sampler in place of the stochastic update")
+    ap.add_argument("--sampler", default=None, choices=["ddim0", "dpmpp2m", "ddim1", "dpmpp2m_sde"],
+                    help="a few-step sampler in place of the reference's update: deterministic (ddim0, dpmpp2m) or stochastic (ddim1, dpmpp2m_sde)")
     ap.add_argument("--spacing", default=None, choices=["uniform", "logsnr"], help="timestep grid of --sampler (logsnr: uniform in log-SNR)")
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--seed", type=int, default=0)

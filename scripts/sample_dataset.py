@@ -40,7 +40,8 @@ if __name__ == "__main__":
     ap.add_argument("--no-files", action="store_true", help="run the egress (device conversion + async copy) but skip the PNG encoder")
     ap.add_argument("--compare-no-egress", action="store_true", help="also time the same generation with the images left on the device")
     ap.add_argument("--writer-threads", type=int, default=2, help="PNG encoder threads of the asynchronous writer")
-    ap.add_argument("--sampler", default=None, choices=["ddim0", "dpmpp2m"], help="a deterministic few-step sampler (default: the reference's loop)")
+    ap.add_argument("--sampler", default=None, choices=["ddim0", "dpmpp2m", "ddim1", "dpmpp2m_sde"],
+                    help="a few-step sampler, deterministic (ddim0, dpmpp2m) or stochastic (ddim1, dpmpp2m_sde); default: the reference's loop")
     ap.add_argument("--spacing", default=None, choices=["uniform", "logsnr"], help="timestep grid of --sampler (logsnr: uniform in log-SNR)")
     args = ap.parse_args()
     solver = {} if args.sampler is None and args.spacing is None else dict(sampler=args.sampler, spacing=args.spacing)

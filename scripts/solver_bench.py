@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""What the deterministic few-step samplers cost and how far they land from the ODE limit, measured on one box in one process
-(profiles/solver_bench.txt).
+"""What the few-step samplers -- deterministic and stochastic -- cost and how far the deterministic ones land from the ODE limit, measured on one
+box in one process (profiles/solver_bench.txt; the stochastic samplers' rows: profiles/sde_bench.txt).
 
   python scripts/solver_bench.py [--batch 16] [--rounds 3] [--limit-steps 1000]      (on a ROCm device)
   python scripts/solver_bench.py --plan                                               (no device: the configurations and their executed counts)
@@ -8,10 +8,12 @@
 cfg2 of bench.py: published architecture with seeded weights, B = 16, latent (8, 32, 32), device Philox noise, VAE decode included.  Every time is
 the wall time of ONE call, synchronised before and after, after one warm-up call per configuration; the configurations are interleaved
 over `rounds` rounds.
-  * images/s: sampler=None at 150 iterations (the loop every earlier commit runs: the baseline), "ddim0" at 150, "dpmpp2m" + "logsnr" at 20 / 25 / 30;
-  * ms per executed iteration of each loop kind (None / "ddim0" / "dpmpp2m"): (wall(150) - wall(75)) / 75 on the uniform grid, per round -- the decode
-    and the fixed cost of a call cancel.  GATE: a solver iteration is not slower than a sampler=None iteration beyond the larger of the two
-    run-to-run spreads (max - min over the rounds); it launches strictly less (no Philox draws).  Exit status 1 when the gate is missed;
+  * images/s: sampler=None at 150 iterations (the loop every earlier commit runs: the baseline), "ddim0" at 150, "dpmpp2m" + "logsnr" and
+    "dpmpp2m_sde" + "logsnr" at 20 / 25 / 30;
+  * ms per executed iteration of each loop kind (None / "ddim0" / "dpmpp2m" / "ddim1" / "dpmpp2m_sde"): (wall(150) - wall(75)) / 75 on the uniform
+    grid, per round -- the decode and the fixed cost of a call cancel.  GATE (the deterministic samplers): a solver iteration is not slower than a
+    sampler=None iteration beyond the larger of the two run-to-run spreads (max - min over the rounds); it launches strictly less (no Philox
+    draws).  Exit status 1 when the gate is missed.  The stochastic samplers draw inside the same one launch: reported next to the others, not gated;
   * the fixed cost of a call at 20 executed iterations: wall(20) - 18 x the replayed iteration's time (iterations 0 and 1 go through Python --
     eager, then recorded -- and the list is rebuilt on every call), next to the decoder's own time;
   * solver error ON SYNTHETIC WEIGHTS: max-norm relative error of the final latent of each few-step run against "ddim0" on the uniform grid at
@@ -28,8 +30,11 @@ sys.path.insert(0, str(ROOT))
 
 # label -> (sampler, spacing, steps)
 HEADLINE = {"sampler=None @150": (None, None, 150), "ddim0 @150": ("ddim0", None, 150), "dpmpp2m+logsnr @20": ("dpmpp2m", "logsnr", 20),
-            "dpmpp2m+logsnr @25": ("dpmpp2m", "logsnr", 25), "dpmpp2m+logsnr @30": ("dpmpp2m", "logsnr", 30)}
-SLOPE = {"sampler=None": (None, None), "ddim0": ("ddim0", None), "dpmpp2m": ("dpmpp2m", None)}
+            "dpmpp2m+logsnr @25": ("dpmpp2m", "logsnr", 25), "dpmpp2m+logsnr @30": ("dpmpp2m", "logsnr", 30),
+            "dpmpp2m_sde+logsnr @20": ("dpmpp2m_sde", "logsnr", 20), "dpmpp2m_sde+logsnr @25": ("dpmpp2m_sde", "logsnr", 25),
+            "dpmpp2m_sde+logsnr @30": ("dpmpp2m_sde", "logsnr", 30)}
+SLOPE = {"sampler=None": (None, None), "ddim0": ("ddim0", None), "dpmpp2m": ("dpmpp2m", None), "ddim1": ("ddim1", None), "dpmpp2m_sde": ("dpmpp2m_sde", None)}
+STOCHASTIC = ("ddim1", "dpmpp2m_sde")     # (one Philox draw per non-final iteration: they have no ODE limit to be compared with)
 SLOPE_STEPS = (75, 150)
 
 
@@ -86,7 +91,7 @@ def main(a):
     base = stats(wall["sampler=None @150"])[0]
     for label in HEADLINE:
         m, sp_ = stats(wall[label])
-        print(f"{label:22s} executed {executed[label]:4d} | {fmt(wall[label])} | mean {m * 1e3:.1f} spread {sp_ * 1e3:.1f} | {B / m:7.1f} images/s | {base / m:.2f} x baseline")
+        print(f"{label:24s} executed {executed[label]:4d} | {fmt(wall[label])} | mean {m * 1e3:.1f} spread {sp_ * 1e3:.1f} | {B / m:7.1f} images/s | {base / m:.2f} x baseline")
     print(f"-- ms per executed iteration: (wall({SLOPE_STEPS[1]}) - wall({SLOPE_STEPS[0]})) / {SLOPE_STEPS[1] - SLOPE_STEPS[0]} per round")
     it = {}
     for label in SLOPE:
@@ -117,7 +122,7 @@ def main(a):
     rel = lambda x, y: float((x.double() - y.double()).abs().max() / y.double().abs().max())
     limit = call("ddim0", None, a.limit_steps, 77, decode=False)[1]
     for label, (s, sp, n) in HEADLINE.items():
-        if s is None:
+        if s is None or s in STOCHASTIC:
             continue
         print(f"{label:22s} relerr {rel(call(s, sp, n, 77, decode=False)[1], limit):.3e}")
     for s, sp, n in (("dpmpp2m", None, 20), ("ddim0", "logsnr", 20), ("ddim0", None, 20)):
@@ -136,6 +141,6 @@ if __name__ == "__main__":
     a = ap.parse_args()
     if a.plan:
         for label, sampler, spacing, steps, executed in plan():
-            print(f"{label:44s} sampler={sampler!s:8s} spacing={spacing!s:7s} steps={steps:4d} executed={executed}")
+            print(f"{label:44s} sampler={sampler!s:11s} spacing={spacing!s:7s} steps={steps:4d} executed={executed}")
         sys.exit(0)
     main(a)
