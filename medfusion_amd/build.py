@@ -130,14 +130,21 @@ def build_variant(name: str, conv_flags=(), packed_fp32: bool = False, verbose: 
     flags = {k: list(v) for k, v in (unit_flags or {}).items()}
     if conv_flags or packed_fp32 or not flags:
         flags["conv_f16x2.hip"] = list(conv_flags) + flags.get("conv_f16x2.hip", [])
+    lib = vdir / f"libmedfusion_hip_{name}.so"
+    # a twin is rebuilt only when a source, a header, the product library it shares objects with, or its own flags changed (the flags of
+    # the last build lie next to it): tests and A/B scripts ask for the same twin again and again
+    how = vdir / f"libmedfusion_hip_{name}.flags"
+    want = repr((sorted(flags.items()), packed_fp32, CFLAGS, sorted(EXTRA_CFLAGS.items())))
+    if how.exists() and how.read_text() == want and not _stale(lib, [CSRC / s for s in SOURCES] + _deps() + [LIB, Path(__file__)]):
+        return lib
     objs = {}
     for src, fl in flags.items():
         obj = vdir / f"{Path(src).stem}_{name}.o"
         extra = [] if (packed_fp32 and src == "conv_f16x2.hip") else EXTRA_CFLAGS.get(src, [])
         _run([hipcc(), *CFLAGS, *extra, *fl, "-c", str(CSRC / src), "-o", str(obj)], verbose)
         objs[src] = obj
-    lib = vdir / f"libmedfusion_hip_{name}.so"
     _link([objs.get(s, OBJ / (Path(s).stem + ".o")) for s in SOURCES], lib, verbose)
+    how.write_text(want)
     return lib
 
 

@@ -71,47 +71,82 @@ struct FuseP {
   unsigned* rv_err;             // one word: a rendezvous timed out
 };
 
+// Field order.  The struct is a by-value kernel argument of 424 bytes = seven 64-byte lines of the kernel-argument segment, read through the
+// scalar cache.  Everything a workgroup needs between its entry and its first barrier (the ramp) comes FIRST and is contiguous, so that the
+// body fetches it in a few wide scalar loads behind ONE wait (MFC2_RAMP_ARGS below) instead of line by line as the address arithmetic
+// gets to each field; what only the epilogue reads follows, and its lines are touched by the same burst so that they are warm at the drain.
 struct ConvP2 {
+  // ---- the ramp block (42 dwords)
   const void* x1;   // [N][Hin][Win][C1/8][2][8] fp16 pairs
   const void* x2;   // second source of the fused channel concat, or null
   const void* w;    // [phases][Cout][taps][Cin/8][2][8] fp16 pairs
-  const float* bias;
-  float* y;         // fp32 NHWC output, or the split-K slabs
   const float* bound1;   // [N] per-sample bounds the sources were scaled with (split_f16.h), or null = unscaled
   const float* bound2;
-  int wexp;              // the weights were split as w * 2^-wexp
-  float* out_bound;      // optional [N][slots]: measured max |y| of every (tile, wave) of a sample (splitk == 1, a tile inside one sample)
-  int bound_slots;
+  const float* bias;     // (read by the epilogue, FETCHED in the ramp together with the bounds)
   int N, Hin, Win, C1, C2, Cin, Cout;
-  int Hout, Wout, Heff, Weff, KH, KW, stride, pad;
+  int Wout, Heff, Weff, KH, KW, stride, pad;
   int M, K, HWout;
   int cgroups, cg_per_split, splitk;   // 32-channel chunks: total, per split-K slice (a slice holds ALL taps of its chunks)
   int tiles_m, tiles_n;
-  long slab;
   unsigned bytes1, bytes2, bytesw;
   int subpix, hw_src;
-  int out_nt;            // 1: non-temporal output stores (the component GEMM's output is 4x an activation, read once by the tail)
   int wphase_rows;       // > 0: rows [k wphase_rows, (k + 1) wphase_rows) of the GEMM use weight slab k (the component GEMMs of the Winograd form, winograd.h)
   int walk_n_fast;       // 1: the tile walk runs over the output-channel tiles first (an XCD covers all Cout blocks of a pixel range: activations fetched once)
-  double* gn_partial;   // optional fused GroupNorm statistics [N][gn_parts][G][2] (splitk == 1, or tree)
-  int gn_groups, gn_parts, gn_cpg;
   // split-K reduced INSIDE the launch (tree != 0, splitk a power of two): the partial tiles meet pairwise, level by level; at every level
   // both partners store their tile (write-through, agent scope), bump the pair's counter, and the one that arrives second adds its
   // partner's tile and goes on -- a + b does not depend on who adds, so the result is deterministic.  The last one runs the epilogue.
   int tree;
+  // ---- epilogue only (MFC2_RAMP_ARGS touches one small field per 64 bytes of it: wexp, gn_groups, fz.bconst, fz.res_nslots, fz.emb_stride,
+  // wl1_1, bmax -- keep such a field at most 64 bytes behind the previous one when this part changes)
+  int wexp;              // the weights were split as w * 2^-wexp
+  int Hout;
+  int bound_slots;
+  int out_nt;            // 1: non-temporal output stores (the component GEMM's output is 4x an activation, read once by the tail)
+  float* y;         // fp32 NHWC output, or the split-K slabs
+  float* out_bound;      // optional [N][slots]: measured max |y| of every (tile, wave) of a sample (splitk == 1, a tile inside one sample)
+  long slab;
+  double* gn_partial;   // optional fused GroupNorm statistics [N][gn_parts][G][2] (splitk == 1, or tree)
   float* handoff;       // [tiles][2 (splitk - 1) slots][BM x BN floats]
   unsigned* sync;       // [tiles][splitk - 1] counters, zero between launches (the second arriver of a pair resets its counter)
+  int gn_groups, gn_parts, gn_cpg;
   FuseP fz;
   // the output ALSO as fp16 pairs, scaled per sample by a bound DERIVED from the operands (round 4): |y| <= bound(x1) wl1_1 + bound(x2) wl1_2 + bmax,
   // wl1 = the largest L1 norm of a filter over the source's channels -- no measuring pass, no separate split launch behind the convolutions
   // whose output feeds convolutions un-normalised (down- / up-sampling).  Final-value workgroups only (splitk == 1 or tree).
+  float wl1_1, wl1_2;
   void* y_pairs;
   float* y_pair_bound;   // [N] written
-  float wl1_1, wl1_2, bmax;
+  float bmax;
 #if MFC2_HZ & (256 | 512)
   float* dbg;           // diagnostic builds: [tiles][waves][TM][TN][16][64] the accumulators of the surviving workgroup right behind the tree
 #endif
 };
+
+static_assert(offsetof(ConvP2, wexp) == 168, "the ramp block: 6 pointers + 30 ints, nothing else in front of wexp");
+static_assert(offsetof(ConvP2, gn_groups) - offsetof(ConvP2, wexp) <= 64 && offsetof(ConvP2, fz) + offsetof(FuseP, bconst) - offsetof(ConvP2, gn_groups) <= 64 &&
+              offsetof(FuseP, res_nslots) - offsetof(FuseP, bconst) <= 64 && offsetof(FuseP, emb_stride) - offsetof(FuseP, res_nslots) <= 64 &&
+              offsetof(ConvP2, wl1_1) - offsetof(ConvP2, fz) - offsetof(FuseP, emb_stride) <= 64 && offsetof(ConvP2, bmax) - offsetof(ConvP2, wl1_1) <= 64,
+              "MFC2_RAMP_ARGS touches every 64-byte line of the epilogue's part");
+
+// The ramp block of `P` (a local copy of the kernel argument) fetched at the kernel's entry: every field is an operand of one of three
+// adjacent empty asm statements, so all of them must be in scalar registers THERE -- the compiler issues their loads back to back (merged
+// into dwordx16 / x8 / x4 bursts: the block is contiguous) in front of the first statement and waits once.  Read-write operands: the
+// values behind the statements are the statements' results, which cannot be re-fetched from the argument segment later (what the compiler
+// otherwise does under SGPR pressure, one dependent round trip at a time); the ones that do not fit stay in VGPR lanes (v_writelane /
+// v_readlane, single cycles, all outside the main loop: tests/test_conv_ramp_isa_cpu.py).  The read-only operands of the third statement
+// are one SMALL field of each 64-byte line of the epilogue's part, fetched in the same burst: the lines are in the scalar cache when the
+// drain gets to them (small fields: the compiler may keep what it has fetched until the epilogue, and a pointer or a block of FuseP kept
+// alive across the loop costs lane moves by the hundred).
+#define MFC2_RAMP_ARGS(P)                                                                                               \
+  __builtin_amdgcn_sched_barrier(0);   /* (every load of the copy above stays above: ONE burst, not one per statement) */ \
+  asm volatile("" : "+s"(P.x1), "+s"(P.x2), "+s"(P.w), "+s"(P.bound1), "+s"(P.bound2), "+s"(P.bias), "+s"(P.N), "+s"(P.Hin), "+s"(P.Win), \
+               "+s"(P.C1), "+s"(P.C2), "+s"(P.Cin), "+s"(P.Cout), "+s"(P.Wout));                                        \
+  asm volatile("" : "+s"(P.Heff), "+s"(P.Weff), "+s"(P.KH), "+s"(P.KW), "+s"(P.stride), "+s"(P.pad), "+s"(P.M), "+s"(P.K), "+s"(P.HWout), \
+               "+s"(P.cgroups), "+s"(P.cg_per_split), "+s"(P.splitk), "+s"(P.tiles_m), "+s"(P.tiles_n));                \
+  asm volatile("" : "+s"(P.bytes1), "+s"(P.bytes2), "+s"(P.bytesw), "+s"(P.subpix), "+s"(P.hw_src), "+s"(P.wphase_rows), "+s"(P.walk_n_fast), \
+               "+s"(P.tree)                                                                                             \
+               : "s"(P.wexp), "s"(P.gn_groups), "s"(__float_as_int(P.fz.bconst)), "s"(P.fz.res_nslots), "s"((int)P.fz.emb_stride), "s"(__float_as_int(P.wl1_1)),   \
+                 "s"(__float_as_int(P.bmax)));
 
 __device__ __forceinline__ int xcd_remap2(int bid, int total) {  // bijective; block b runs on XCD b % 8
   const int q = total >> 3, r = total & 7;
@@ -134,6 +169,18 @@ __device__ __forceinline__ int xcd_remap2(int bid, int total) {  // bijective; b
 __device__ __forceinline__ float hz_add(float a, float b) { float r; asm volatile("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ float hz_mul(float a, float b) { float r; asm volatile("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 
+// The epilogue's view of the kernel argument.  A by-value struct argument is taken apart into one scalar load per field in the kernel's ENTRY
+// block, so whatever only the epilogue reads (40 dwords of pointers and FuseP) used to be fetched in the ramp as well -- a dependent round trip
+// per cold line -- and then parked in VGPR lanes across the loop.  The epilogue therefore reads `p` through the argument segment itself
+// (byte OFF of it: 0, or where the second ConvP2 of a grouped launch lies), behind an empty asm statement that makes the pointer opaque:
+// none of these loads can move above this point, and the body's own copy keeps nothing but its ramp block alive.  The lines were touched
+// by MFC2_RAMP_ARGS, so the drain finds them in the scalar cache.
+#define MFC2_EPILOGUE_ARGS(OFF)                                                                                         \
+  const char __attribute__((address_space(4)))* pk_ =                                                                   \
+      (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr() + (OFF);                    \
+  asm volatile("" : "+s"(pk_));                                                                                         \
+  const ConvP2& p = *(const ConvP2*)pk_;
+
 #define MFC2_WAIT_VM(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
 // MFC2_HZ bit 9 (diagnostic build, scripts/conv_timeline.py): workgroup `blockIdx.x` leaves the 100 MHz real-time counter at four points of its
 // life in p.dbg (as uint64 [grid][8]): 0 entry, 1 first chunk landed (end of the ramp), 2 end of the K loop, 3 end of the epilogue; inside the
@@ -150,14 +197,18 @@ __device__ __forceinline__ float hz_mul(float a, float b) { float r; asm volatil
 // pieces are simply never read from LDS.
 #define MFC2_BODY_AS_KERNEL 1
 #define MFC2_BID blockIdx.x
+#define MFC2_KARG_OFF 0
 #include "conv_f16x2_body.inc"
 #undef MFC2_BODY_AS_KERNEL
 #undef MFC2_BID
+#undef MFC2_KARG_OFF
 #define MFC2_BODY_AS_KERNEL 0
 #define MFC2_BID bid
+#define MFC2_KARG_OFF karg_off
 #include "conv_f16x2_body.inc"
 #undef MFC2_BODY_AS_KERNEL
 #undef MFC2_BID
+#undef MFC2_KARG_OFF
 
 // fp32 [rows][per_row] -> fp16 pairs, 8 consecutive elements per thread; row r is scaled by 2^-scale_exp_of(bound[r]) (bound null: unscaled)
 __global__ __launch_bounds__(256) void split_act_f16x2_kernel(const float* __restrict__ x, u32x4* __restrict__ out, long octets,

@@ -1,13 +1,13 @@
 // conv_f16x2_body.inc -- the life of one workgroup of the fp16-pair implicit-GEMM convolution, included TWICE by conv_f16x2.h:
-//   MFC2_BODY_AS_KERNEL 1: as the __global__ conv_f16x2_kernel (its workgroup index is blockIdx.x) -- the text the product kernels have always
-//                          been compiled from, token for token (the ISA of every instantiation is unchanged by the split into two files);
-//   MFC2_BODY_AS_KERNEL 0: as the device function conv_f16x2_body(p, bid) that conv_group_kernel (conv_f16x2.h) runs for the workgroups of one
-//                          of the TWO convolutions of a grouped launch, bid = the index inside that convolution.
+//   MFC2_BODY_AS_KERNEL 1: as the __global__ conv_f16x2_kernel (its workgroup index is blockIdx.x);
+//   MFC2_BODY_AS_KERNEL 0: as the device function conv_f16x2_body(p, bid, karg_off) that conv_group_kernel (conv_f16x2_group.h) runs for the
+//                          workgroups of one of the TWO convolutions of a grouped launch, bid = the index inside that convolution, karg_off =
+//                          the byte offset of its ConvP2 in the kernel-argument segment.
 template <int BM, int BN, int WM, int WN, int NST, int TERMS = 3>
 #if MFC2_BODY_AS_KERNEL
-__global__ __launch_bounds__(WM * WN * 64, 2) void conv_f16x2_kernel(const ConvP2 p) {
+__global__ __launch_bounds__(WM * WN * 64, 2) void conv_f16x2_kernel(const ConvP2 p_arg) {
 #else
-__device__ __forceinline__ void conv_f16x2_body(const ConvP2& p, const int bid) {
+__device__ __forceinline__ void conv_f16x2_body(const ConvP2& p_arg, const int bid, const int karg_off) {
 #endif
   static_assert(TERMS == 3 || TERMS == 1, "three product terms (fp16 pairs) or one (fp16)");
   constexpr int PC = TERMS == 3 ? 2 : 1;                    // pieces of a fragment that are read: hi and lo', or hi only
@@ -25,12 +25,100 @@ __device__ __forceinline__ void conv_f16x2_body(const ConvP2& p, const int bid) 
   static_assert((NR + NF - 1) / NF <= 3, "at most three reads per slot");
 
   extern __shared__ __attribute__((aligned(1024))) char smem[];
-  MFC2_STAMP(0)
+#if MFC2_HZ & 512
+  { const ConvP2& p = p_arg; MFC2_STAMP(0) }   // (the entry, ahead of the argument burst)
+#endif
+  ConvP2 p_own = p_arg;       // (taken apart into registers: never in memory)
+  MFC2_RAMP_ARGS(p_own)       // the ramp's part of the argument in one burst of scalar loads, one wait (conv_f16x2.h)
+  const ConvP2& p = p_own;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
 
+  // per-pixel (= per-lane) operand scales: the accumulators hold sum(w 2^-wexp * x 2^-e), e = e1 or e2 by source; the source switch of
+  // the K loop and the epilogue need the exponents e = scale_exp_of(bound[sample of the lane's pixel]), the epilogue the lane's 8 bias values.
+  // MFC2_EXPS_EARLY selects where they are fetched (A/B builds: medfusion_amd.build.build_variant(..., conv_flags=["-DMFC2_EXPS_EARLY=1"])):
+  //   2 (the product build): ALL loads -- 2 TM bounds, 2 bias quads, independent of each other -- are issued at the kernel's entry, as soon
+  //     as m0 is known and AHEAD of the address arithmetic (~1 us, which hides their round trip); they are converted to exponents right in
+  //     front of the first DMA (MFC2_PIXEL_EXPS_CONVERT: the one place that waits for them, with nothing of the pipeline in flight yet), and
+  //     the loop and the epilogue carry the 2 TM exponents.  From the first DMA on vmcnt counts DMA only: the counted waits of the prologue
+  //     and of the last NST iterations are exact (g resp. r - 1 chunk groups of NL instructions stay in flight, nothing younger exists),
+  //     and the compiler has no pending load to place a wait for between the first DMA and the first barrier
+  //     (tests/test_conv_ramp_isa_cpu.py; profiles/ramp_round_trips.txt).
+  //   1 (rounds 3 - 6): the raw bounds are loaded BEHIND the prologue's DMA and converted where they are used.  The conversion is loop-
+  //     invariant, so the compiler hoists it in front of the loop and puts a full vmcnt(0) behind every bound load: each wave waits for ALL
+  //     NST prologue stages plus 2 TM dependent round trips before its first matrix instruction.
+  //   0 (round 2): bounds and bias fetched where they are used (a dependent ~1.5 us round trip at the top of the epilogue).
+#ifndef MFC2_EXPS_EARLY
+#define MFC2_EXPS_EARLY 2
+#endif
+#if MFC2_EXPS_EARLY == 2
+#define MFC2_PIXEL_EXPS_DECL()                                                                                          \
+  float pb1[TM] = {}, pb2[TM] = {};   /* the raw bounds, in flight until MFC2_PIXEL_EXPS_CONVERT */                      \
+  int pe1[TM] = {}, pe2[TM] = {};     /* their scale exponents (0: unscaled source) */                                  \
+  f32x4 eb0 = {0.f, 0.f, 0.f, 0.f}, eb1 = {0.f, 0.f, 0.f, 0.f};   /* the 8 bias values this lane adds in the epilogue */
+// (rows past M take the bound of the last row: their values are never stored; a 128-row tile of an 8 x 8 image spans two samples, so the
+// lanes of one wave may read different bounds.  Every load is UNCONDITIONAL -- an absent array is replaced by the first bytes of x1, and
+// the value is dropped in MFC2_PIXEL_EXPS_CONVERT: a load under `if (p.bound1)` is waited for at the end of its own branch, i.e. the
+// 2 TM + 2 round trips run one after the other.)
+#define MFC2_PIXEL_EXPS_ISSUE()                                                                                         \
+  {                                                                                                                     \
+    const float* any_ = reinterpret_cast<const float*>(p.x1);                                                           \
+    _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                                                    \
+      const int pm_ = min(m0 + wm * FM + i * 32 + (lane & 31), p.M - 1);                                                \
+      const int pn_ = pm_ / p.HWout;                                                                                    \
+      pb1[i] = *(p.bound1 ? p.bound1 + pn_ : any_);                                                                     \
+      pb2[i] = *((p.bound2 && p.C2 > 0) ? p.bound2 + pn_ : any_);                                                       \
+    }                                                                                                                   \
+    const float* bp_ = ((p.splitk == 1 || p.tree) && p.bias) ? p.bias + (n0 + wn * FN + (lane % (FN / 8)) * 8) : any_;  \
+    eb0 = *reinterpret_cast<const f32x4*>(bp_);                                                                         \
+    eb1 = *reinterpret_cast<const f32x4*>(bp_ + 4);                                                                     \
+  }
+// the empty asm statements are uses in straight-line code: the loads are waited for HERE, once, and the exponents are values the compiler
+// cannot re-derive from the bounds later
+#define MFC2_PIXEL_EXPS_CONVERT()                                                                                       \
+  _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                                                      \
+    pe1[i] = p.bound1 ? scale_exp_of(pb1[i]) : 0;                                                                       \
+    pe2[i] = (p.bound2 && p.C2 > 0) ? scale_exp_of(pb2[i]) : 0;                                                         \
+    asm volatile("" : "+v"(pe1[i]), "+v"(pe2[i]));                                                                      \
+  }                                                                                                                     \
+  if (!((p.splitk == 1 || p.tree) && p.bias)) { eb0 = f32x4{0.f, 0.f, 0.f, 0.f}; eb1 = eb0; }                           \
+  asm volatile("" : "+v"(eb0), "+v"(eb1));
+#define MFC2_PIXEL_EXPS_LOAD()
+#define MFC2_PIXEL_EXPS(I) const int e1_ = pe1[I], e2_ = pe2[I];
+#elif MFC2_EXPS_EARLY
+#define MFC2_PIXEL_EXPS_DECL()                                                                                          \
+  float pb1[TM] = {}, pb2[TM] = {};   /* the raw bounds: converted where they are used */                               \
+  f32x4 eb0 = {0.f, 0.f, 0.f, 0.f}, eb1 = {0.f, 0.f, 0.f, 0.f};   /* the 8 bias values this lane adds in the epilogue */
+#define MFC2_PIXEL_EXPS_ISSUE()
+#define MFC2_PIXEL_EXPS_CONVERT()
+// issued BEHIND the DMA of the prologue (loads return in order: the counted vmcnt waits see 2 TM + 2 younger loads and wait for them too)
+#define MFC2_PIXEL_EXPS_LOAD()                                                                                          \
+  _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                                                      \
+    const int pm_ = min(m0 + wm * FM + i * 32 + (lane & 31), p.M - 1);                                                  \
+    const int pn_ = pm_ / p.HWout;                                                                                      \
+    pb1[i] = p.bound1 ? p.bound1[pn_] : 0.f;                                                                            \
+    pb2[i] = (p.bound2 && p.C2 > 0) ? p.bound2[pn_] : 0.f;                                                              \
+  }                                                                                                                     \
+  if ((p.splitk == 1 || p.tree) && p.bias) {                                                                            \
+    const int bc0_ = n0 + wn * FN + (lane % (FN / 8)) * 8;                                                              \
+    eb0 = *reinterpret_cast<const f32x4*>(p.bias + bc0_);                                                               \
+    eb1 = *reinterpret_cast<const f32x4*>(p.bias + bc0_ + 4);                                                           \
+  }
+#define MFC2_PIXEL_EXPS(I) const int e1_ = p.bound1 ? scale_exp_of(pb1[I]) : 0, e2_ = (p.bound2 && p.C2 > 0) ? scale_exp_of(pb2[I]) : 0;
+#else
+#define MFC2_PIXEL_EXPS_DECL()
+#define MFC2_PIXEL_EXPS_ISSUE()
+#define MFC2_PIXEL_EXPS_CONVERT()
+#define MFC2_PIXEL_EXPS_LOAD()
+#define MFC2_PIXEL_EXPS(I)                                                                                              \
+    const int pm_ = min(m0 + wm * FM + (I) * 32 + (lane & 31), p.M - 1);                                                \
+    const int pn_ = pm_ / p.HWout;                                                                                      \
+    const int e1_ = p.bound1 ? scale_exp_of(p.bound1[pn_]) : 0;                                                         \
+    const int e2_ = (p.bound2 && p.C2 > 0) ? scale_exp_of(p.bound2[pn_]) : 0;
+#endif
+  MFC2_PIXEL_EXPS_DECL()
   const int total = p.tiles_m * p.tiles_n * p.splitk;
   const int logical = xcd_remap2(MFC2_BID, total);
   int tile_m = logical % p.tiles_m;
@@ -57,6 +145,7 @@ __device__ __forceinline__ void conv_f16x2_body(const ConvP2& p, const int bid) 
     kz = r2 / ncomp;
   }
   const int m0 = tile_m * BM, n0 = tile_n * BN;
+  MFC2_PIXEL_EXPS_ISSUE()   // (MFC2_EXPS_EARLY == 2: the bound and bias loads, ahead of the address arithmetic -- see MFC2_PIXEL_EXPS_DECL)
   const int cg_beg = kz * p.cg_per_split;
   const int cg_end = min(p.cgroups, cg_beg + p.cg_per_split);
   const int taps = p.KH * p.KW;
@@ -197,44 +286,8 @@ __device__ __forceinline__ void conv_f16x2_body(const ConvP2& p, const int bid) 
 
   f16x8 fx[2][TM][2], fw[2][TN][2];   // [step][sub-tile][piece]
 
-  // per-pixel (= per-lane) operand scales: the accumulators hold sum(w 2^-wexp * x 2^-e), e = e1 or e2 by source.  The exponents are read
-  // from the bound arrays HERE, ahead of the first DMA (their round trip hides behind it; loads return in order, so the counted vmcnt waits
-  // of the pipeline are unaffected), and stay in 2 TM registers: fetched at the top of the epilogue they were a dependent ~1.5 us round trip
-  // with nothing to hide behind (scripts/conv_timeline.py: drain 4.2 us of a 57 us launch).
   const bool first_src1 = cg_beg * 32 < p.C1, last_src2 = (cg_end - 1) * 32 >= p.C1;
   const int it_sw = __builtin_amdgcn_readfirstlane((first_src1 && last_src2) ? (p.C1 / 32 - cg_beg) * taps : -1);   // first iteration that reads the second source
-#ifndef MFC2_EXPS_EARLY
-#define MFC2_EXPS_EARLY 1   // 0: the round-2 form (bounds fetched where they are used), for A/B builds
-#endif
-#if MFC2_EXPS_EARLY
-#define MFC2_PIXEL_EXPS_DECL()                                                                                          \
-  float pb1[TM] = {}, pb2[TM] = {};   /* the raw bounds: converted where they are used, nothing waits for them up here */ \
-  f32x4 eb0 = {0.f, 0.f, 0.f, 0.f}, eb1 = {0.f, 0.f, 0.f, 0.f};   /* the 8 bias values this lane adds in the epilogue */
-// issued BEHIND the DMA of the prologue (ahead of it they delayed the first chunk by 0.5 us: loads return in order); the counted vmcnt
-// waits then see 2 TM younger loads, i.e. at worst wait for that many loads of the next chunk as well
-#define MFC2_PIXEL_EXPS_LOAD()                                                                                          \
-  _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                                                      \
-    const int pm_ = min(m0 + wm * FM + i * 32 + (lane & 31), p.M - 1);                                                  \
-    const int pn_ = pm_ / p.HWout;                                                                                      \
-    pb1[i] = p.bound1 ? p.bound1[pn_] : 0.f;                                                                            \
-    pb2[i] = (p.bound2 && p.C2 > 0) ? p.bound2[pn_] : 0.f;                                                              \
-  }                                                                                                                     \
-  if ((p.splitk == 1 || p.tree) && p.bias) {                                                                            \
-    const int bc0_ = n0 + wn * FN + (lane % (FN / 8)) * 8;                                                              \
-    eb0 = *reinterpret_cast<const f32x4*>(p.bias + bc0_);                                                               \
-    eb1 = *reinterpret_cast<const f32x4*>(p.bias + bc0_ + 4);                                                           \
-  }
-#define MFC2_PIXEL_EXPS(I) const int e1_ = p.bound1 ? scale_exp_of(pb1[I]) : 0, e2_ = (p.bound2 && p.C2 > 0) ? scale_exp_of(pb2[I]) : 0;
-#else
-#define MFC2_PIXEL_EXPS_DECL()
-#define MFC2_PIXEL_EXPS_LOAD()
-#define MFC2_PIXEL_EXPS(I)                                                                                              \
-    const int pm_ = min(m0 + wm * FM + (I) * 32 + (lane & 31), p.M - 1);                                                \
-    const int pn_ = pm_ / p.HWout;                                                                                      \
-    const int e1_ = p.bound1 ? scale_exp_of(p.bound1[pn_]) : 0;                                                         \
-    const int e2_ = (p.bound2 && p.C2 > 0) ? scale_exp_of(p.bound2[pn_]) : 0;
-#endif
-  MFC2_PIXEL_EXPS_DECL()
 #define MFC2_SOURCE_SWITCH()                                                                                            \
   if (__builtin_expect(it == it_sw, 0)) {                                                                               \
     if constexpr (MFC2_HZ_ON(0)) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");                                     \
@@ -267,6 +320,7 @@ __device__ __forceinline__ void conv_f16x2_body(const ConvP2& p, const int bid) 
     if constexpr (t_ == 2) accx[i_][j_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fw[S][j_][PC - 1], fx[S][i_][0], accx[i_][j_], 0, 0, 0); \
   }
 
+  MFC2_PIXEL_EXPS_CONVERT()
   if (nit > 0) {
     // ---- prologue: up to NST chunks in flight, wait for the first
     MFC2_CHUNK_SETUP()
@@ -369,8 +423,11 @@ __device__ __forceinline__ void conv_f16x2_body(const ConvP2& p, const int bid) 
   }
 
   MFC2_STAMP(2)
+  {
+    MFC2_EPILOGUE_ARGS(MFC2_KARG_OFF)   // (`p` from here on: the argument segment, conv_f16x2.h)
 #define MFC2_EPILOGUE_LDS_BYTES (NST * STAGE)
 #include "conv_f16x2_epilogue.inc"
 #undef MFC2_EPILOGUE_LDS_BYTES
-  MFC2_STAMP(3)
+    MFC2_STAMP(3)
+  }
 }

@@ -131,7 +131,8 @@
   const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(out, 0, (unsigned)((long)p.M * p.Cout * 4), 0x00020000);
 #endif
 #if MFC2_EXPS_EARLY
-  // the bias was fetched behind the prologue's DMA.  It must be KNOWN to have arrived before the store passes below: they sit under
+  // the bias was fetched in the ramp (MFC2_EXPS_EARLY == 2: at the entry, waited for in front of the first DMA -- nothing is pending here; == 1:
+  // behind the prologue's DMA).  It must be KNOWN to have arrived before the store passes below: they sit under
   // per-row `if (m < M)` branches, and with a load still pending on some path the compiler re-waits vmcnt(0) in every pass -- which on this
   // target also waits for the previous pass's output STORES (they count in vmcnt): eight serialised store round trips per workgroup,
   // 2.9 us of a 57 us launch (scripts/conv_timeline.py).  The empty asm is a use in straight-line code: one wait, here.

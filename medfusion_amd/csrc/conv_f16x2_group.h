@@ -18,24 +18,26 @@ template <int BM_, int BN_, int WM_, int WN_, int NST_>
 struct PlainTile {
   static constexpr int threads = WM_ * WN_ * 64;
   static constexpr size_t lds = (size_t)NST_ * (BM_ + BN_) * 128u;
-  template <int TERMS> static __device__ __forceinline__ void run(const ConvP2& p, int bid) { conv_f16x2_body<BM_, BN_, WM_, WN_, NST_, TERMS>(p, bid); }
+  template <int TERMS> static __device__ __forceinline__ void run(const ConvP2& p, int bid, int karg_off) { conv_f16x2_body<BM_, BN_, WM_, WN_, NST_, TERMS>(p, bid, karg_off); }
 };
 template <int BM_, int BN_, int WM_, int WN_, int HG_>
 struct HaloTile {
   static constexpr int threads = WM_ * WN_ * 64;
   static constexpr size_t lds = (size_t)2 * HG_ * (WM_ * WN_) * 1024 + (size_t)3 * BN_ * 128;
-  template <int TERMS> static __device__ __forceinline__ void run(const ConvP2& p, int bid) { conv_halo_body<BM_, BN_, WM_, WN_, HG_, TERMS>(p, bid); }
+  template <int TERMS> static __device__ __forceinline__ void run(const ConvP2& p, int bid, int karg_off) { conv_halo_body<BM_, BN_, WM_, WN_, HG_, TERMS>(p, bid, karg_off); }
 };
 
-// workgroups [0, na): convolution A (pa); [na, na + nb): convolution B (pb)
+// workgroups [0, na): convolution A (pa); [na, na + nb): convolution B (pb).  The two descriptors are the first two explicit arguments: pa
+// at byte 0 of the kernel-argument segment, pb right behind it (its alignment is 8 and sizeof(ConvP2) is a multiple of 8) -- the offsets the
+// bodies read their epilogue's fields at (conv_f16x2.h: MFC2_EPILOGUE_ARGS; tests/test_conv_ramp_isa_cpu.py checks them in the metadata).
 template <class A, class B, int TERMS>
 __global__ __launch_bounds__(A::threads, 2) void conv_group_kernel(const ConvP2 pa, const ConvP2 pb, const int na) {
   static_assert(A::threads == B::threads, "one workgroup size");
   const int bid = (int)blockIdx.x;
   if (bid < na) {
-    A::template run<TERMS>(pa, bid);
+    A::template run<TERMS>(pa, bid, 0);
   } else {
-    B::template run<TERMS>(pb, bid - na);
+    B::template run<TERMS>(pb, bid - na, (int)sizeof(ConvP2));
   }
 }
 

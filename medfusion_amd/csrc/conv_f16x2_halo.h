@@ -25,13 +25,17 @@ namespace mfc2 {
 // HG: 1-KB halo pieces per wave and chunk (8 halo pixels each): HG x 8 x NW >= halo pixels of the tile
 #define MFC2_BODY_AS_KERNEL 1
 #define MFC2_BID blockIdx.x
+#define MFC2_KARG_OFF 0
 #include "conv_f16x2_halo_body.inc"
 #undef MFC2_BODY_AS_KERNEL
 #undef MFC2_BID
+#undef MFC2_KARG_OFF
 #define MFC2_BODY_AS_KERNEL 0
 #define MFC2_BID bid
+#define MFC2_KARG_OFF karg_off
 #include "conv_f16x2_halo_body.inc"
 #undef MFC2_BODY_AS_KERNEL
 #undef MFC2_BID
+#undef MFC2_KARG_OFF
 
 }  // namespace mfc2

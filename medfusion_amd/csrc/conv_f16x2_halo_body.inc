@@ -1,11 +1,11 @@
 // conv_f16x2_halo_body.inc -- one workgroup of the halo convolution, included twice by conv_f16x2_halo.h: as the __global__ conv_halo_kernel
-// (MFC2_BODY_AS_KERNEL 1; the product kernels, token for token what they were) and as the device function conv_halo_body(p, bid) of a grouped
-// launch (MFC2_BODY_AS_KERNEL 0) -- see conv_f16x2_body.inc.
+// (MFC2_BODY_AS_KERNEL 1) and as the device function conv_halo_body(p, bid, karg_off) of a grouped launch (MFC2_BODY_AS_KERNEL 0) -- see
+// conv_f16x2_body.inc.
 template <int BM, int BN, int WM, int WN, int HG, int TERMS = 3>
 #if MFC2_BODY_AS_KERNEL
-__global__ __launch_bounds__(WM * WN * 64, 2) void conv_halo_kernel(const ConvP2 p) {
+__global__ __launch_bounds__(WM * WN * 64, 2) void conv_halo_kernel(const ConvP2 p_arg) {
 #else
-__device__ __forceinline__ void conv_halo_body(const ConvP2& p, const int bid) {
+__device__ __forceinline__ void conv_halo_body(const ConvP2& p_arg, const int bid, const int karg_off) {
 #endif
   static_assert(TERMS == 3 || TERMS == 1, "three product terms (fp16 pairs) or one (fp16)");
   constexpr int PC = TERMS == 3 ? 2 : 1;
@@ -22,6 +22,9 @@ __device__ __forceinline__ void conv_halo_body(const ConvP2& p, const int bid) {
   constexpr int NM = TERMS * TM * TN;
 
   extern __shared__ __attribute__((aligned(1024))) char smem[];
+  ConvP2 p_own = p_arg;       // the ramp's part of the argument in one burst of scalar loads, one wait (conv_f16x2.h: MFC2_RAMP_ARGS)
+  MFC2_RAMP_ARGS(p_own)
+  const ConvP2& p = p_own;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
@@ -34,6 +37,8 @@ __device__ __forceinline__ void conv_halo_body(const ConvP2& p, const int bid) {
   const int tile_n = p.walk_n_fast ? logical % p.tiles_n : rest % p.tiles_n;
   const int kz = p.walk_n_fast ? logical / (p.tiles_n * p.tiles_m) : rest / p.tiles_n;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
+  MFC2_PIXEL_EXPS_DECL()    // (operand scale exponents of this lane's pixels and its bias values: conv_f16x2_body.inc)
+  MFC2_PIXEL_EXPS_ISSUE()   // (MFC2_EXPS_EARLY == 2: their loads, ahead of the halo arithmetic)
   const int cg_beg = kz * p.cg_per_split;
   const int cg_end = min(p.cgroups, cg_beg + p.cg_per_split);
   const int nchunks = cg_end - cg_beg;
@@ -220,7 +225,7 @@ __device__ __forceinline__ void conv_halo_body(const ConvP2& p, const int bid) {
     ws = wsn_;                                                                                                            \
   }
 
-  MFC2_PIXEL_EXPS_DECL()   // (operand scale exponents of this lane's pixels: conv_f16x2.h)
+  MFC2_PIXEL_EXPS_CONVERT()   // (MFC2_EXPS_EARLY == 2: the one wait for them, in front of the first DMA -- vmcnt counts DMA only from here on)
   if (nchunks > 0) {
     // ---- prologue: halo of the first chunk, weights of its first two taps; wait, barrier, first fragments
     int cc = cg_beg;
@@ -272,7 +277,10 @@ __device__ __forceinline__ void conv_halo_body(const ConvP2& p, const int bid) {
     MFC2_WAIT_VM(0);   // (the zero-filling prefetches of the last taps)
   }
 
+  {
+    MFC2_EPILOGUE_ARGS(MFC2_KARG_OFF)   // (`p` from here on: the argument segment, conv_f16x2.h)
 #define MFC2_EPILOGUE_LDS_BYTES (WBASE + NST * WST)
 #include "conv_f16x2_epilogue.inc"
 #undef MFC2_EPILOGUE_LDS_BYTES
+  }
 }

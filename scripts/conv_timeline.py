@@ -18,6 +18,7 @@ from medfusion_amd import lib as L
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--fused", action="store_true", help="time mf_conv2d_f16x2_gn_apply (GroupNorm + Swish + residual + embedding inside the launch) instead")
+    ap.add_argument("--wino", action="store_true", help="the 3x3 shapes in their Winograd form: the stamps are those of the component-GEMM launch (descriptor with upsample = 3)")
     ap.add_argument("--shapes", default="16,32,32,256,0,256,3:52:1;16,16,16,512,0,512,3:52:2;16,8,8,1024,0,1024,3:53:4;16,32,32,512,0,256,1:52:1")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -38,7 +39,11 @@ def main():
         parts = K.conv_gn_parts(d, 32)
         y = torch.empty((n, h, w, co), device=dev)
         setter(None)
-        if args.fused:
+        if args.wino:
+            uh = K.split_weight_f16x2(K.wino_pack_weight((torch.randn((co, c1 + c2, 3, 3), generator=g) * 0.02).to(dev)))
+            wparts = K.wino_gn_parts(d, 32)
+            run = lambda: K.conv2d_wino_f16x2(x, uh, b, d, gn_groups=32, gn_parts=wparts)
+        elif args.fused:
             words = K.conv_fuse_words(d, 32)
             gamma, beta = torch.rand((co,), device=dev) + 0.5, torch.randn((co,), device=dev) * 0.1
             res = torch.randn((n, h, w, co), device=dev)
