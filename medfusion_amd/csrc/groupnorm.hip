@@ -190,6 +190,179 @@ __device__ __forceinline__ GnChan gn_chan_consts(const float* sm, const float* _
   return k;
 }
 
+#if MF_PASS_CHAIN == 2
+// gn_chan_consts with UNCONDITIONAL loads (an absent array reads kZeros8; ga / be are read under `if (gamma)`, em under `if (emb)` only): the
+// three loads leave together, none is merged with a constant at the end of an `if`
+__device__ __forceinline__ GnChan gn_chan_consts_any(const float* sm, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                     const float* __restrict__ emb_row, int c, int cpg) {
+  GnChan k;
+  const float4 ga = *reinterpret_cast<const float4*>(gamma ? gamma + c : kZeros8), be = *reinterpret_cast<const float4*>(gamma ? beta + c : kZeros8);
+  k.em = *reinterpret_cast<const float4*>(emb_row ? emb_row + c : kZeros8);
+  k.ga[0] = ga.x; k.ga[1] = ga.y; k.ga[2] = ga.z; k.ga[3] = ga.w;
+  k.be[0] = be.x; k.be[1] = be.y; k.be[2] = be.z; k.be[3] = be.w;
+  if (cpg % 4 == 0) {   // (c is a multiple of 4: one group)
+    const int g = c / cpg;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { k.mean[i] = sm[2 * g]; k.rstd[i] = sm[2 * g + 1]; }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { const int g = (c + i) / cpg; k.mean[i] = sm[2 * g]; k.rstd[i] = sm[2 * g + 1]; }
+  }
+  return k;
+}
+
+// MF_PASS_CHAIN == 2 (split_f16.h): the same pass with its memory requests in the order it needs them.  At the entry, in straight-line code
+// and without a condition on any load: the thread's first record, the two bounds, gamma / beta / embedding row of the thread's channels, the
+// first 256 slots of the residual's bound, THEN round 0 of x and of the residual (an absent operand reads kZeros8, an index past the end is
+// clamped, the residual's 16 bytes come as two 8-byte halves whatever its kind and are decoded where they are used).  The record is waited
+// for by COUNT (loads retire in order: everything requested behind it stays in flight), each round of x is waited for once, in front of its
+// first element, so that no wait stands between the stores of one element and the arithmetic of the next, and the barriers order LDS only.
+// The form of rounds 3 - 6 (below) loaded the records BEHIND round 0 and waited for everything, fetched bounds and channel constants after the
+// second barrier, and waited for the stores of every element (profiles/pass_round_trips.txt).  FIXED_C is a template parameter here: the
+// per-element reload of the channel constants of the other form (loads behind the statistics, by necessity) is code of another kernel.
+template <bool SPLIT, int U, bool FIXED_C>
+__global__ __launch_bounds__(256) void gn_apply_part_kernel(const float* __restrict__ x, const double* __restrict__ partial, int parts, double count, float eps,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            const float* __restrict__ residual, const float* __restrict__ emb, long emb_stride,
+                                                            float* __restrict__ out, int HW, int C, int G, int act, const GnSplit sp) {
+  __shared__ float sm[2 * 256 + 4];
+  __shared__ double sd[2 * 256];
+  const int n = blockIdx.y, tid = threadIdx.x;
+  const int C4 = C >> 2, cpg = C / G;
+  const unsigned per4 = (unsigned)HW * (unsigned)C4;   // (host: < 2^31)
+  const long base = (long)n * per4;
+  constexpr unsigned SPAN = 256u * U;
+  const unsigned step = gridDim.x * SPAN;
+  const bool res_p = SPLIT && sp.res_pairs != nullptr;                                    // the residual lives as fp16 pairs only
+  const bool res_f = !res_p && residual != nullptr;
+  constexpr bool fixed_c = FIXED_C;   // (host: 256 % (C / 4) == 0, every published width -- a thread keeps its 4 channels through every round)
+  const float* emb_row = emb ? emb + (long)n * emb_stride : nullptr;
+  const int PPT = 256 / G, g = tid % G, kk = tid / G;
+
+  // ---- the entry burst
+  const double* rp0 = partial + (((long)n * parts + min(kk, parts - 1)) * G + g) * 2;
+  const double rec_s = rp0[0], rec_q = rp0[1];
+  float rbv = 0.f, ebv = 0.f, sl0 = 0.f;
+  if (SPLIT) {
+    rbv = *(sp.res_bound ? sp.res_bound + n : kZeros8);
+    ebv = *(sp.emb_bound ? sp.emb_bound + n : kZeros8);
+    sl0 = *((sp.res_slots && sp.res_nslots > 0) ? sp.res_slots + (long)n * sp.res_nslots + min(tid, sp.res_nslots - 1) : kZeros8);   // (a slot read twice changes no maximum)
+  }
+  const int cfix = fixed_c ? (tid % C4) * 4 : 0;
+  float4 g4 = *reinterpret_cast<const float4*>(gamma ? gamma + cfix : kZeros8), e4 = *reinterpret_cast<const float4*>(gamma ? beta + cfix : kZeros8);
+  float4 em4 = *reinterpret_cast<const float4*>(emb_row ? emb_row + cfix : kZeros8);
+  const char* const rbase = res_p ? reinterpret_cast<const char*>(sp.res_pairs) : res_f ? reinterpret_cast<const char*>(residual) : reinterpret_cast<const char*>(kZeros8);
+  const int rhalf = res_p ? 16 : 8;
+  float4 v[U];
+  uint2 ra[U], rb[U];
+  unsigned jw = blockIdx.x * SPAN;
+#define GN_LOAD_ROUND()                                                                                                  \
+  _Pragma("unroll") for (int u = 0; u < U; ++u) {                                                                        \
+    const long e = (base + min(jw + 256u * u + tid, per4 - 1u)) * 4;                                                     \
+    v[u] = *reinterpret_cast<const float4*>(x + e);                                                                      \
+    const char* q_ = rbase + (res_p ? (e >> 3) * 32 + ((e >> 2) & 1) * 8 : res_f ? e * 4 : 0L);                          \
+    ra[u] = *reinterpret_cast<const uint2*>(q_);                                                                         \
+    rb[u] = *reinterpret_cast<const uint2*>(q_ + rhalf);   /* pairs: [lo' x 4], 16 bytes behind [hi x 4]; fp32: the second half of the float4 */ \
+  }
+  GN_LOAD_ROUND()
+
+  {   // the sample's statistics: thread (kk, g) adds records kk, kk + PPT, ...; the first G threads add the PPT sums of their group
+    double s = 0, q = 0;
+    if (kk < PPT) {
+      if (kk < parts) { s += rec_s; q += rec_q; }
+      for (int k = kk + PPT; k < parts; k += PPT) {
+        const double* p = partial + (((long)n * parts + k) * G + g) * 2;
+        s += p[0]; q += p[1];
+      }
+    }
+    sd[tid] = s; sd[256 + tid] = q;
+  }
+  if (SPLIT && sp.res_slots) {   // the residual's measured bound, straight from the slots its convolution wrote (no finalize launch)
+    float m = fmaxf(0.f, sl0);
+    for (int i = tid + 256; i < sp.res_nslots; i += 256) m = fmaxf(m, sp.res_slots[(long)n * sp.res_nslots + i]);
+    m = wave_max(m);
+    if ((tid & 63) == 0) sm[2 * 256 + (tid >> 6)] = m;
+  }
+  MF_LDS_BARRIER();
+  if (tid < G) {
+    double s = sd[tid], q = sd[256 + tid];
+    for (int k2 = 1; k2 < PPT; ++k2) { s += sd[k2 * G + tid]; q += sd[256 + k2 * G + tid]; }
+    const double mean = s / count;
+    double var = q / count - mean * mean;
+    if (var < 0) var = 0;
+    sm[2 * tid] = (float)mean;
+    sm[2 * tid + 1] = (float)(1.0 / sqrt(var + (double)eps));
+  }
+  MF_LDS_BARRIER();
+  float sc = 1.f, rsc = 1.f, obound = 0.f;
+  if (SPLIT) {
+    const float rbd = sp.res_slots ? fmaxf(fmaxf(sm[512], sm[513]), fmaxf(sm[514], sm[515])) : rbv;   // (rbv, ebv: 0.f from kZeros8 when absent)
+    obound = sp.bconst + rbd + ebv;
+    sc = exp2i(-scale_exp_of(obound));
+    if (res_p) rsc = exp2i(scale_exp_of(rbv));
+  }
+  GnChan kc;
+  {   // (the channel constants of gn_chan_consts from the registers of the entry burst; ga / be are read under `if (gamma)`, em under `if (emb)`)
+    if (cpg % 4 == 0) {
+      const int gq = cfix / cpg;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { kc.mean[i] = sm[2 * gq]; kc.rstd[i] = sm[2 * gq + 1]; }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { const int gq = (cfix + i) / cpg; kc.mean[i] = sm[2 * gq]; kc.rstd[i] = sm[2 * gq + 1]; }
+    }
+    asm volatile("" : "+v"(g4.x), "+v"(g4.y), "+v"(g4.z), "+v"(g4.w), "+v"(e4.x), "+v"(e4.y), "+v"(e4.z), "+v"(e4.w), "+v"(em4.x), "+v"(em4.y), "+v"(em4.z), "+v"(em4.w));
+    kc.ga[0] = g4.x; kc.ga[1] = g4.y; kc.ga[2] = g4.z; kc.ga[3] = g4.w;
+    kc.be[0] = e4.x; kc.be[1] = e4.y; kc.be[2] = e4.z; kc.be[3] = e4.w;
+    kc.em = em4;
+  }
+
+  for (;;) {
+    // the ONE wait of the round, in code every lane runs: a first use inside `if (j < per4)` would be waited for again by the next element, by
+    // a count that then includes the stores in between (vmcnt counts stores)
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      asm volatile("" : "+v"(v[u].x), "+v"(v[u].y), "+v"(v[u].z), "+v"(v[u].w), "+v"(ra[u].x), "+v"(ra[u].y), "+v"(rb[u].x), "+v"(rb[u].y));
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const unsigned j = jw + 256u * u + tid;
+      if (j < per4) {
+        if (!fixed_c) {
+          // (no published width: the channel constants are fetched per element, the three loads together, and waited for once)
+          kc = gn_chan_consts_any(sm, gamma, beta, emb_row, (int)(j % (unsigned)C4) * 4, cpg);
+          asm volatile("" : "+v"(kc.ga[0]), "+v"(kc.ga[1]), "+v"(kc.ga[2]), "+v"(kc.ga[3]), "+v"(kc.be[0]), "+v"(kc.be[1]), "+v"(kc.be[2]), "+v"(kc.be[3]),
+                            "+v"(kc.em.x), "+v"(kc.em.y), "+v"(kc.em.z), "+v"(kc.em.w));
+        }
+        float e[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          float t = (e[k] - kc.mean[k]) * kc.rstd[k];
+          if (gamma) t = t * kc.ga[k] + kc.be[k];
+          if (act == 1) t = swish_apply(t);
+          e[k] = t;
+        }
+        if (res_p) {
+          const sf_f16x2 h0 = __builtin_bit_cast(sf_f16x2, ra[u].x), h1 = __builtin_bit_cast(sf_f16x2, ra[u].y),
+                         l0 = __builtin_bit_cast(sf_f16x2, rb[u].x), l1 = __builtin_bit_cast(sf_f16x2, rb[u].y);
+          e[0] += ((float)h0[0] + (float)l0[0] * kLoInv) * rsc; e[1] += ((float)h0[1] + (float)l0[1] * kLoInv) * rsc;
+          e[2] += ((float)h1[0] + (float)l1[0] * kLoInv) * rsc; e[3] += ((float)h1[1] + (float)l1[1] * kLoInv) * rsc;
+        } else if (res_f) {
+          e[0] += __uint_as_float(ra[u].x); e[1] += __uint_as_float(ra[u].y); e[2] += __uint_as_float(rb[u].x); e[3] += __uint_as_float(rb[u].y);
+        }
+        if (emb) { e[0] += kc.em.x; e[1] += kc.em.y; e[2] += kc.em.z; e[3] += kc.em.w; }
+        if (!SPLIT || out) *reinterpret_cast<float4*>(out + (base + j) * 4) = make_float4(e[0], e[1], e[2], e[3]);   // (null: pairs only)
+        if (SPLIT) store_split4<false>(sp.outs, (base + j) * 4, e[0], e[1], e[2], e[3], sc);   // (the bound is derived: no clamp, split_f16.h)
+      }
+    }
+    jw += step;
+    if (jw >= per4) break;
+    GN_LOAD_ROUND()
+  }
+#undef GN_LOAD_ROUND
+  // (behind the rounds: in front of them the wait for round 0 would wait for this store as well)
+  if (SPLIT && blockIdx.x == 0 && tid == 0) sp.out_bound[n] = obound;
+}
+#else
 template <bool SPLIT, int U>
 __global__ __launch_bounds__(256) void gn_apply_part_kernel(const float* __restrict__ x, const double* __restrict__ partial, int parts, double count, float eps,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -293,6 +466,7 @@ __global__ __launch_bounds__(256) void gn_apply_part_kernel(const float* __restr
   }
 #undef GN_LOAD_ROUND
 }
+#endif
 
 // max of |x| over this block's share of sample n -> partial[n][blockIdx.x * 4 + wave].  grid (blocks, N)
 __global__ __launch_bounds__(256) void maxabs_kernel(const float* __restrict__ x, float* __restrict__ partial, long per_sample4) {
@@ -422,15 +596,26 @@ int mf_gn_apply_from_partials_pairs_f32(const float* x, const double* gn_partial
   if (bps > cap) bps = cap;
   const GnSplit sp{out_split, nullptr, res_bound, emb_bound, bconst, out_bound, res_bound ? nullptr : res_bound_slots, res_nslots, residual_pairs};
   const double count = (double)HW * (C / G);
+#if MF_PASS_CHAIN == 2
+#define GN_PART_LAUNCH_(SPLIT_, U_, FIXED_)                                                                                                          \
+  MF_LAUNCH((gn_apply_part_kernel<SPLIT_, U_, FIXED_>), dim3((int)bps, N), dim3(256), 0, s, x, gn_partial, parts, count, eps, gamma, beta, residual, \
+            emb, (long)emb_stride, out, HW, C, G, act, sp)
+#define GN_PART_LAUNCH(SPLIT_, U_)                                                    \
+  do {                                                                                \
+    if (256 % (C / 4) == 0) GN_PART_LAUNCH_(SPLIT_, U_, true); else GN_PART_LAUNCH_(SPLIT_, U_, false); \
+  } while (0)
+#else
 #define GN_PART_LAUNCH(SPLIT_, U_)                                                                                                          \
   MF_LAUNCH((gn_apply_part_kernel<SPLIT_, U_>), dim3((int)bps, N), dim3(256), 0, s, x, gn_partial, parts, count, eps, gamma, beta, residual, emb, \
             (long)emb_stride, out, HW, C, G, act, sp)
+#endif
   if (out_split) {
     if (U == 4) GN_PART_LAUNCH(true, 4); else if (U == 2) GN_PART_LAUNCH(true, 2); else GN_PART_LAUNCH(true, 1);
   } else {
     if (U == 4) GN_PART_LAUNCH(false, 4); else if (U == 2) GN_PART_LAUNCH(false, 2); else GN_PART_LAUNCH(false, 1);
   }
 #undef GN_PART_LAUNCH
+#undef GN_PART_LAUNCH_
   return check_launch("gn_apply_from_partials");
 }
 

@@ -19,6 +19,31 @@ typedef _Float16 sf_f16x2 __attribute__((ext_vector_type(2)));
 
 constexpr float kLoScale = 2048.f, kLoInv = 1.f / 2048.f, kF16Max = 65504.f;
 
+// MF_PASS_CHAIN selects how the memory-bound passes around the convolutions (wino_tail_kernel in winograd.h, gn_apply_part_kernel in
+// groupnorm.hip) order their memory requests (A/B builds: medfusion_amd.build.build_variant(..., conv_flags=["-DMF_PASS_CHAIN=1"],
+// unit_flags={"groupnorm.hip": ["-DMF_PASS_CHAIN=1"]})):
+//   2 (the product build): everything that depends on nothing -- residual rows, records, bounds, gamma / beta / embedding row -- is requested at
+//     the kernel's entry with UNCONDITIONAL loads in straight-line code and waited for once, where it is first used; the barriers order LDS only
+//     and no wait stands behind a store.  Same values, same arithmetic, same order: bit-identical results (tests/test_pass_chain_gpu.py).
+//   1 (rounds 3 - 6): the loads sit under `if (present)` and in front of full waits, the barriers are __syncthreads() (which waits for every
+//     store): a chain of dependent round trips (profiles/pass_round_trips.txt).
+#ifndef MF_PASS_CHAIN
+#define MF_PASS_CHAIN 2
+#endif
+// what an ABSENT optional operand (null bias, no residual, no bound ...) is read from: a load under `if (p)` merges the loaded register with a
+// constant at the join, the merge is a copy, and the copy waits for the data right there -- an unconditional load of zeros merges nothing.
+// (Not `const`, and never written: a constant lives in another address space than the operands it stands in for, and a pointer that may be
+// either is a FLAT pointer -- flat loads return out of order and every wait behind one is a full wait.)
+__attribute__((unused, aligned(16))) static __device__ float kZeros8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+// a workgroup barrier that orders LDS traffic only (conv_f16x2_body.inc: MFC2_WAIT_LGKM0 + s_barrier): __syncthreads() also waits for every
+// global store in flight (vmcnt counts stores on gfx950), which a pass whose phases exchange data through LDS alone does not need
+#define MF_LDS_BARRIER()                                  \
+  do {                                                    \
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    \
+    __builtin_amdgcn_s_barrier();                         \
+    asm volatile("" ::: "memory");                        \
+  } while (0)
+
 // exponent s of the per-sample scale 2^-s for an upper bound of |x| (0, denormal, inf and NaN bounds are clamped to +-100)
 __device__ __forceinline__ int scale_exp_of(float bound) {
   const int e = (int)((__float_as_uint(bound) >> 23) & 0xffu) - 127;

@@ -86,6 +86,38 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const void* __restrict_
     const long r = i / C4;
     const int tile = (int)(r % T), n = (int)(r / T);
     const int ty = tile / TW, tx = tile - ty * TW;
+#if MF_PASS_CHAIN == 2
+    // MF_PASS_CHAIN == 2 (split_f16.h): the bound and the 16 patch rows are requested together -- a pixel outside the image reads the clamped
+    // pixel and is replaced by zero bits when the rows are decoded (the pair form of 0.f).  The form below loads under `if (inside)`: the zero
+    // it merges with makes every one of the 16 loads wait before the next is issued (profiles/pass_round_trips.txt).
+    const float b = *(xbound ? xbound + n : kZeros8);
+    uint2 ph[16], pl[16];
+#pragma unroll
+    for (int py = 0; py < 4; ++py)
+#pragma unroll
+      for (int px = 0; px < 4; ++px) {
+        const int y = min(max(2 * ty - 1 + py, 0), H - 1), x = min(max(2 * tx - 1 + px, 0), W - 1);
+        const long e = (((long)n * H + y) * W + x) * C + c4 * 4;
+        const uint2* gp = reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(xs) + (e >> 3) * 32 + ((e >> 2) & 1) * 8);
+        ph[4 * py + px] = gp[0]; pl[4 * py + px] = gp[2];   // [hi x 8] then [lo' x 8]: 16 bytes apart (wino_load_pairs4)
+      }
+    const float vb = 4.f * b;
+    // x = x' 2^s, v = transform(x') 2^s, stored as v 2^-sv: factor 2^(s - sv) (= 1/4 away from the clamps of scale_exp_of)
+    const float f = xbound ? exp2i(scale_exp_of(b)) * exp2i(-scale_exp_of(vb)) : 1.f;
+    float d[4][16];
+#pragma unroll
+    for (int py = 0; py < 4; ++py)
+#pragma unroll
+      for (int px = 0; px < 4; ++px) {
+        const int y = 2 * ty - 1 + py, x = 2 * tx - 1 + px, k = 4 * py + px;
+        const bool inside = (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
+        const uint2 h = inside ? ph[k] : make_uint2(0u, 0u), l = inside ? pl[k] : make_uint2(0u, 0u);
+        const sf_f16x2 h0 = __builtin_bit_cast(sf_f16x2, h.x), h1 = __builtin_bit_cast(sf_f16x2, h.y), l0 = __builtin_bit_cast(sf_f16x2, l.x),
+                       l1 = __builtin_bit_cast(sf_f16x2, l.y);
+        d[0][k] = (float)h0[0] + (float)l0[0] * kLoInv; d[1][k] = (float)h0[1] + (float)l0[1] * kLoInv;
+        d[2][k] = (float)h1[0] + (float)l1[0] * kLoInv; d[3][k] = (float)h1[1] + (float)l1[1] * kLoInv;
+      }
+#else
     const float b = xbound ? xbound[n] : 0.f;
     const float vb = 4.f * b;
     // x = x' 2^s, v = transform(x') 2^s, stored as v 2^-sv: factor 2^(s - sv) (= 1/4 away from the clamps of scale_exp_of)
@@ -100,6 +132,7 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const void* __restrict_
         if ((unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W) v = wino_load_pairs4(xs, (((long)n * H + y) * W + x) * C + c4 * 4);
         d[0][4 * py + px] = v.x; d[1][4 * py + px] = v.y; d[2][4 * py + px] = v.z; d[3][4 * py + px] = v.w;
       }
+#endif
 #pragma unroll
     for (int k = 0; k < 4; ++k) wino_bt_d_b(d[k]);
     const long e0 = ((long)n * T + tile) * C + c4 * 4;
@@ -272,9 +305,39 @@ __global__ __launch_bounds__(256) void wino_tail_kernel(const WinoTailP p) {
   const long plane = (long)p.N * T * C;
   const int c4 = tid % cq;   // (host: 256 % cq == 0 -- a thread keeps its 4 channels through every loop)
   // the residual rows of this thread's first RJ elements of phase 2 are requested NOW: they depend on nothing, and their round trip hides behind
-  // phase 1 instead of standing between the statistics and the stores (the tail is a chain of dependent memory round trips: every one removed
-  // is ~1.5 us of a 14 us launch at the 8 x 8 level)
+  // phase 1 instead of standing between the statistics and the stores.  The tail is a chain of dependent memory round trips, but with two
+  // workgroups per CU most of the chain is hidden behind the neighbour: taking 4 + 1 + 2 + 4 + 1 of them out (MF_PASS_CHAIN == 2) moved the
+  // launch from 14.38 to 14.12 us on the cfg2 step, not by the 3 - 5 us their count suggests (profiles/pass_round_trips.txt, sections 2 and 3)
   constexpr int RJ = 4;
+#if MF_PASS_CHAIN == 2
+  // MF_PASS_CHAIN == 2 (split_f16.h): the rows, and with them everything else the kernel reads besides M -- bias, gamma, beta, the embedding row,
+  // the two bounds, the first round of the residual's slots -- in ONE burst of unconditional loads.  An absent operand reads zeros (kZeros8), a
+  // row past the end reads the last row again, the residual's 16 bytes are fetched as two 8-byte halves whatever its kind (fp32: the halves
+  // of a float4, pairs: [hi x 4] and, 16 bytes on, [lo' x 4]) and decoded in phase 2.  Nothing here merges a loaded register with a constant,
+  // so no wait stands between the entry and the first load of M (tests/test_pass_chain_isa_cpu.py); the form of rounds 5 - 6 below waited
+  // RJ times in a row (profiles/pass_round_trips.txt).
+  const int nel = HW * cq, cc = c0 + c4 * 4;
+  const bool res_p = p.res_pairs != nullptr, res_f = !res_p && p.res_f32 != nullptr;
+  const char* const rbase = res_p ? reinterpret_cast<const char*>(p.res_pairs) : res_f ? reinterpret_cast<const char*>(p.res_f32) : reinterpret_cast<const char*>(kZeros8);
+  const int rhalf = res_p ? 16 : 8;
+  auto res_at = [&](int it) {   // address of the first half of element `it`'s residual
+    const long eo = ((long)n * HW + it / cq) * C + cc;
+    return rbase + (res_p ? (eo >> 3) * 32 + ((eo >> 2) & 1) * 8 : res_f ? eo * 4 : 0L);
+  };
+  uint2 rqa[RJ + 1], rqb[RJ + 1];   // (row RJ: the first round of the loop behind the RJ unrolled elements of phase 2, which keeps one round ahead)
+#pragma unroll
+  for (int j = 0; j <= RJ; ++j) {
+    const char* q = res_at(min(tid + 256 * j, nel - 1));
+    rqa[j] = *reinterpret_cast<const uint2*>(q);
+    rqb[j] = *reinterpret_cast<const uint2*>(q + rhalf);
+  }
+  float4 b4 = *reinterpret_cast<const float4*>(p.bias ? p.bias + cc : kZeros8);
+  float4 g4 = *reinterpret_cast<const float4*>(p.gamma ? p.gamma + cc : kZeros8), e4 = *reinterpret_cast<const float4*>(p.gamma ? p.beta + cc : kZeros8);
+  float4 em = *reinterpret_cast<const float4*>(p.emb ? p.emb + (long)n * p.emb_stride + cc : kZeros8);
+  const float rbv = *(p.res_bound ? p.res_bound + n : kZeros8), ebv = *(p.emb_bound ? p.emb_bound + n : kZeros8);
+  const bool slots = p.res_slots != nullptr && p.res_nslots > 0;
+  float sl0 = *(slots ? p.res_slots + (long)n * p.res_nslots + min(tid, p.res_nslots - 1) : kZeros8);   // (a slot read twice changes no maximum)
+#else
   uint2 rph[RJ], rpl[RJ];
   float4 rpf[RJ];
 #pragma unroll
@@ -291,8 +354,9 @@ __global__ __launch_bounds__(256) void wino_tail_kernel(const WinoTailP p) {
       }
     }
   }
-  // ---- 1. y = A^T M A + bias into LDS, statistics on the way
   const float4 b4 = p.bias ? *reinterpret_cast<const float4*>(p.bias + c0 + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+#endif
+  // ---- 1. y = A^T M A + bias into LDS, statistics on the way
   double s = 0, q = 0;
   for (int it = tid; it < T * cq; it += 256) {
     const int t = it / cq;
@@ -342,6 +406,15 @@ __global__ __launch_bounds__(256) void wino_tail_kernel(const WinoTailP p) {
   }
   if (lane == 0) { sd[wave] = s; sd[4 + wave] = q; }
   // the residual's measured bound straight from the slots its convolution wrote (max: any order gives the same bits)
+#if MF_PASS_CHAIN == 2
+  if (p.res_slots) {   // (the first 256 slots came with the entry burst; a convolution leaves fewer)
+    float mx = fmaxf(0.f, sl0);
+    for (int i = tid + 256; i < p.res_nslots; i += 256) mx = fmaxf(mx, p.res_slots[(long)n * p.res_nslots + i]);
+    mx = wave_max(mx);
+    if (lane == 0) sf[wave] = mx;
+  }
+  MF_LDS_BARRIER();   // (sd, sf and ys are LDS; nothing global is exchanged inside the workgroup)
+#else
   if (p.res_slots) {
     float mx = 0.f;
     for (int i = tid; i < p.res_nslots; i += 256) mx = fmaxf(mx, p.res_slots[(long)n * p.res_nslots + i]);
@@ -349,22 +422,37 @@ __global__ __launch_bounds__(256) void wino_tail_kernel(const WinoTailP p) {
     if (lane == 0) sf[wave] = mx;
   }
   __syncthreads();
+#endif
   const double S = ((sd[0] + sd[1]) + sd[2]) + sd[3], Q = ((sd[4] + sd[5]) + sd[6]) + sd[7];
   const double count = (double)HW * cpg;
   const double mean_d = S / count;
   double var = Q / count - mean_d * mean_d;
   if (var < 0) var = 0;
   const float mean = (float)mean_d, rstd = (float)(1.0 / sqrt(var + (double)p.eps));
+#if MF_PASS_CHAIN == 2
+  const float rb = p.res_slots ? fmaxf(fmaxf(sf[0], sf[1]), fmaxf(sf[2], sf[3])) : rbv;   // (rbv, ebv: 0.f read from kZeros8 when absent)
+  const float ob = p.bconst + rb + ebv;   // (the order of mf_gn_apply_*: bconst + residual + embedding)
+  const float rsc = p.res_pairs ? exp2i(scale_exp_of(rbv)) : 1.f;
+#else
   const float rb = p.res_slots ? fmaxf(fmaxf(sf[0], sf[1]), fmaxf(sf[2], sf[3])) : (p.res_bound ? p.res_bound[n] : 0.f);
   const float ob = p.bconst + rb + (p.emb_bound ? p.emb_bound[n] : 0.f);   // (the order of mf_gn_apply_*: bconst + residual + embedding)
-  const float osc = exp2i(-scale_exp_of(ob));
   const float rsc = p.res_pairs ? exp2i(scale_exp_of(p.res_bound[n])) : 1.f;
+#endif
+  const float osc = exp2i(-scale_exp_of(ob));
   const float vb = 4.f * ob;
   if (g == 0) {
     if (tid == 0 && p.out_bound) p.out_bound[n] = ob;
     if (tid < 16 && p.wino_bound) p.wino_bound[tid * p.N + n] = vb;
   }
   // ---- 2. normalise, Swish, + residual, + embedding: the per-element arithmetic of gn_apply_part_kernel, same operations in the same order
+#if MF_PASS_CHAIN == 2
+  // the ONE place that waits for the entry burst, in code every lane runs: a first use inside `if (it < nel)` would be waited for again by
+  // the next element, by a count that then includes the stores in between (vmcnt counts stores)
+  asm volatile("" : "+v"(g4.x), "+v"(g4.y), "+v"(g4.z), "+v"(g4.w), "+v"(e4.x), "+v"(e4.y), "+v"(e4.z), "+v"(e4.w), "+v"(em.x), "+v"(em.y), "+v"(em.z), "+v"(em.w));
+#pragma unroll
+  for (int j = 0; j <= RJ; ++j) asm volatile("" : "+v"(rqa[j].x), "+v"(rqa[j].y), "+v"(rqb[j].x), "+v"(rqb[j].y));
+  const float ga[4] = {g4.x, g4.y, g4.z, g4.w}, be[4] = {e4.x, e4.y, e4.z, e4.w};   // (read under `if (p.gamma)` only)
+#else
   float ga[4] = {1.f, 1.f, 1.f, 1.f}, be[4] = {0.f, 0.f, 0.f, 0.f};
   if (p.gamma) {
     const float4 g4 = *reinterpret_cast<const float4*>(p.gamma + c0 + c4 * 4), e4 = *reinterpret_cast<const float4*>(p.beta + c0 + c4 * 4);
@@ -372,6 +460,7 @@ __global__ __launch_bounds__(256) void wino_tail_kernel(const WinoTailP p) {
     be[0] = e4.x; be[1] = e4.y; be[2] = e4.z; be[3] = e4.w;
   }
   const float4 em = p.emb ? *reinterpret_cast<const float4*>(p.emb + (long)n * p.emb_stride + c0 + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+#endif
   const bool keep = p.out_wino != nullptr;
   auto pairs_to_f4 = [](uint2 h, uint2 l) {
     const sf_f16x2 h0 = __builtin_bit_cast(sf_f16x2, h.x), h1 = __builtin_bit_cast(sf_f16x2, h.y), l0 = __builtin_bit_cast(sf_f16x2, l.x),
@@ -379,7 +468,8 @@ __global__ __launch_bounds__(256) void wino_tail_kernel(const WinoTailP p) {
     return make_float4((float)h0[0] + (float)l0[0] * kLoInv, (float)h0[1] + (float)l0[1] * kLoInv, (float)h1[0] + (float)l1[0] * kLoInv,
                        (float)h1[1] + (float)l1[1] * kLoInv);
   };
-#define WINO_TAIL_ELEMENT(IT, RES_EXPR_PAIRS, RES_EXPR_F32)                                                            \
+#define WINO_TAIL_ELEMENT(IT, RES_EXPR_PAIRS, RES_EXPR_F32) WINO_TAIL_ELEMENT_TO(IT, RES_EXPR_PAIRS, RES_EXPR_F32, p.out_f32, p.out_pairs)
+#define WINO_TAIL_ELEMENT_TO(IT, RES_EXPR_PAIRS, RES_EXPR_F32, TO_F32, TO_PAIRS)                                       \
   {                                                                                                                   \
     const int pix = (IT) / cq;                                                                                        \
     float* yp = ys + pix * cpg + c4 * 4;                                                                              \
@@ -400,22 +490,58 @@ __global__ __launch_bounds__(256) void wino_tail_kernel(const WinoTailP p) {
       e[0] += r.x; e[1] += r.y; e[2] += r.z; e[3] += r.w;                                                             \
     }                                                                                                                 \
     if (p.emb) { e[0] += em.x; e[1] += em.y; e[2] += em.z; e[3] += em.w; }                                            \
-    if (p.out_f32) *reinterpret_cast<float4*>(p.out_f32 + eo) = make_float4(e[0], e[1], e[2], e[3]);                  \
-    if (p.out_pairs) store_split4<false>(p.out_pairs, eo, e[0], e[1], e[2], e[3], osc);   /* (the bound is derived: no clamp, split_f16.h) */ \
+    if (TO_F32) *reinterpret_cast<float4*>(p.out_f32 + eo) = make_float4(e[0], e[1], e[2], e[3]);                     \
+    if (TO_PAIRS) store_split4<false>(p.out_pairs, eo, e[0], e[1], e[2], e[3], osc);   /* (the bound is derived: no clamp, split_f16.h) */ \
     if (keep) *reinterpret_cast<float4*>(yp) = p.v_f32 ? make_float4(e[0], e[1], e[2], e[3])                                                                     \
                                                        : make_float4(wino_pair_round(e[0] * osc), wino_pair_round(e[1] * osc), wino_pair_round(e[2] * osc), wino_pair_round(e[3] * osc)); \
   }
+#if MF_PASS_CHAIN == 2
+  auto raw_to_f4 = [](uint2 a, uint2 b) { return make_float4(__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(b.x), __uint_as_float(b.y)); };
+  // the loop behind RJ (more than 1024 float4 per workgroup: the 32 x 32 level) keeps ONE round of residual rows ahead; its first round came
+  // with the entry burst (a load that no path consumes would be waited for where its register is written next -- behind the stores)
+  uint2 nqa = rqa[RJ], nqb = rqb[RJ];
+#pragma unroll
+  for (int j = 0; j < RJ; ++j) {
+    const int it = tid + 256 * j;
+    if (it < nel) WINO_TAIL_ELEMENT(it, pairs_to_f4(rqa[j], rqb[j]), raw_to_f4(rqa[j], rqb[j]))
+  }
+  // one instance per combination of outputs: the number of stores between two rounds of loads is then a constant of the loop, and the wait for
+  // round k's rows is a COUNT that leaves round k - 1's stores and round k + 1's loads in flight (vmcnt retires in order; a count the compiler
+  // cannot know -- stores under `if (p.out_f32)` -- degrades to "everything older", i.e. to a wait for the stores)
+#define WINO_TAIL_REST(TO_F32, TO_PAIRS)                                                                              \
+  for (int it = tid + 256 * RJ; it < nel; it += 256) {                                                                \
+    const uint2 cqa = nqa, cqb = nqb;                                                                                 \
+    const char* q = res_at(min(it + 256, nel - 1));                                                                   \
+    nqa = *reinterpret_cast<const uint2*>(q);                                                                         \
+    nqb = *reinterpret_cast<const uint2*>(q + rhalf);                                                                 \
+    WINO_TAIL_ELEMENT_TO(it, pairs_to_f4(cqa, cqb), raw_to_f4(cqa, cqb), TO_F32, TO_PAIRS)                            \
+  }
+  if (nel > 256 * RJ) {
+    if (p.out_f32) {
+      if (p.out_pairs) WINO_TAIL_REST(true, true) else WINO_TAIL_REST(true, false)
+    } else {
+      if (p.out_pairs) WINO_TAIL_REST(false, true) else WINO_TAIL_REST(false, false)
+    }
+  }
+#undef WINO_TAIL_REST
+#else
 #pragma unroll
   for (int j = 0; j < RJ; ++j) {
     const int it = tid + 256 * j;
     if (it < HW * cq) WINO_TAIL_ELEMENT(it, pairs_to_f4(rph[j], rpl[j]), rpf[j])
   }
   for (int it = tid + 256 * RJ; it < HW * cq; it += 256) WINO_TAIL_ELEMENT(it, wino_load_pairs4(p.res_pairs, eo), *reinterpret_cast<const float4*>(p.res_f32 + eo))
+#endif
 #undef WINO_TAIL_ELEMENT
+#undef WINO_TAIL_ELEMENT_TO
   if (!keep) return;
   // ---- 3. the input transform of the next Winograd convolution, from the pair-rounded result in LDS: bit for bit what wino_input_kernel
   // makes of out_pairs
+#if MF_PASS_CHAIN == 2
+  MF_LDS_BARRIER();   // (phase 3 reads ys and writes V: the stores of phase 2, to other tensors, stay in flight behind it)
+#else
   __syncthreads();
+#endif
   const float f = exp2i(scale_exp_of(ob)) * exp2i(-scale_exp_of(vb));
   for (int it = tid; it < T * cq; it += 256) {
     const int t = it / cq, ty = t / TW, tx = t - ty * TW;
