@@ -532,6 +532,35 @@ int mf_select_cells_f32(const uint8_t* mask, const float* a, const float* b, flo
 /* [N][1][D][H][W] mask (uint8: != 0; mask_is_f32 = 1: fp32 > 0.5; D = 1 in 2-D) -> [N][1][D/fd][H/fh][W/fw] uint8 0 / 1 by max over fd x fh x fw
  * blocks: an image-resolution mask reduced to the latent's cells (a cell is regenerated if any of its pixels is). */
 int mf_mask_maxpool_u8(const void* mask, int mask_is_f32, uint8_t* out, int N, int D, int H, int W, int fd, int fh, int fw, void* stream);
+/* Windowed denoising of a canvas larger than the trained size (MultiDiffusion; additive to ABI 250).  A canvas [B][C][D][H][W] fp32 (D = 1 and
+ * dims = 2 for images) is covered by M = count[0] * count[1] * count[2] windows of extent window[0..2], window m = (k0 * count[1] + k1) * count[2]
+ * + k2 (last axis fastest) starting at (origin[0][k0], origin[1][k1], origin[2][k2]).  Origins ascend strictly on every axis, start at 0, end at
+ * canvas - window and never leave a gap (origin[a][k + 1] - origin[a][k] <= window[a]), so every cell is covered.  The window tensor is
+ * [B * M][C][d][h][w], row b * M + m = window m of canvas row b (sample-major).
+ *   mf_window_gather_f32  windows[b * M + m] = the crop of canvas[b]: a copy, bit for bit.
+ *   mf_window_merge_f32   canvas_out[cell] = sum_m w_m p_m / sum_m w_m over the windows m that cover the cell, visited in ASCENDING m:
+ *                         acc = fmaf(w_m, p_m, acc), den += w_m, then one division.  A cell that exactly ONE window covers takes that window's
+ *                         value bit for bit (no multiply, no divide).  w_m is the product over the axes of the profile at the cell's offset i
+ *                         inside the window: MF_WINDOW_UNIFORM 1; MF_WINDOW_TENT min(i + 1, extent - i) (small integers: exact in fp32).
+ *                         No atomics, a fixed order: the same bits on every launch.
+ * B is the number of canvas rows of the launch (2 B' for the classifier-free-guidance pair).  Both are plain stream launches that allocate
+ * nothing and read nothing on the host (command list / graph capture).  16-byte vectors along the last axis when canvas[2], window[2] and every
+ * origin[2][k] are multiples of 4 and both tensors are 16-byte aligned; element by element otherwise.  The tensors must not overlap. */
+enum { MF_WINDOW_UNIFORM = 0, MF_WINDOW_TENT = 1 };
+#define MF_WINDOW_MAX_PER_AXIS 32
+typedef struct MfWindowDesc {
+  int32_t dims;                                 /* 2 or 3 (2: canvas[0] = window[0] = count[0] = 1, origin[0][0] = 0) */
+  int32_t canvas[3];                            /* D, H, W of the canvas */
+  int32_t window[3];                            /* d, h, w of a window (<= canvas) */
+  int32_t count[3];                             /* origins per axis, 1 .. MF_WINDOW_MAX_PER_AXIS */
+  int32_t origin[3][MF_WINDOW_MAX_PER_AXIS];    /* ascending; entries past count[a] are ignored */
+  int32_t weight;                               /* MF_WINDOW_* */
+  int32_t B;                                    /* canvas rows */
+  int32_t C;                                    /* channels */
+  int32_t reserved;                             /* 0 */
+} MfWindowDesc;
+int mf_window_gather_f32(const float* canvas, float* windows, const MfWindowDesc* desc, void* stream);
+int mf_window_merge_f32(const float* windows, float* canvas_out, const MfWindowDesc* desc, void* stream);
 /* out[0..n) = table[step] with step = *step_dev (or `step`): `t.expand(B)` of diffusion_pipeline.py:294 inside a captured graph */
 int mf_broadcast_from_table_f32(const float* table, const int32_t* step_dev, int32_t step, float* out, int n, void* stream);
 /* out[b][:] = table[step][cols[b]][:] for a [S][ncol][row_len] table, step = *step_dev (or `step`): the per-iteration gather of the

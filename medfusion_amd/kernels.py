@@ -1151,6 +1151,54 @@ def select_cells(mask: torch.Tensor, a: torch.Tensor, b: torch.Tensor, out: Opti
     return out
 
 
+def _window_rows(what: str, canvas_shape, windows_shape, plan):
+    """the canvas rows of a windowed launch, after the shapes were checked against the plan"""
+    sp = len(plan.canvas)
+    ok = (len(canvas_shape) == 2 + sp and len(windows_shape) == 2 + sp and tuple(canvas_shape[2:]) == plan.canvas and tuple(windows_shape[2:]) == plan.window
+          and canvas_shape[1] == windows_shape[1] and windows_shape[0] == canvas_shape[0] * plan.M and canvas_shape[0] > 0)
+    if not ok:
+        raise ValueError(f"{what}: canvas [B,C,{plan.canvas}] against windows [B*{plan.M},C,{plan.window}], got {tuple(canvas_shape)} and {tuple(windows_shape)}")
+    return canvas_shape[0]
+
+
+def window_gather(canvas: torch.Tensor, plan, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """canvas [B,C,(D,)H,W] fp32 -> windows [B*M,C,(d,)h,w]: row b*M + m is window m of `plan` (medfusion_amd.window.WindowPlan) cropped from
+    canvas row b, bit for bit (mf_window_gather_f32)"""
+    _gpu(canvas, out)
+    if canvas.dtype != torch.float32:
+        raise ValueError(f"window_gather: an fp32 canvas, got {canvas.dtype}")
+    canvas = canvas.contiguous()
+    if out is None:
+        out = torch.empty((canvas.shape[0] * plan.M, canvas.shape[1], *plan.window), dtype=torch.float32, device=canvas.device)
+    else:
+        drop_split(out)
+    B = _window_rows("window_gather", canvas.shape, out.shape, plan)
+    if out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("window_gather: a contiguous fp32 output")
+    desc = plan.desc(B, canvas.shape[1])
+    L.check(L.load().mf_window_gather_f32(canvas.data_ptr(), out.data_ptr(), C.byref(desc), stream()), "mf_window_gather_f32")
+    return out
+
+
+def window_merge(windows: torch.Tensor, plan, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """windows [B*M,C,(d,)h,w] fp32 -> canvas [B,C,(D,)H,W]: per cell the weighted average of the covering windows in ascending window order, a
+    cell under exactly one window that window's value bit for bit (mf_window_merge_f32)"""
+    _gpu(windows, out)
+    if windows.dtype != torch.float32 or windows.shape[0] % plan.M:
+        raise ValueError(f"window_merge: fp32 windows, a whole number of canvases of {plan.M}, got {tuple(windows.shape)} {windows.dtype}")
+    windows = windows.contiguous()
+    if out is None:
+        out = torch.empty((windows.shape[0] // plan.M, windows.shape[1], *plan.canvas), dtype=torch.float32, device=windows.device)
+    else:
+        drop_split(out)
+    B = _window_rows("window_merge", out.shape, windows.shape, plan)
+    if out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("window_merge: a contiguous fp32 output")
+    desc = plan.desc(B, windows.shape[1])
+    L.check(L.load().mf_window_merge_f32(windows.data_ptr(), out.data_ptr(), C.byref(desc), stream()), "mf_window_merge_f32")
+    return out
+
+
 def sched_step_blend(args: L.MfSchedArgs, blend: L.MfSchedBlend, outputs=()) -> None:
     """sched_step with the kept cells of x_t_out replaced by the known latent at the next timestep (mf_sched_step_blend_f32)"""
     _drop_outputs(outputs)

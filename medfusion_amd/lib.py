@@ -70,6 +70,15 @@ class MfSolverTraj(C.Structure):
                 ("slot_stride", C.c_int32), ("slots", C.c_int32), ("reserved", C.c_int32)]
 
 
+WINDOW_UNIFORM, WINDOW_TENT = 0, 1
+WINDOW_MAX_PER_AXIS = 32
+
+
+class MfWindowDesc(C.Structure):
+    _fields_ = [("dims", C.c_int32), ("canvas", C.c_int32 * 3), ("window", C.c_int32 * 3), ("count", C.c_int32 * 3),
+                ("origin", (C.c_int32 * WINDOW_MAX_PER_AXIS) * 3), ("weight", C.c_int32), ("B", C.c_int32), ("C", C.c_int32), ("reserved", C.c_int32)]
+
+
 class MfGnFuse(C.Structure):
     _fields_ = [("gamma", c_fp), ("beta", c_fp), ("residual", c_fp), ("residual_pairs", c_fp), ("res_bound", c_fp), ("res_bound_slots", c_fp),
                 ("emb", c_fp), ("emb_bound", c_fp), ("out", c_fp), ("out_split", c_fp), ("out_bound", c_fp), ("rendezvous", c_fp), ("error_flag", c_fp),
@@ -169,6 +178,8 @@ _SIGS = {
     "mf_solver_step_noise_f32": (_I, [C.POINTER(MfSolverArgs), C.POINTER(MfSolverNoise), C.POINTER(MfSchedBlend), c_fp]),
     "mf_absdiff_mean_c_f32": (_I, [c_fp, c_fp, c_fp, _I, _I, _I64, c_fp]),
     "mf_select_cells_f32": (_I, [c_fp, c_fp, c_fp, c_fp, _I, _I, _I64, c_fp]),
+    "mf_window_gather_f32": (_I, [c_fp, c_fp, C.POINTER(MfWindowDesc), c_fp]),
+    "mf_window_merge_f32": (_I, [c_fp, c_fp, C.POINTER(MfWindowDesc), c_fp]),
     "mf_mask_maxpool_u8": (_I, [c_fp, _I, c_fp, _I, _I, _I, _I, _I, _I, _I, c_fp]),
     "mf_image_ingress_u8": (_I, [c_fp, c_fp, _I, _I, _I, _I, c_fp]),
     "mf_gather_step_rows3_f32": (_I, [C.POINTER(c_fp), C.POINTER(_I64), C.POINTER(c_fp), _I, c_fp, c_fp, C.c_int32, _I, _I, c_fp]),

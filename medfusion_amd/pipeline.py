@@ -124,11 +124,20 @@ class DiffusionPipeline(nn.Module):
     def _estimator(self):
         return self.ema_model.averaged_model if self.use_ema else self.noise_estimator
 
-    def _predict(self, x_t, t, condition, self_cond, guidance_scale, un_cond, emb=None):
+    def _predict(self, x_t, t, condition, self_cond, guidance_scale, un_cond, emb=None, win=None):
         """UNet call(s) of forward :240-253.  Returns (pred, pred_uncond|None, pred_var|None).
         emb = (table, i, cols_cond, cols_uncond, cols_uncond ++ cols_cond): the loop's precomputed embeddings
-        (UNet.precompute_embeddings), or None."""
+        (UNet.precompute_embeddings), or None.
+        win: a WindowPlan (windowed denoising, _window_plan) -- x_t is the canvas [B, ...]; it is cropped into B * M windows (one launch,
+        K.window_gather), the estimator runs on those rows -- t, condition, un_cond and the embedding columns come with B * M rows, window m of
+        sample b at row b * M + m -- and its output is merged back to canvas shape (one launch, K.window_merge; the guidance pair's 2 B M rows as
+        2 B canvas rows), so whatever follows sees canvas tensors.  The estimator is never told."""
         est = self._estimator()
+        if win is not None:   # (never with a learned variance head or self-conditioning: _window_plan refuses them)
+            canvas_rows, x_t = x_t.shape[0], K.window_gather(x_t, win)
+            merge = lambda p: K.window_merge(p, win)
+        else:
+            canvas_rows, merge = x_t.shape[0], (lambda p: p)
         cfg = (condition is not None) and (guidance_scale != 1.0)
         ec = (lambda cols: None) if emb is None else (lambda cols: est.step_embeddings(emb[0], emb[1], cols))
         if cfg:
@@ -138,17 +147,41 @@ class DiffusionPipeline(nn.Module):
             if self.batch_cfg and not self.use_self_conditioning:
                 # both passes of diffusion_pipeline.py:242-243 as ONE UNet call over 2B rows (rows are independent):
                 # rows [0,B) = un-guided (condition = un_cond, possibly None), rows [B,2B) = guided.
-                pred2 = est.forward_cfg_pair(x_t, t, condition, un_cond, emb_cache=None if emb is None else ec(emb[4]))
-                B = x_t.shape[0]
+                pred2 = merge(est.forward_cfg_pair(x_t, t, condition, un_cond, emb_cache=None if emb is None else ec(emb[4])))
+                B = canvas_rows
                 return pred2[B:], pred2[:B], None
             pred_uncond, _ = est(x_t, t, condition=un_cond, self_cond=self_cond, emb_cache=None if emb is None else ec(emb[3]))  # un-guided pass FIRST (Q6)
             pred_cond, _ = est(x_t, t, condition=condition, self_cond=self_cond, emb_cache=None if emb is None else ec(emb[2]))
-            return pred_cond, pred_uncond, None
+            return merge(pred_cond), merge(pred_uncond), None
         if self.estimate_variance:
             pred, pred_var = est.forward_split(x_t, t, condition=condition, self_cond=self_cond, emb_cache=None if emb is None else ec(emb[2]))
             return pred, None, pred_var
         pred, _ = est(x_t, t, condition=condition, self_cond=self_cond, emb_cache=None if emb is None else ec(emb[2]))
-        return pred, None, None
+        return merge(pred), None, None
+
+    # ------------------------------------------------------------------ windowed denoising
+    WINDOW_KEYS = ("window", "window_stride", "window_weight")
+
+    def _window_plan(self, canvas, window=None, window_stride=None, window_weight="tent", cold_diffusion=False):
+        """the rules of `window=` / `window_stride=` / `window_weight=` (denoise, sample, sample_from), checked before anything touches the device
+        -> the WindowPlan of a canvas (its spatial extents in latent cells), or None: no window, or one equal to the canvas (the un-windowed path)"""
+        if window is None:
+            if window_stride is not None:
+                raise ValueError(f"window_stride={window_stride!r} needs window=")
+            return None
+        from .window import WindowPlan
+
+        if self.use_self_conditioning:
+            raise ValueError("window= with use_self_conditioning: the self-conditioning input is not carried through the windows (out of scope)")
+        if self.estimate_variance:
+            raise ValueError("window= with estimate_variance: the learned variance head is not merged (out of scope)")
+        if cold_diffusion:
+            raise ValueError("window= with cold_diffusion=True: cold diffusion runs through the single-step API, which has no windows (out of scope)")
+        plan = WindowPlan(tuple(canvas), window, window_stride, window_weight, dims=getattr(self._estimator(), "spatial_dims", None))
+        return None if plan.none else plan
+
+    def _check_window(self, canvas, kwargs):
+        self._window_plan(canvas, *(kwargs.get(k, d) for k, d in zip(self.WINDOW_KEYS, (None, None, "tent"))), kwargs.get("cold_diffusion", False))
 
     @torch.no_grad()
     def forward(self, x_t, t, condition=None, self_cond=None, guidance_scale=1.0, cold_diffusion=False, un_cond=None, noise=None):
@@ -257,8 +290,15 @@ class DiffusionPipeline(nn.Module):
         a callback that wants finished iterations synchronises the stream itself.  The replayed loops (command list, graph) call it after the eager
         first iteration, then every max(1, total // 20) iterations; the Python loop every iteration.  The counts a caller sees are STRICTLY
         INCREASING: when the loop has to be re-run (a fused rendezvous timed out, K.with_fused_fallback) the counts already reported are not
-        reported again."""
+        reported again.
+        window=(h, w) | (d, h, w), window_stride=None, window_weight="tent" | "uniform": windowed denoising (MultiDiffusion) of an x_t larger than
+        the trained size -- x_t is the CANVAS; every iteration the estimator runs on the overlapping windows of medfusion_amd.window.WindowPlan
+        (B * M rows; `condition` / `un_cond` repeated per window once, before the loop), the predictions are merged per cell with fixed weights and
+        the scheduler / solver step, the inpainting select, the draws and the decode run once on the canvas, exactly as without a window: same
+        draw order, same draw count, canvas-shaped draws.  Two more launches per iteration, both the library's (all three loop forms).  A window
+        equal to the canvas is the un-windowed path.  ValueError with use_self_conditioning, estimate_variance or cold_diffusion=True."""
         self._check_sampler(kwargs.get("sampler"), kwargs.get("spacing"), use_ddim, kwargs.get("cold_diffusion", False))
+        self._check_window(tuple(x_t.shape[2:]), kwargs)
         return self._denoise_guarded(x_t, steps, condition, use_ddim, noise, trace, decode, use_graph, loop, progress_cb, 0, None, kwargs)
 
     def _denoise_guarded(self, x_t, steps, condition, use_ddim, noise, trace, decode, use_graph, loop, progress_cb, start, blend, kwargs, traj=None, up=None):
@@ -307,9 +347,11 @@ class DiffusionPipeline(nn.Module):
         un_cond = kwargs.pop("un_cond", None)
         cold_diffusion = bool(kwargs.pop("cold_diffusion", False))
         sampler, spacing = kwargs.pop("sampler", None), kwargs.pop("spacing", None)
+        window = [kwargs.pop(k, d) for k, d in zip(self.WINDOW_KEYS, (None, None, "tent"))]
         if kwargs:
             raise TypeError(f"forward() got an unexpected keyword argument '{next(iter(kwargs))}'")
         self._check_sampler(sampler, spacing, use_ddim, cold_diffusion)
+        win = self._window_plan(tuple(x_t.shape[2:]), *window, cold_diffusion)
         if self.estimator_objective not in ("x_T", "x_0"):
             raise ValueError("Unknown Objective")
         if not x_t.is_cuda:
@@ -348,6 +390,11 @@ class DiffusionPipeline(nn.Module):
         use_graph = mode == "graph"
         dev = x_t.device
         B = x_t.shape[0]
+        Bw = B   # the estimator's rows: one per sample, or one per window of every sample (sample-major)
+        if win is not None:
+            Bw = B * win.M
+            condition = None if condition is None else condition.repeat_interleave(win.M, dim=0)
+            un_cond = None if un_cond is None else un_cond.repeat_interleave(win.M, dim=0)
         if sampler is None:
             timesteps, steps = sch.loop_timesteps(steps, use_ddim)
             recs = sch.step_records(timesteps, use_ddim)
@@ -412,15 +459,15 @@ class DiffusionPipeline(nn.Module):
         nz, n_buf = self._solver_noise(noise, scales, x_t, blend, noise.draw_index) if stochastic else (None, None)
         if mode in ("graph", "cmdlist"):
             self._denoise_graph(x_t, rev, recs, table, condition, guidance_scale, un_cond, use_ddim, noise, objective, cmdlist=(mode == "cmdlist"),
-                                progress_cb=progress_cb, blend=blend, solver=None if sampler is None else (hist, _traj, nz, n_buf))
+                                progress_cb=progress_cb, blend=blend, solver=None if sampler is None else (hist, _traj, nz, n_buf), win=win)
         elif sampler is not None:
-            t_all = torch.tensor(rev, dtype=torch.float32, device=dev).reshape(-1, 1).expand(-1, B).contiguous()
+            t_all = torch.tensor(rev, dtype=torch.float32, device=dev).reshape(-1, 1).expand(-1, Bw).contiguous()
             x0 = torch.empty_like(x_t) if (self.use_self_conditioning or trace is not None) else None
             self_cond = None
-            emb_tab = self._hoisted_embeddings(self._estimator(), t_all[:, 0].contiguous(), condition, un_cond, B, dev)
+            emb_tab = self._hoisted_embeddings(self._estimator(), t_all[:, 0].contiguous(), condition, un_cond, Bw, dev)
             for i in range(len(rev)):
                 pred, pred_uncond, _ = self._predict(x_t, t_all[i], condition, self_cond, guidance_scale, un_cond,
-                                                     emb=None if emb_tab is None else (emb_tab[0], i, emb_tab[1], emb_tab[2], emb_tab[3]))
+                                                     emb=None if emb_tab is None else (emb_tab[0], i, emb_tab[1], emb_tab[2], emb_tab[3]), win=win)
                 if stochastic and i < len(rev) - 1:
                     if n_buf is None:
                         noise.draw_index += 1                          # (draw nz.draw_base + i, generated inside the launch)
@@ -433,16 +480,16 @@ class DiffusionPipeline(nn.Module):
                 if progress_cb is not None:
                     progress_cb(i + 1, len(rev))
         else:
-            t_all = torch.tensor(rev, dtype=torch.float32, device=dev).reshape(-1, 1).expand(-1, B).contiguous()  # t.expand(B) per iteration (Q7)
+            t_all = torch.tensor(rev, dtype=torch.float32, device=dev).reshape(-1, 1).expand(-1, Bw).contiguous()  # t.expand(B) per iteration (Q7)
             n_post = torch.empty_like(x_t)
             n_ddim = torch.empty_like(x_t)
             x0 = torch.empty_like(x_t)
             self_cond = None
             est = self._estimator()
-            emb_tab = self._hoisted_embeddings(est, t_all[:, 0].contiguous(), condition, un_cond, B, dev)
+            emb_tab = self._hoisted_embeddings(est, t_all[:, 0].contiguous(), condition, un_cond, Bw, dev)
             for i in range(len(rev)):
                 pred, pred_uncond, pred_var = self._predict(x_t, t_all[i], condition, self_cond, guidance_scale, un_cond,
-                                                            emb=None if emb_tab is None else (emb_tab[0], i, emb_tab[1], emb_tab[2], emb_tab[3]))
+                                                            emb=None if emb_tab is None else (emb_tab[0], i, emb_tab[1], emb_tab[2], emb_tab[3]), win=win)
                 noise.draw(tuple(x_t.shape), out=n_post)          # gaussian_scheduler.py:99 -- drawn on every iteration (Q3)
                 ddim = recs[i].mode == 1
                 if ddim:
@@ -479,7 +526,7 @@ class DiffusionPipeline(nn.Module):
         return (tab, cc, cu, torch.cat([cu, cc]))   # (the last: columns of the 2B-row classifier-free-guidance pair, un-guided rows first)
 
     def _denoise_graph(self, x_t, rev, recs, table, condition, guidance_scale, un_cond, use_ddim, noise, objective, cmdlist=False, progress_cb=None,
-                       blend=None, solver=None):
+                       blend=None, solver=None, win=None):
         """The loop body as ONE captured hipGraph replayed `steps` times (BASELINE.json configs[3]) -- or, cmdlist=True, recorded by the
         library while it runs once and re-issued from C (mf_cmdlist_*: the native command list of the loop body).  Everything the
         reference reads on the host each iteration (t, alphas_cumprod[t], the t==0 test, the RNG state) is indexed by a
@@ -489,7 +536,9 @@ class DiffusionPipeline(nn.Module):
         solver = (x_0 history or None, MfSolverTraj or None, MfSolverNoise or None, its draw buffer or None): `table` holds MfSolverStep rows and the
         tail of an iteration is mf_solver_step_f32 (mf_solver_step_traj_f32 with a trajectory, whose slot the same counter indexes), which reads
         the counter, advances it and draws nothing -- or, for a stochastic sampler, mf_solver_step_noise_f32, whose draw index the same counter
-        advances (draw base + step, inside the launch; through the buffer and one more launch where the in-launch form does not apply)."""
+        advances (draw base + step, inside the launch; through the buffer and one more launch where the in-launch form does not apply).
+        win: a WindowPlan -- x_t is the canvas, `condition` / `un_cond` come with B * M rows (_denoise repeated them), and so do t and the hoisted
+        embedding columns; the crop and the merge are two more recorded launches of the body (_predict)."""
         from .noise import PhiloxDeviceNoise
 
         if (solver is None or solver[2] is not None) and not isinstance(noise, PhiloxDeviceNoise):
@@ -498,7 +547,8 @@ class DiffusionPipeline(nn.Module):
         t_table = torch.tensor(rev, dtype=torch.float32, device=dev)
         counter = torch.zeros(2, dtype=torch.int32, device=dev)    # (step, ticket word of the fused tail launch)
         step_dev = counter[:1]
-        t_cur = torch.zeros(B, dtype=torch.float32, device=dev)   # (filled per iteration only when the estimator reads t: not with hoisted embeddings)
+        Bw = B if win is None else B * win.M
+        t_cur = torch.zeros(Bw, dtype=torch.float32, device=dev)   # (filled per iteration only when the estimator reads t: not with hoisted embeddings)
         n_post, n_ddim, x0 = (None, None, None) if solver is not None else (torch.empty_like(x_t), torch.empty_like(x_t), torch.empty_like(x_t))
         if solver is not None and self.use_self_conditioning:
             x0 = torch.empty_like(x_t)
@@ -507,7 +557,7 @@ class DiffusionPipeline(nn.Module):
         drawn = stride * len(rev) if solver is None else (len(rev) - 1 if solver[2] is not None else 0)   # (a stochastic sampler: all but the last iteration)
         clip, g = int(bool(self.clip_x0)), float(guidance_scale)
 
-        emb_tab = self._hoisted_embeddings(self._estimator(), t_table, condition, un_cond, B, dev)
+        emb_tab = self._hoisted_embeddings(self._estimator(), t_table, condition, un_cond, Bw, dev)
         emb = None if emb_tab is None else (emb_tab[0], step_dev, emb_tab[1], emb_tab[2], emb_tab[3])   # rows of iteration *step_dev, gathered on the device
 
         # the tail of an iteration -- posterior draw, DDIM draw, scheduler step, counter += 1 -- as ONE launch (mf_sched_step_philox_f32: the same
@@ -529,7 +579,7 @@ class DiffusionPipeline(nn.Module):
         def body():
             if emb is None:   # (with the embedding rows hoisted out of the loop the estimator never reads t)
                 K.broadcast_from_table(t_table, step_dev, t_cur)
-            pred, pred_uncond, pred_var = self._predict(x_t, t_cur, condition, None if not self.use_self_conditioning else x0, g, un_cond, emb=emb)
+            pred, pred_uncond, pred_var = self._predict(x_t, t_cur, condition, None if not self.use_self_conditioning else x0, g, un_cond, emb=emb, win=win)
             if solver is not None:
                 solver_tail(pred, pred_uncond)
                 return pred
@@ -665,8 +715,11 @@ class DiffusionPipeline(nn.Module):
     @torch.no_grad()
     def sample(self, num_samples, img_size, condition=None, noise: Optional[NoiseSource] = None, shard=None, **kwargs):
         """diffusion_pipeline.py:312-317.  `shard=(rank, world)`: this process generates rows
-        [rank*num_samples/world, (rank+1)*num_samples/world) of the global batch (condition/un_cond are global)."""
+        [rank*num_samples/world, (rank+1)*num_samples/world) of the global batch (condition/un_cond are global).
+        window= / window_stride= / window_weight= (see denoise): `img_size` is the CANVAS, a latent larger than the trained size; draw #0 has its
+        shape and the whole canvas is decoded in one latent_embedder.decode call."""
         self._check_sampler(kwargs.get("sampler"), kwargs.get("spacing"), kwargs.get("use_ddim", True), kwargs.get("cold_diffusion", False))
+        self._check_window(tuple(img_size)[1:], kwargs)
         dev = self.device
         if dev.type != "cuda":
             raise RuntimeError("medfusion_amd.DiffusionPipeline.sample: move the pipeline to a ROCm device first (no CPU fallback)")
@@ -720,7 +773,8 @@ class DiffusionPipeline(nn.Module):
     @torch.no_grad()
     def sample_from(self, x, strength, condition=None, *, mask=None, is_latent=False, steps=None, use_ddim=True, noise: Optional[NoiseSource] = None,
                     encode_noise: Optional[NoiseSource] = None, composite=False, shard=None, decode=True, trace=None, loop=None, use_graph=None,
-                    progress_cb=None, guidance_scale=1.0, un_cond=None, sampler=None, spacing=None, **kwargs):
+                    progress_cb=None, guidance_scale=1.0, un_cond=None, sampler=None, spacing=None, window=None, window_stride=None, window_weight="tent",
+                    **kwargs):
         """Image-conditioned sampling: img2img (variations of `x` at a chosen `strength`) and, with `mask`, inpainting.  A composition of the
         reference's own functions -- the training front end (diffusion_pipeline.py:84-90), GaussianNoiseScheduler.estimate_x_t
         (gaussian_scheduler.py:61-77) and the LAST k iterations of denoise's loop (:278-310):
@@ -740,7 +794,9 @@ class DiffusionPipeline(nn.Module):
         cold_diffusion=True raises ValueError; `eta` raises TypeError like everywhere.
         sampler= / spacing= as in denoise(): the few-step samplers on the EXECUTED grid -- the same strength rule picks the last k of its
         iterations, the first of them is first-order, the kept cells take the known latent at the next timestep of that grid; eps0 is the only
-        draw of a deterministic sampler, a stochastic one ("ddim1", "dpmpp2m_sde") adds one draw per non-final iteration (k draws in all)."""
+        draw of a deterministic sampler, a stochastic one ("ddim1", "dpmpp2m_sde") adds one draw per non-final iteration (k draws in all).
+        window= / window_stride= / window_weight= as in denoise(): the input's latent is the canvas; eps0, the mask's select and the decode are
+        canvas-sized and unchanged, so the kept cells still end as z0 exactly."""
         if "eta" in kwargs:
             raise TypeError("forward() got an unexpected keyword argument 'eta'")
         if kwargs.pop("cold_diffusion", False):
@@ -748,6 +804,11 @@ class DiffusionPipeline(nn.Module):
         if kwargs:
             raise TypeError(f"forward() got an unexpected keyword argument '{next(iter(kwargs))}'")
         self._check_sampler(sampler, spacing, use_ddim, False)
+        if window is not None or window_stride is not None:   # (the latent's extents, known before the encoder runs)
+            emb, canvas = self.latent_embedder, tuple(x.shape[2:])
+            if not is_latent and emb is not None:
+                canvas = tuple(a // b for a, b in zip(canvas, getattr(emb, "scale3", None) or (emb.scale,) * len(canvas)))
+            self._window_plan(canvas, window, window_stride, window_weight)
         sch = self.noise_scheduler
         timesteps, _ = sch.loop_timesteps(steps, use_ddim, spacing)
         asked, steps = steps, len(timesteps)
@@ -803,7 +864,8 @@ class DiffusionPipeline(nn.Module):
             blend = None if cmask is None else (z0, eps0, cmask)
             # (the loop rebuilds the grid from the step count: the log-SNR grid of `asked` steps is not the one of len(timesteps) steps)
             out = self._denoise_guarded(x_t, asked if sampler is not None else steps, condition, use_ddim, noise, trace, decode, use_graph, loop, progress_cb,
-                                        s, blend, dict(guidance_scale=guidance_scale, un_cond=un_cond, sampler=sampler, spacing=spacing))
+                                        s, blend, dict(guidance_scale=guidance_scale, un_cond=un_cond, sampler=sampler, spacing=spacing, window=window,
+                                                       window_stride=window_stride, window_weight=window_weight))
             if composite:
                 pix = (mask > 0.5) if mask.is_floating_point() else (mask != 0)
                 out = K.select_cells(pix.to(torch.uint8).contiguous(), out, x)
@@ -825,6 +887,8 @@ class DiffusionPipeline(nn.Module):
         """the argument rules invert() and edit() share, checked before anything touches the device -> (timesteps, k)"""
         if "eta" in kwargs:
             raise TypeError("forward() got an unexpected keyword argument 'eta'")
+        if any(k in kwargs for k in self.WINDOW_KEYS):
+            raise ValueError(f"window= is not built for {who}: an inversion's trajectory is not carried through the windows (out of scope)")
         if kwargs.pop("cold_diffusion", False):
             raise ValueError(f"cold_diffusion is not built for {who}")
         if kwargs:

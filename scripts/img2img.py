@@ -14,6 +14,8 @@ The mask PNG has the images' size; non-zero pixels are REGENERATED, zero pixels 
 Draws: #0 diffuses the encoded image, then the loop's draws as in sample() (Philox key --seed; the encoder's draw uses key --seed + 1).
 --sampler ddim0 | dpmpp2m (with --spacing logsnr: fewer iterations for the same solver accuracy) runs the loop deterministically: draw #0 only.
 --sampler ddim1 | dpmpp2m_sde (the latter meant for --spacing logsnr) keeps the loop stochastic at few steps: one more draw per non-final iteration.
+--window H W (latent cells) [--window-stride ...] [--window-weight tent|uniform]: images larger than the trained size -- the estimator runs on
+overlapping windows of the trained size, everything else on the whole latent (DiffusionPipeline.sample_from(window=...)).
 """
 import argparse
 import sys
@@ -61,6 +63,9 @@ if __name__ == "__main__":
     ap.add_argument("--sampler", default=None, choices=["ddim0", "dpmpp2m", "ddim1", "dpmpp2m_sde"],
                     help="a few-step sampler in place of the reference's update: deterministic (ddim0, dpmpp2m) or stochastic (ddim1, dpmpp2m_sde)")
     ap.add_argument("--spacing", default=None, choices=["uniform", "logsnr"], help="timestep grid of --sampler (logsnr: uniform in log-SNR)")
+    ap.add_argument("--window", type=int, nargs="+", default=None, help="windowed denoising: the trained extents, in latent cells (smaller than the images' latent)")
+    ap.add_argument("--window-stride", type=int, nargs="+", default=None, help="stride of the windows per axis (default: half a window)")
+    ap.add_argument("--window-weight", default="tent", choices=["tent", "uniform"], help="weights of the per-cell average over the windows")
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--save-tensor", action="store_true", help="also write result.pt: the fp32 images behind the PNG files")
@@ -91,7 +96,8 @@ if __name__ == "__main__":
         # (one Philox key for the whole folder, the chunk's rows at their global offset: the result does not depend on --batch)
         res = pipeline.sample_from(x, args.strength, condition=cond, mask=None if mask is None else mask.expand(n, -1, -1, -1).contiguous(),
                                    steps=args.steps, use_ddim=not args.ddpm, guidance_scale=args.guidance, un_cond=None, composite=mask is not None,
-                                   sampler=args.sampler, spacing=args.spacing,
+                                   sampler=args.sampler, spacing=args.spacing, window=None if args.window is None else tuple(args.window),
+                                   window_stride=None if args.window_stride is None else tuple(args.window_stride), window_weight=args.window_weight,
                                    noise=_ChunkNoise(args.seed, lo, len(files)), encode_noise=_ChunkNoise(args.seed + 1, lo, len(files)))
         writer.submit(res, [out / f.name for f in chunk])
         if args.save_tensor:

@@ -6,6 +6,10 @@ Same flow: seed, load pipeline, `.to(device)`, loop over conditions [0, 1, None]
 then `(x+1)/2`, clamp, `save_image(normalize=True, scale_each=True)` and the |class1 - class0| difference image.
 Only the import line and the checkpoint source differ; `--synthetic` builds the published architecture with
 seeded synthetic weights because no checkpoint/dataset exists offline.
+
+--canvas H W (latent cells; default 32 32, the trained size) with --window H W [--window-stride S ...] [--window-weight tent|uniform] samples a
+field of view larger than the trained size by windowed denoising (DiffusionPipeline.sample(window=...)): `--canvas 32 96 --window 32 32` writes
+256 x 768 strips.
 """
 import argparse
 import math
@@ -66,6 +70,10 @@ if __name__ == "__main__":
     ap.add_argument("--steps", type=int, default=150)
     ap.add_argument("--n", type=int, default=16)
     ap.add_argument("--out", default="results/CheXpert/samples")
+    ap.add_argument("--canvas", type=int, nargs="+", default=[32, 32], help="spatial extents of the sampled latent, in latent cells")
+    ap.add_argument("--window", type=int, nargs="+", default=None, help="windowed denoising: the trained extents, in latent cells (smaller than --canvas)")
+    ap.add_argument("--window-stride", type=int, nargs="+", default=None, help="stride of the windows per axis (default: half a window)")
+    ap.add_argument("--window-weight", default="tent", choices=["tent", "uniform"], help="weights of the per-cell average over the windows")
     args = ap.parse_args()
     path_out = Path.cwd() / args.out
     path_out.mkdir(parents=True, exist_ok=True)
@@ -77,12 +85,15 @@ if __name__ == "__main__":
     pipeline.to(device)
 
     steps, use_ddim, images, n_samples = args.steps, True, {}, args.n
+    window_kw = {}
+    if args.window is not None:
+        window_kw = dict(window=tuple(args.window), window_stride=None if args.window_stride is None else tuple(args.window_stride), window_weight=args.window_weight)
     raw = {}
     for cond in [0, 1, None]:
         torch.manual_seed(0)
         condition = torch.tensor([cond] * n_samples, device=device) if cond is not None else None
         un_cond = None
-        results = pipeline.sample(n_samples, (8, 32, 32), guidance_scale=8, condition=condition, un_cond=un_cond, steps=steps, use_ddim=use_ddim)
+        results = pipeline.sample(n_samples, (8, *args.canvas), guidance_scale=8, condition=condition, un_cond=un_cond, steps=steps, use_ddim=use_ddim, **window_kw)
         raw[str(cond)] = results.cpu()
         results = (results + 1) / 2
         results = results.clamp(0, 1)
