@@ -679,6 +679,48 @@ int mf_image_egress_u8(const float* x_nchw, uint8_t* out_nhwc, float* minmax_ws,
  * tF.normalize(x / 255, 0.5, 0.5) (scripts/evaluate_latent_embedder.py:77). */
 int mf_image_ingress_u8(const uint8_t* x_nhwc, float* out_nchw, int N, int C, int H, int W, void* stream);
 
+/* Image-quality metrics on the device (additive to ABI 250): SSIM / MS-SSIM / MSE of image PAIRS taken from two banks of fp32 NCHW images,
+ * xbank [Nx][C][H][W] and ybank [Ny][C][H][W] (the same pointer twice for the pairwise diversity of one set).  Pair p compares xbank[ix[p]] with
+ * ybank[iy[p]]; a null index array is the identity (then P <= the bank's rows).  Nothing is gathered into per-pair copies.  An index outside
+ * its bank makes that pair's results NaN and reads nothing.
+ *   mf_ssim_pairs_f32   ONE scale of all P pairs in one launch.  The window is taps (x) taps (k taps by value in the descriptor, the caller
+ *                       normalises them), VALID positions only: (H - k + 1) x (W - k + 1) windows per channel.  Per window mu_x, mu_y, E[x^2],
+ *                       E[y^2], E[xy]; c1 = (k1 L)^2, c2 = (k2 L)^2; cs = (2 s_xy + c2) / (s_x^2 + s_y^2 + c2), ssim = (2 mu_x mu_y + c1) /
+ *                       (mu_x^2 + mu_y^2 + c1) * cs.  L is data_range, or with range_on_device = 1 max(max x - min x, max y - min y) of the
+ *                       pair, formed in the kernel from minmax_x [Nx][2] / minmax_y [Ny][2] (mf_rows_minmax_f32 of the scale-0 banks): no host
+ *                       sync.  The second moments are taken about a per-tile pivot, so a near-constant region does not cancel.  A workgroup owns
+ *                       32 x 32 window origins of one (pair, channel) and writes three fp64 partial sums (ssim, cs, and with want_mse (x - y)^2
+ *                       over the pixels it owns) to the workspace: mf_ssim_workspace_bytes(desc) bytes, 8-byte aligned.  16-byte loads when
+ *                       W % 4 == 0 and both banks are 16-byte aligned, element by element otherwise: the same bits either way, in sim, cs and mse (a thread
+ *                       takes the same pixels in the same order on both).
+ *   mf_ssim_finish_f32  adds each pair's partials in ascending (channel, tile) order in fp64 and writes sim[p * out_stride], cs[p * out_stride]
+ *                       (the means over all channels and valid positions) and mse[p] (the mean over C H W; want_mse only) as fp32; any of the
+ *                       three may be null.  out_stride lets a caller fill one column of a [P][S] table per scale.
+ * No floating-point atomics: the same inputs give the same bits on every launch, and a pair's result depends neither on P nor on its place
+ * among the pairs.  mf_ssim_ok / mf_ssim_workspace_bytes are host-only (the descriptor's rules: k odd in 3 .. MF_SSIM_MAX_K, H, W >= k,
+ * 0 < P, C <= 65535, banks non-empty, P within an un-indexed bank); every entry point refuses a bad descriptor with MF_EINVAL before any launch.
+ *   mf_avgpool2_planes_f32  y[pl][oy][ox] = ((x[2oy][2ox] + x[2oy][2ox+1]) + (x[2oy+1][2ox] + x[2oy+1][2ox+1])) / 4 on [planes][H][W] ->
+ *                       [planes][H/2][W/2] (an odd trailing row or column is dropped): the next level of a bank's pyramid, built once per bank.
+ *   mf_rows_minmax_f32  out[row] = {min, max} of x[row][0 .. n), both NaN when the row holds a NaN; one workgroup per row. */
+#define MF_SSIM_MAX_K 11
+typedef struct MfSsimDesc {
+  int32_t P, C, H, W;             /* pairs, channels, extents of THIS scale */
+  int32_t Nx, Ny;                 /* rows of the two banks */
+  int32_t k;                      /* taps: odd, 3 .. MF_SSIM_MAX_K */
+  int32_t indexed;                /* bit 0: ix is given, bit 1: iy is given */
+  int32_t want_mse;               /* 1: also sum (x - y)^2 (scale 0) */
+  int32_t range_on_device;        /* 1: L from minmax_x / minmax_y; 0: data_range */
+  float taps[MF_SSIM_MAX_K];      /* the 1-D window, entries past k ignored */
+  float k1, k2, data_range;
+} MfSsimDesc;
+int mf_ssim_ok(const MfSsimDesc* desc);
+size_t mf_ssim_workspace_bytes(const MfSsimDesc* desc);
+int mf_ssim_pairs_f32(const float* xbank, const float* ybank, const int32_t* ix, const int32_t* iy, const float* minmax_x, const float* minmax_y,
+                      void* workspace, size_t workspace_bytes, const MfSsimDesc* desc, void* stream);
+int mf_ssim_finish_f32(const void* workspace, float* sim, float* cs, float* mse, int out_stride, const MfSsimDesc* desc, void* stream);
+int mf_avgpool2_planes_f32(const float* x, float* y, int64_t planes, int H, int W, void* stream);
+int mf_rows_minmax_f32(const float* x, float* out, int N, int64_t n, void* stream);
+
 /* ------------------------------------------------------------------ built-in launch timing (bench / roofline)
  * When enabled every launch is bracketed by hipEvents on its own stream and attributed to a kernel family.
  * NOT capture-safe; off by default. */

@@ -1199,6 +1199,74 @@ def window_merge(windows: torch.Tensor, plan, out: Optional[torch.Tensor] = None
     return out
 
 
+def rows_minmax(x: torch.Tensor) -> torch.Tensor:
+    """[N, ...] fp32 -> [N, 2]: the min and the max of every row (mf_rows_minmax_f32)"""
+    _gpu(x)
+    _need_f32(x)
+    x = x.contiguous()
+    n = x.shape[0]
+    out = torch.empty((n, 2), dtype=torch.float32, device=x.device)
+    L.check(L.load().mf_rows_minmax_f32(x.data_ptr(), out.data_ptr(), n, x.numel() // n, stream()), "mf_rows_minmax_f32")
+    return out
+
+
+def avgpool2_planes(x: torch.Tensor) -> torch.Tensor:
+    """[N, C, H, W] fp32 -> [N, C, H // 2, W // 2] by 2 x 2 means, an odd trailing row or column dropped (mf_avgpool2_planes_f32)"""
+    _gpu(x)
+    _need_f32(x)
+    x = x.contiguous()
+    n, c, h, w = x.shape
+    out = torch.empty((n, c, h // 2, w // 2), dtype=torch.float32, device=x.device)
+    L.check(L.load().mf_avgpool2_planes_f32(x.data_ptr(), out.data_ptr(), n * c, h, w, stream()), "mf_avgpool2_planes_f32")
+    return out
+
+
+def make_ssim_desc(P: int, C_: int, H: int, W: int, Nx: int, Ny: int, taps, k1: float, k2: float, data_range: Optional[float], indexed: int = 0,
+                   want_mse: bool = False) -> L.MfSsimDesc:
+    """data_range=None: L of every pair from the banks' min / max rows on the device"""
+    d = L.MfSsimDesc(P=P, C=C_, H=H, W=W, Nx=Nx, Ny=Ny, k=len(taps), indexed=indexed, want_mse=int(want_mse), range_on_device=int(data_range is None),
+                     k1=k1, k2=k2, data_range=0.0 if data_range is None else data_range)
+    for j, v in enumerate(taps[:L.SSIM_MAX_K]):
+        d.taps[j] = v
+    return d
+
+
+def ssim_ok(d: L.MfSsimDesc) -> bool:
+    return bool(L.load().mf_ssim_ok(C.byref(d)))
+
+
+def ssim_pairs(xbank: torch.Tensor, ybank: torch.Tensor, d: L.MfSsimDesc, sim: Optional[torch.Tensor], cs: Optional[torch.Tensor],
+               mse: Optional[torch.Tensor] = None, ix: Optional[torch.Tensor] = None, iy: Optional[torch.Tensor] = None,
+               minmax_x: Optional[torch.Tensor] = None, minmax_y: Optional[torch.Tensor] = None) -> None:
+    """One scale of d.P pairs (mf_ssim_pairs_f32 + mf_ssim_finish_f32): pair p is xbank[ix[p]] against ybank[iy[p]] (contiguous fp32 [N, C, H, W] banks,
+    int32 indices or None for the identity); sim / cs: fp32 views with one element per pair (any stride: a column of a [P, S] table), mse: [P]."""
+    _gpu(xbank, ybank, sim, cs, mse, ix, iy, minmax_x, minmax_y)
+    _need_f32(xbank, ybank)
+    if not (xbank.is_contiguous() and ybank.is_contiguous()) or tuple(xbank.shape[1:]) != (d.C, d.H, d.W) or tuple(ybank.shape[1:]) != (d.C, d.H, d.W) \
+            or xbank.shape[0] != d.Nx or ybank.shape[0] != d.Ny:
+        raise ValueError(f"ssim_pairs: contiguous banks [{d.Nx}|{d.Ny}, {d.C}, {d.H}, {d.W}], got {tuple(xbank.shape)} and {tuple(ybank.shape)}")
+    for name, idx in (("ix", ix), ("iy", iy)):
+        if idx is not None and (idx.dtype != torch.int32 or not idx.is_contiguous() or idx.numel() != d.P):
+            raise ValueError(f"ssim_pairs: {name} is a contiguous int32 [{d.P}]")
+    stride = None
+    for name, o in (("sim", sim), ("cs", cs)):
+        if o is None:
+            continue
+        if o.dtype != torch.float32 or o.dim() != 1 or o.shape[0] != d.P or (stride is not None and o.stride(0) != stride and d.P > 1):
+            raise ValueError(f"ssim_pairs: {name} is an fp32 view of {d.P} elements, of sim's stride")
+        stride = o.stride(0) if d.P > 1 else 1
+    if mse is not None and (mse.dtype != torch.float32 or not mse.is_contiguous() or mse.numel() != d.P):
+        raise ValueError(f"ssim_pairs: mse is a contiguous fp32 [{d.P}]")
+    h = L.load()
+    need = h.mf_ssim_workspace_bytes(C.byref(d))
+    if need == 0:
+        raise ValueError(f"ssim_pairs: descriptor refused: {L.last_error()}")
+    ws = Workspace.get(need, xbank.device)
+    L.check(h.mf_ssim_pairs_f32(xbank.data_ptr(), ybank.data_ptr(), _ptr(ix), _ptr(iy), _ptr(minmax_x), _ptr(minmax_y), ws.data_ptr(), ws.numel(),
+                                C.byref(d), stream()), "mf_ssim_pairs_f32")
+    L.check(h.mf_ssim_finish_f32(ws.data_ptr(), _ptr(sim), _ptr(cs), _ptr(mse), stride or 1, C.byref(d), stream()), "mf_ssim_finish_f32")
+
+
 def sched_step_blend(args: L.MfSchedArgs, blend: L.MfSchedBlend, outputs=()) -> None:
     """sched_step with the kept cells of x_t_out replaced by the known latent at the next timestep (mf_sched_step_blend_f32)"""
     _drop_outputs(outputs)

@@ -79,6 +79,14 @@ class MfWindowDesc(C.Structure):
                 ("origin", (C.c_int32 * WINDOW_MAX_PER_AXIS) * 3), ("weight", C.c_int32), ("B", C.c_int32), ("C", C.c_int32), ("reserved", C.c_int32)]
 
 
+SSIM_MAX_K = 11
+
+
+class MfSsimDesc(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("P", "C", "H", "W", "Nx", "Ny", "k", "indexed", "want_mse", "range_on_device")]
+                + [("taps", C.c_float * SSIM_MAX_K), ("k1", C.c_float), ("k2", C.c_float), ("data_range", C.c_float)])
+
+
 class MfGnFuse(C.Structure):
     _fields_ = [("gamma", c_fp), ("beta", c_fp), ("residual", c_fp), ("residual_pairs", c_fp), ("res_bound", c_fp), ("res_bound_slots", c_fp),
                 ("emb", c_fp), ("emb_bound", c_fp), ("out", c_fp), ("out_split", c_fp), ("out_bound", c_fp), ("rendezvous", c_fp), ("error_flag", c_fp),
@@ -182,6 +190,12 @@ _SIGS = {
     "mf_window_merge_f32": (_I, [c_fp, c_fp, C.POINTER(MfWindowDesc), c_fp]),
     "mf_mask_maxpool_u8": (_I, [c_fp, _I, c_fp, _I, _I, _I, _I, _I, _I, _I, c_fp]),
     "mf_image_ingress_u8": (_I, [c_fp, c_fp, _I, _I, _I, _I, c_fp]),
+    "mf_ssim_ok": (_I, [C.POINTER(MfSsimDesc)]),
+    "mf_ssim_workspace_bytes": (_SZ, [C.POINTER(MfSsimDesc)]),
+    "mf_ssim_pairs_f32": (_I, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, _SZ, C.POINTER(MfSsimDesc), c_fp]),
+    "mf_ssim_finish_f32": (_I, [c_fp, c_fp, c_fp, c_fp, _I, C.POINTER(MfSsimDesc), c_fp]),
+    "mf_avgpool2_planes_f32": (_I, [c_fp, c_fp, _I64, _I, _I, c_fp]),
+    "mf_rows_minmax_f32": (_I, [c_fp, c_fp, _I, _I64, c_fp]),
     "mf_gather_step_rows3_f32": (_I, [C.POINTER(c_fp), C.POINTER(_I64), C.POINTER(c_fp), _I, c_fp, c_fp, C.c_int32, _I, _I, c_fp]),
     "mf_broadcast_from_table_f32": (_I, [c_fp, c_fp, C.c_int32, c_fp, _I, c_fp]),
     "mf_gather_step_rows_f32": (_I, [c_fp, c_fp, c_fp, C.c_int32, _I, _I64, c_fp, _I, c_fp]),

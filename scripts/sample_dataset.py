@@ -7,7 +7,8 @@ un_cond=1 - label, steps=steps)`, each image clipped to [-1, 1], scaled to uint8
 Differences, outside the arithmetic: the clip / uint8 / channel-last conversion runs on the device and the pixels leave through pinned
 buffers with an asynchronous copy while the next chunk samples (medfusion_amd/egress.py); `--synthetic` builds the published
 architecture with seeded weights because no checkpoint exists offline; the run prints one JSON line with the images/s it reached
-with and without the egress.
+with and without the egress.  `--diversity PAIRS` (off by default; adds nothing to the run when off) also reports the mean ± std MS-SSIM over PAIRS
+random pairs of every generated set, from the device tensors, before they are written (scripts/diversity.py, medfusion_amd.metrics).
 """
 import argparse
 import json
@@ -43,7 +44,14 @@ if __name__ == "__main__":
     ap.add_argument("--sampler", default=None, choices=["ddim0", "dpmpp2m", "ddim1", "dpmpp2m_sde"],
                     help="a few-step sampler, deterministic (ddim0, dpmpp2m) or stochastic (ddim1, dpmpp2m_sde); default: the reference's loop")
     ap.add_argument("--spacing", default=None, choices=["uniform", "logsnr"], help="timestep grid of --sampler (logsnr: uniform in log-SNR)")
+    ap.add_argument("--diversity", type=int, default=0, metavar="PAIRS",
+                    help="also report the pairwise MS-SSIM (mean ± std over PAIRS random pairs, seed 0) of every generated set; 0: off.  Keeps every "
+                         "set on the device until it is measured: 2 x 4 bytes per value of --n-samples images on top of the run's own memory")
     args = ap.parse_args()
+    if args.diversity < 0:
+        ap.error("--diversity: a number of pairs")
+    if args.diversity and args.n_samples < 2:
+        ap.error("--diversity: at least two images (--n-samples) make a pair")
     solver = {} if args.sampler is None and args.spacing is None else dict(sampler=args.sampler, spacing=args.spacing)
 
     device = torch.device("cuda")
@@ -56,7 +64,7 @@ if __name__ == "__main__":
     pipeline.to(device)
     labels = [(kv.split(":")[0], int(kv.split(":")[1])) for kv in args.labels.split(",")]
     cfg = 1
-    stats = {}
+    stats, diversity_stats = {}, {}
     for egress in ([True, False] if args.compare_no_egress else [True]):
         total, t_all = 0, 0.0
         for steps in [int(v) for v in args.steps_list.split(",")]:
@@ -68,22 +76,32 @@ if __name__ == "__main__":
                 torch.manual_seed(0)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                counter = 0
+                counter, kept = 0, []
                 for chunk in chunks(list(range(args.n_samples)), args.sample_batch):
                     condition = torch.tensor([label] * len(chunk), device=device)
                     un_cond = torch.tensor([1 - label] * len(chunk), device=device)
                     results = pipeline.sample(len(chunk), (8, 32, 32), guidance_scale=cfg, condition=condition, un_cond=un_cond, steps=steps, **solver)
                     if writer is not None:
                         writer.submit(results, [path_out / f"fake_{counter + i}.png" for i in range(len(chunk))])
+                    if args.diversity and egress:
+                        kept.append((results.clamp(-1, 1) + 1) / 2)      # the set in [0, 1], on the device
                     counter += len(chunk)
                 if writer is not None:
                     writer.close()
                 torch.cuda.synchronize()
                 t_all += time.perf_counter() - t0
+                if kept:                                                   # (outside the timed region)
+                    from diversity import diversity
+                    res = diversity(torch.cat(kept), args.diversity, 0)
+                    print(f"MS-SSIM (pairwise, {res['pairs']} pairs of {res['images']} images) steps={steps} {name}: "
+                          f"{res['ms_ssim_pairwise_mean']} ± {res['ms_ssim_pairwise_std']}", file=sys.stderr)
+                    diversity_stats[f"{steps}/{name}"] = res
                 total += counter
         stats["with_egress" if egress else "images_left_on_device"] = {"images": total, "seconds": round(t_all, 3), "images_per_s": round(total / t_all, 3)}
     out = {"bulk_generation": stats, "sample_batch": args.sample_batch, "guidance_scale": cfg, "n_samples_per_class": args.n_samples, "steps": args.steps_list,
            "png_files_written": not args.no_files, "writer_threads": args.writer_threads}
     if "with_egress" in stats and "images_left_on_device" in stats:
         out["egress_overlap"] = round(stats["with_egress"]["images_per_s"] / stats["images_left_on_device"]["images_per_s"], 4)   # 1.0 = the egress is free
+    if diversity_stats:
+        out["diversity"] = diversity_stats
     print(json.dumps(out))
