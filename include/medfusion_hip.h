@@ -721,6 +721,51 @@ int mf_ssim_finish_f32(const void* workspace, float* sim, float* cs, float* mse,
 int mf_avgpool2_planes_f32(const float* x, float* y, int64_t planes, int H, int W, void* stream);
 int mf_rows_minmax_f32(const float* x, float* out, int N, int64_t n, void* stream);
 
+/* Improved precision / recall of two feature sets on the device (additive to ABI 250): squared distances between the rows of two contiguous fp32
+ * feature banks [rows][D] on the fp32 matrix cores, the k-NN radius of every row of a bank, and the membership of query rows in a bank's manifold
+ * -- the last two WITHOUT the rows x rows matrix ever being written.  The definition: xt = fl32(x - pivot), n(x) = the fp64 sum of xt_k^2 rounded
+ * to fp32, d2(x, y) = max(0, fl32(fl32(n(x) + n(y)) - 2 dot(xt, yt))) with dot ONE fp32 fmaf chain over k ascending (v_mfma_f32_32x32x2_f32; no
+ * split-K).  The bits of d2(i, j) depend on the two rows and the pivot only: not on N, M, the tile, the grid or the rows' places in their banks,
+ * and d2(i, j) of (x, y) equals d2(j, i) of (y, x).  Sixteen-byte loads when D % 4 == 0 and the banks and the pivot are 16-byte aligned, element
+ * loads otherwise: the same bits.  Every global access is masked: N, M and D are arbitrary.
+ *   mf_feat_colmean_f32      pivot[k] = the fp64 mean of column k of x [N][D], rows added in a fixed order, rounded to fp32.
+ *   mf_feat_norms_f32        norms[i] = n(x_i), one wave per row, fp64, a fixed order.
+ *   mf_feat_sqdist_f32       out [N][M] = d2(x_i, y_j); with same_bank (x == y, nx == ny) the diagonal is stored as exactly 0.
+ *   mf_knn_partial_f32       grid (row tiles of 128, `splits` column splits): every row's MF_FIDELITY_LIST smallest d2(x_i, x_j) over the split's column
+ *                            tiles, ascending, the j == i entry counted as exactly 0, +inf where a split holds fewer; [splits][N][MF_FIDELITY_LIST]
+ *                            floats to the workspace.  desc->N rows; desc->M is not read.
+ *   mf_knn_finish_f32        merges the splits in ascending order: radii_sq[i] = the (knn + 1)-th smallest (the reference's topk(knn + 1), self included).
+ *   mf_manifold_partial_f32  grid (query tiles of 128, `splits` splits of the reference rows): flag[s][j] = any_i [d2(ref_i, query_j) < radii_sq[i]]
+ *                            (strict, on squared values) over the split's rows, as bytes [splits][M] to the workspace.  desc->N reference rows,
+ *                            desc->M queries.
+ *   mf_manifold_finish_f32   ORs the splits in ascending order: hit[j] (0 / 1) and count = the number of hits, by a fixed tree in one workgroup;
+ *                            either output may be null.
+ * No atomics: the same bits on every launch and for every `splits`.  Launches are asynchronous on `stream`; nothing is allocated, retained or
+ * read back.  mf_fidelity_ok / mf_fidelity_workspace_bytes are host-only (the rules: 1 <= knn <= 15, knn < N, 1 <= N, M < 2^24, 1 <= D <= 65536,
+ * 1 <= splits <= MF_FIDELITY_MAX_SPLITS, same_bank only with M == N); the workspace (16-byte aligned) serves either pair of launches:
+ * max(splits N MF_FIDELITY_LIST 4, splits M rounded up to 16) bytes.  Every entry point refuses a bad descriptor with MF_EINVAL before any launch. */
+#define MF_FIDELITY_LIST 16
+#define MF_FIDELITY_MAX_SPLITS 16
+typedef struct MfFidelityDesc {
+  int32_t N, M, D;                /* rows of the first bank (the reference rows), rows of the second (the queries), features per row */
+  int32_t knn;                    /* 1 .. 15, < N */
+  int32_t splits;                 /* 1 .. MF_FIDELITY_MAX_SPLITS */
+  int32_t same_bank;              /* 1: both banks are one (mf_feat_sqdist_f32: the diagonal is exactly 0) */
+  int32_t reserved[2];
+} MfFidelityDesc;
+int mf_fidelity_ok(const MfFidelityDesc* desc);
+size_t mf_fidelity_workspace_bytes(const MfFidelityDesc* desc);
+int mf_feat_colmean_f32(const float* x, float* pivot, int N, int D, void* stream);
+int mf_feat_norms_f32(const float* x, const float* pivot, float* norms, int N, int D, void* stream);
+int mf_feat_sqdist_f32(const float* x, const float* nx, const float* y, const float* ny, const float* pivot, float* out, const MfFidelityDesc* desc,
+                       void* stream);
+int mf_knn_partial_f32(const float* x, const float* nx, const float* pivot, void* workspace, size_t workspace_bytes, const MfFidelityDesc* desc,
+                       void* stream);
+int mf_knn_finish_f32(const void* workspace, float* radii_sq, const MfFidelityDesc* desc, void* stream);
+int mf_manifold_partial_f32(const float* ref, const float* nref, const float* radii_sq, const float* query, const float* nquery, const float* pivot,
+                            void* workspace, size_t workspace_bytes, const MfFidelityDesc* desc, void* stream);
+int mf_manifold_finish_f32(const void* workspace, uint8_t* hit, int32_t* count, const MfFidelityDesc* desc, void* stream);
+
 /* ------------------------------------------------------------------ built-in launch timing (bench / roofline)
  * When enabled every launch is bracketed by hipEvents on its own stream and attributed to a kernel family.
  * NOT capture-safe; off by default. */

@@ -5,7 +5,9 @@ Drop-in for the reference's sampling API (`DiffusionPipeline.sample/denoise/forw
 C-ABI (include/medfusion_hip.h).  No CPU fallback: the library must load and tensors must be on the GPU.
 """
 from .lib import load as load_library  # noqa: F401
-from . import metrics  # noqa: F401
+from . import fidelity, metrics  # noqa: F401
+from .fidelity import (EmbedderFeatures, FidelityMeter, frechet_distance, knn_radii, manifold_hits, pairwise_sqdist,  # noqa: F401
+                       precision_recall)
 from .metrics import ReconstructionMeter, ms_ssim, mse, pairwise_ms_ssim, ssim  # noqa: F401
 from .noise import HostNoise, NoiseSource, PhiloxDeviceNoise, torch_cpu_noise  # noqa: F401
 from .pipeline import DiffusionPipeline, EMAModel  # noqa: F401

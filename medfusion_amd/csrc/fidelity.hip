@@ -1,0 +1,475 @@
+// fidelity.hip -- improved precision / recall of two feature sets on the device (include/medfusion_hip.h, MfFidelityDesc): squared distances between
+// the rows of two fp32 feature banks on the fp32 matrix cores, and three things done with a 128 x 128 tile of them while it is still in the
+// accumulators: stored (mf_feat_sqdist_f32), merged into every row's ascending list of its 16 smallest (the k-NN radii), or compared with the
+// rows' radii (manifold membership).  The N x M matrix is never written by the last two.
+//
+// The definition (README "Fidelity"): xt = fl32(x - c) with the pivot c, n(x) = the fp64 sum of xt_k^2 rounded to fp32,
+//   d2(x, y) = max(0, fl32(fl32(n(x) + n(y)) - 2 dot(xt, yt))),   dot = ONE fp32 fmaf chain over k ascending (v_mfma_f32_32x32x2_f32 is that chain).
+// There is no split-K: the bits of d2(i, j) depend on the two rows and the pivot only -- not on the tile, the grid, N, M or the rows' places in
+// their banks -- and d2(i, j) of (x, y) is d2(j, i) of (y, x).  No atomics anywhere: the column / row splits of the k-NN and manifold launches write
+// partial lists / flags to a workspace, and a finish launch merges them in ascending split order.
+// Built without packed fp32 like metrics.hip (medfusion_amd/build.py): the staging subtraction and the epilogues are plain fp32 VALU work.
+#include "common.h"
+
+#include <math.h>
+
+using namespace mf;
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+constexpr int TM = 128;                 // rows of bank A and rows of bank B per workgroup: a TM x TM tile of d2
+constexpr int BK = 32;                  // k per staged chunk
+constexpr int LDK = BK + 4;             // a staged row: +4 floats, so that the sixteen lanes of a ds_read_b128 group hit sixteen different 16-byte slots
+constexpr int OPER = TM * LDK;          // one operand's chunk
+constexpr int BUF = 2 * OPER;           // A and B of one chunk
+constexpr int STAGE = 2 * BUF;          // two chunks: 18432 floats
+constexpr int LDT = TM + 1;             // a row of the d2 tile when it goes through LDS (the k-NN selection reads it row by thread)
+constexpr int LIST = MF_FIDELITY_LIST;  // 16 values per row and split
+static_assert(TM * LDT <= STAGE && TM * (LIST + 1) <= STAGE, "the epilogues reuse the staging buffers");
+constexpr int SMEM = STAGE + 2 * TM;    // + the A rows' norms and radii
+
+// One chunk of one operand, global -> registers: 128 rows x 32 k as 1024 groups of four consecutive k, four groups per thread.  The pivot is
+// subtracted here; zeros past the last row and past D (a zero row adds fma(0, 0, acc) = acc to the chain: nothing).  V = 4: sixteen-byte loads
+// (D % 4 == 0: a group is inside or outside as a whole); V = 1: element by element.  The same values either way.  Every load is issued
+// UNCONDITIONALLY from an address clamped into the bank and masked afterwards by a select: a branch around a load makes the compiler wait for
+// each load before the next one, eight memory round trips per chunk instead of one.
+template <int V>
+__device__ __forceinline__ void load_chunk(const float* __restrict__ bank, int rows, int r0, int D, int k0, const float* __restrict__ pivot, int t,
+                                           f32x4 (&reg)[4]) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int idx = t + 256 * q, row = idx >> 3, k = k0 + (idx & 7) * 4;
+    const bool row_in = r0 + row < rows;
+    const float* __restrict__ p = bank + (long)min(r0 + row, rows - 1) * D;
+    f32x4 v;
+    if (V == 4) {
+      const int kc = min(k, D - 4);
+      const f32x4 d = *reinterpret_cast<const f32x4*>(p + kc) - *reinterpret_cast<const f32x4*>(pivot + kc);
+      const bool in = row_in && k < D;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = in ? d[e] : 0.f;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int kc = min(k + e, D - 1);
+        const float d = p[kc] - pivot[kc];
+        v[e] = (row_in && k + e < D) ? d : 0.f;
+      }
+    }
+    reg[q] = v;
+  }
+}
+
+// registers -> LDS.  Inside every group of eight k the staged order is k = 0 2 4 6 1 3 5 7: lane (row, half h) of the wave then reads ITS four
+// operands of the next four matrix instructions -- k = 2t + h, t = 0 .. 3 -- as one 16-byte read, and instruction t covers k = 2t, 2t + 1: ascending.
+__device__ __forceinline__ void store_chunk(float* __restrict__ dst, int t, const f32x4 (&reg)[4]) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int idx = t + 256 * q, row = idx >> 3, c4 = idx & 7;
+    float* d = dst + row * LDK + 8 * (c4 >> 1) + 2 * (c4 & 1);
+    *reinterpret_cast<f32x2*>(d) = f32x2{reg[q][0], reg[q][2]};
+    *reinterpret_cast<f32x2*>(d + 4) = f32x2{reg[q][1], reg[q][3]};
+  }
+}
+
+// acc[m][n] = the dot products of A rows a0 + wr 64 + m 32 + (0 .. 31) with B rows b0 + wc 64 + n 32 + (0 .. 31), wave (wr, wc) of the 2 x 2 waves.
+// K goes through LDS in chunks of BK, two buffers: the next chunk's global loads are in flight while this one is multiplied, and are written to
+// the other buffer behind it -- one barrier per chunk.  Enters with a barrier (smem may still be read as the previous tile's d2) and leaves with
+// one (smem is free again).
+template <int V>
+__device__ __forceinline__ void tile_dot(const float* __restrict__ A, int NA, int a0, const float* __restrict__ B, int NB, int b0, int D,
+                                         const float* __restrict__ pivot, float* __restrict__ smem, f32x16 (&acc)[2][2]) {
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wr = wave >> 1, wc = wave & 1, j = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
+  f32x4 ra[4], rb[4];
+  const int chunks = (D + BK - 1) / BK;
+  load_chunk<V>(A, NA, a0, D, 0, pivot, t, ra);
+  load_chunk<V>(B, NB, b0, D, 0, pivot, t, rb);
+  __syncthreads();
+  store_chunk(smem, t, ra);
+  store_chunk(smem + OPER, t, rb);
+  __syncthreads();
+  for (int c = 0; c < chunks; ++c) {
+    const float* cur = smem + (c & 1) * BUF;
+    const bool more = c + 1 < chunks;
+    if (more) {
+      load_chunk<V>(A, NA, a0, D, (c + 1) * BK, pivot, t, ra);
+      load_chunk<V>(B, NB, b0, D, (c + 1) * BK, pivot, t, rb);
+    }
+    const float* As = cur + (wr * 64 + j) * LDK + 4 * h;
+    const float* Bs = cur + OPER + (wc * 64 + j) * LDK + 4 * h;
+#pragma unroll
+    for (int g = 0; g < BK / 8; ++g) {
+      const f32x4 fa0 = *reinterpret_cast<const f32x4*>(As + 8 * g), fa1 = *reinterpret_cast<const f32x4*>(As + 32 * LDK + 8 * g);
+      const f32x4 fb0 = *reinterpret_cast<const f32x4*>(Bs + 8 * g), fb1 = *reinterpret_cast<const f32x4*>(Bs + 32 * LDK + 8 * g);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa0[s], fb0[s], acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa0[s], fb1[s], acc[0][1], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa1[s], fb0[s], acc[1][0], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa1[s], fb1[s], acc[1][1], 0, 0, 0);
+      }
+    }
+    if (more) {
+      float* nxt = smem + ((c + 1) & 1) * BUF;
+      store_chunk(nxt, t, ra);
+      store_chunk(nxt + OPER, t, rb);
+    }
+    __syncthreads();
+  }
+}
+
+// d2 of every element this lane holds, handed to f(local row, local column, d2).  Accumulator layout of the 32 x 32 instruction: the lane's
+// column is lane & 31, register r is row (r & 3) + 8 (r >> 2) + 4 (lane >> 5).  na: the A rows' norms in LDS; nb: the norms of the lane's two columns.
+template <class F>
+__device__ __forceinline__ void for_each_d2(const f32x16 (&acc)[2][2], const float* __restrict__ na, const float (&nb)[2], F f) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wr = wave >> 1, wc = wave & 1, j = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int il = wr * 64 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, jl = wc * 64 + n * 32 + j;
+        const float s = na[il] + nb[n];
+        f(il, jl, n, fmaxf(s - 2.f * acc[m][n][r], 0.f));
+      }
+}
+
+__device__ __forceinline__ void column_norms(const float* __restrict__ nb, int NB, int b0, float (&out)[2]) {
+  const int lane = threadIdx.x & 63, wc = (threadIdx.x >> 6) & 1;
+#pragma unroll
+  for (int n = 0; n < 2; ++n) {
+    const int jg = b0 + wc * 64 + n * 32 + (lane & 31);
+    out[n] = jg < NB ? nb[jg] : 0.f;
+  }
+}
+
+// ---- epilogue 1: the matrix itself
+template <int V>
+__global__ __launch_bounds__(256) void sqdist_kernel(const float* __restrict__ x, const float* __restrict__ nx, const float* __restrict__ y,
+                                                     const float* __restrict__ ny, const float* __restrict__ pivot, float* __restrict__ out, int N, int M,
+                                                     int D, int col_tiles, int same_bank) {
+  __shared__ __attribute__((aligned(16))) float smem[SMEM];
+  const int t = threadIdx.x;
+  const int rt = blockIdx.x / col_tiles, ct = blockIdx.x - rt * col_tiles;
+  const int a0 = rt * TM, b0 = ct * TM;
+  float* na = smem + STAGE;
+  if (t < TM) na[t] = a0 + t < N ? nx[a0 + t] : 0.f;
+  f32x16 acc[2][2];
+  tile_dot<V>(x, N, a0, y, M, b0, D, pivot, smem, acc);
+  float nb[2];
+  column_norms(ny, M, b0, nb);
+  for_each_d2(acc, na, nb, [&](int il, int jl, int, float d) {
+    const int ig = a0 + il, jg = b0 + jl;
+    if (ig < N && jg < M) out[(long)ig * M + jg] = (same_bank && ig == jg) ? 0.f : d;
+  });
+}
+
+// the ascending list of the 16 smallest values seen: v goes in where it belongs, the largest falls out
+__device__ __forceinline__ void list_insert(float (&l)[LIST], float v) {
+  if (v < l[LIST - 1]) {
+#pragma unroll
+    for (int p = 0; p < LIST; ++p) {
+      const float lo = fminf(l[p], v);
+      v = fmaxf(l[p], v);
+      l[p] = lo;
+    }
+  }
+}
+
+// ---- epilogue 2: every row's 16 smallest d2 over the column tiles of split blockIdx.y (the row itself counts, as exactly 0)
+// After each column tile the d2 tile goes to LDS (the accumulator layout spreads a row over lanes and registers); thread (row, half) merges 64 of
+// the row's 128 values into its own list, the two halves meet at the end.  Only values are kept: ties cannot matter.
+template <int V>
+__global__ __launch_bounds__(256, 2) void knn_partial_kernel(const float* __restrict__ x, const float* __restrict__ nx, const float* __restrict__ pivot,
+                                                          float* __restrict__ part, int N, int D, int S) {
+  __shared__ __attribute__((aligned(16))) float smem[SMEM];
+  const int t = threadIdx.x, row = t & (TM - 1), half = t >> 7;
+  const int a0 = blockIdx.x * TM, s = blockIdx.y;
+  const int col_tiles = (N + TM - 1) / TM;
+  const int cb = (int)((long)s * col_tiles / S), ce = (int)((long)(s + 1) * col_tiles / S);
+  float* na = smem + STAGE;
+  if (t < TM) na[t] = a0 + t < N ? nx[a0 + t] : 0.f;
+  float l[LIST];
+#pragma unroll
+  for (int p = 0; p < LIST; ++p) l[p] = INFINITY;
+  for (int ct = cb; ct < ce; ++ct) {
+    const int b0 = ct * TM;
+    f32x16 acc[2][2];
+    tile_dot<V>(x, N, a0, x, N, b0, D, pivot, smem, acc);
+    float nb[2];
+    column_norms(nx, N, b0, nb);
+    for_each_d2(acc, na, nb, [&](int il, int jl, int, float d) {
+      const int ig = a0 + il, jg = b0 + jl;
+      smem[il * LDT + jl] = jg >= N ? INFINITY : (ig == jg ? 0.f : d);
+    });
+    __syncthreads();
+    const float* mine = smem + row * LDT + half * 64;
+    for (int c = 0; c < 64; ++c) list_insert(l, mine[c]);
+  }
+  __syncthreads();
+  if (half == 1) {
+#pragma unroll
+    for (int p = 0; p < LIST; ++p) smem[row * (LIST + 1) + p] = l[p];
+  }
+  __syncthreads();
+  if (half == 0) {
+#pragma unroll
+    for (int p = 0; p < LIST; ++p) list_insert(l, smem[row * (LIST + 1) + p]);
+    if (a0 + row < N) {
+      float* o = part + ((long)s * N + a0 + row) * LIST;
+#pragma unroll
+      for (int p = 0; p < LIST; p += 4) *reinterpret_cast<f32x4*>(o + p) = f32x4{l[p], l[p + 1], l[p + 2], l[p + 3]};
+    }
+  }
+}
+
+// r2[i] = the (knn + 1)-th smallest of row i: the S partial lists merged in ascending split order, one thread per row
+__global__ __launch_bounds__(256) void knn_finish_kernel(const float* __restrict__ part, float* __restrict__ r2, int N, int S, int knn) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  float l[LIST];
+  const float* q = part + (long)i * LIST;
+#pragma unroll
+  for (int p = 0; p < LIST; ++p) l[p] = q[p];
+  for (int s = 1; s < S; ++s) {
+    q = part + ((long)s * N + i) * LIST;
+    for (int p = 0; p < LIST; ++p) list_insert(l, q[p]);
+  }
+  float v = l[0];
+#pragma unroll
+  for (int p = 1; p < LIST; ++p) v = p == knn ? l[p] : v;
+  r2[i] = v;
+}
+
+// ---- epilogue 3: is query j inside any reference row's ball?  hit_j = any_i [d2(R_i, Q_j) < r2_i], strict, over the reference tiles of split blockIdx.y.
+// The queries are the tile's COLUMNS: a lane owns two of them for the whole launch and ORs over its registers, tile after tile.
+template <int V>
+__global__ __launch_bounds__(256, 2) void manifold_partial_kernel(const float* __restrict__ ref, const float* __restrict__ nref, const float* __restrict__ r2,
+                                                               const float* __restrict__ qry, const float* __restrict__ nqry,
+                                                               const float* __restrict__ pivot, uint8_t* __restrict__ part, int NR, int M, int D, int S) {
+  __shared__ __attribute__((aligned(16))) float smem[SMEM];
+  const int t = threadIdx.x;
+  const int b0 = blockIdx.x * TM, s = blockIdx.y;
+  const int row_tiles = (NR + TM - 1) / TM;
+  const int rb = (int)((long)s * row_tiles / S), re = (int)((long)(s + 1) * row_tiles / S);
+  float* na = smem + STAGE;
+  float* rad = na + TM;
+  float nb[2];
+  column_norms(nqry, M, b0, nb);
+  bool hit[2] = {false, false};
+  for (int rt = rb; rt < re; ++rt) {
+    const int a0 = rt * TM;
+    if (t < TM) {
+      const bool in = a0 + t < NR;
+      na[t] = in ? nref[a0 + t] : 0.f;
+      rad[t] = in ? r2[a0 + t] : -1.f;     // d2 >= 0: a row past the end holds nobody
+    }
+    f32x16 acc[2][2];
+    tile_dot<V>(ref, NR, a0, qry, M, b0, D, pivot, smem, acc);
+    for_each_d2(acc, na, nb, [&](int il, int, int n, float d) { hit[n] = hit[n] || d < rad[il]; });
+    __syncthreads();                       // na / rad are rewritten by the next tile
+  }
+  int* flags = reinterpret_cast<int*>(smem);
+  if (t < TM) flags[t] = 0;
+  __syncthreads();
+  const int lane = t & 63, wc = (t >> 6) & 1;
+#pragma unroll
+  for (int n = 0; n < 2; ++n)
+    if (hit[n]) flags[wc * 64 + n * 32 + (lane & 31)] = 1;    // (several lanes may store the same 1)
+  __syncthreads();
+  if (t < TM && b0 + t < M) part[(long)s * M + b0 + t] = (uint8_t)flags[t];
+}
+
+// hit[j] = the OR of the S partial flags in ascending split order; count = their number, by a fixed tree.  ONE workgroup.
+__global__ __launch_bounds__(1024) void manifold_finish_kernel(const uint8_t* __restrict__ part, uint8_t* __restrict__ hit, int* __restrict__ count, int M,
+                                                               int S) {
+  __shared__ int red[1024];
+  int c = 0;
+  for (int j = threadIdx.x; j < M; j += 1024) {
+    uint8_t f = 0;
+    for (int s = 0; s < S; ++s) f |= part[(long)s * M + j];
+    f = f ? 1 : 0;
+    if (hit) hit[j] = f;
+    c += f;
+  }
+  red[threadIdx.x] = c;
+  __syncthreads();
+  for (int o = 512; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && count) *count = red[0];
+}
+
+// n(x) of every row: xt = fl32(x - c), the sum of xt^2 in fp64 -- lane l of the row's wave takes k = l, l + 64, ... ascending, then a fixed shuffle
+// tree -- rounded to fp32.  Four rows per workgroup, one wave each; element loads, so a row's result does not depend on its alignment or place.
+__global__ __launch_bounds__(256) void norms_kernel(const float* __restrict__ x, const float* __restrict__ pivot, float* __restrict__ out, int N, int D) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= N) return;
+  const float* __restrict__ p = x + row * D;
+  double s = 0.0;
+  for (int k = lane; k < D; k += 64) {
+    const float v = p[k] - pivot[k];
+    s += (double)v * (double)v;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if (lane == 0) out[row] = (float)s;
+}
+
+// c[k] = the mean of column k in fp64, rounded to fp32.  A workgroup takes 32 columns; thread (column, phase p of 8) adds rows p, p + 8, ... in
+// ascending order, the eight phases are added in ascending order.
+__global__ __launch_bounds__(256) void colmean_kernel(const float* __restrict__ x, float* __restrict__ out, int N, int D) {
+  __shared__ double red[8][32];
+  const int col = threadIdx.x & 31, ph = threadIdx.x >> 5;
+  const int k = blockIdx.x * 32 + col;
+  double s = 0.0;
+  if (k < D)
+    for (long i = ph; i < N; i += 8) s += (double)x[i * D + k];
+  red[ph][col] = s;
+  __syncthreads();
+  if (ph == 0 && k < D) {
+    double a = red[0][col];
+#pragma unroll
+    for (int p = 1; p < 8; ++p) a += red[p][col];
+    out[k] = (float)(a / (double)N);
+  }
+}
+
+// the descriptor's rules, on the host, before any launch
+int fidelity_rules(const MfFidelityDesc* d, const char* what) {
+  MF_REQUIRE(d != nullptr, MF_EINVAL, "%s: no descriptor", what);
+  MF_REQUIRE(d->N >= 1 && d->N < (1 << 24) && d->M >= 1 && d->M < (1 << 24), MF_EINVAL, "%s: N=%d M=%d (1 .. 2^24 - 1)", what, d->N, d->M);
+  MF_REQUIRE(d->D >= 1 && d->D <= 65536, MF_EINVAL, "%s: D=%d (1 .. 65536)", what, d->D);
+  MF_REQUIRE(d->knn >= 1 && d->knn <= MF_FIDELITY_LIST - 1, MF_EINVAL, "%s: knn=%d (1 .. %d)", what, d->knn, MF_FIDELITY_LIST - 1);
+  MF_REQUIRE(d->knn < d->N, MF_EINVAL, "%s: knn=%d needs more than %d rows", what, d->knn, d->N);
+  MF_REQUIRE(d->splits >= 1 && d->splits <= MF_FIDELITY_MAX_SPLITS, MF_EINVAL, "%s: splits=%d (1 .. %d)", what, d->splits, MF_FIDELITY_MAX_SPLITS);
+  MF_REQUIRE((d->same_bank & ~1) == 0, MF_EINVAL, "%s: same_bank is 0 or 1", what);
+  MF_REQUIRE(!d->same_bank || d->M == d->N, MF_EINVAL, "%s: same_bank with N=%d M=%d", what, d->N, d->M);
+  return MF_OK;
+}
+
+inline size_t knn_bytes(const MfFidelityDesc* d) { return (size_t)d->splits * d->N * LIST * sizeof(float); }
+inline size_t manifold_bytes(const MfFidelityDesc* d) { return ((size_t)d->splits * d->M + 15) & ~(size_t)15; }
+
+inline bool by16(int D, std::initializer_list<const void*> ptrs) {
+  uintptr_t bits = 0;
+  for (const void* p : ptrs) bits |= (uintptr_t)p;
+  return D % 4 == 0 && (bits & 15) == 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mf_fidelity_ok(const MfFidelityDesc* desc) { return fidelity_rules(desc, "fidelity_ok") == MF_OK ? 1 : 0; }
+
+size_t mf_fidelity_workspace_bytes(const MfFidelityDesc* desc) {
+  if (fidelity_rules(desc, "fidelity_workspace_bytes") != MF_OK) return 0;
+  const size_t a = knn_bytes(desc), b = manifold_bytes(desc);
+  return a > b ? a : b;
+}
+
+int mf_feat_colmean_f32(const float* x, float* pivot, int N, int D, void* stream) {
+  MF_REQUIRE(x && pivot && N >= 1 && N < (1 << 24) && D >= 1 && D <= 65536, MF_EINVAL, "feat_colmean: N=%d D=%d", N, D);
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(MF_FAM_MISC, s, (double)N * D, 4.0 * N * D);
+  MF_LAUNCH(colmean_kernel, dim3(cdiv(D, 32)), dim3(256), 0, s, x, pivot, N, D);
+  return check_launch("feat_colmean");
+}
+
+int mf_feat_norms_f32(const float* x, const float* pivot, float* norms, int N, int D, void* stream) {
+  MF_REQUIRE(x && pivot && norms && N >= 1 && N < (1 << 24) && D >= 1 && D <= 65536, MF_EINVAL, "feat_norms: N=%d D=%d", N, D);
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(MF_FAM_MISC, s, 3.0 * N * D, 4.0 * N * D);
+  MF_LAUNCH(norms_kernel, dim3(cdiv(N, 4)), dim3(256), 0, s, x, pivot, norms, N, D);
+  return check_launch("feat_norms");
+}
+
+int mf_feat_sqdist_f32(const float* x, const float* nx, const float* y, const float* ny, const float* pivot, float* out, const MfFidelityDesc* desc,
+                       void* stream) {
+  const int rc = fidelity_rules(desc, "feat_sqdist");
+  if (rc != MF_OK) return rc;
+  MF_REQUIRE(x && nx && y && ny && pivot && out, MF_EINVAL, "feat_sqdist: bad args");
+  MF_REQUIRE(!desc->same_bank || (x == y && nx == ny), MF_EINVAL, "feat_sqdist: same_bank with two banks");
+  const long row_tiles = cdiv(desc->N, TM), col_tiles = cdiv(desc->M, TM);
+  MF_REQUIRE(row_tiles * col_tiles <= 0x7fffffffL, MF_EINVAL, "feat_sqdist: %ld x %ld tiles", row_tiles, col_tiles);
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(MF_FAM_MISC, s, 2.0 * desc->N * desc->M * desc->D, 4.0 * ((double)desc->N * desc->M + ((double)desc->N + desc->M) * desc->D));
+  const dim3 grid((unsigned)(row_tiles * col_tiles));
+  if (by16(desc->D, {x, y, pivot}))
+    MF_LAUNCH(sqdist_kernel<4>, grid, dim3(256), 0, s, x, nx, y, ny, pivot, out, desc->N, desc->M, desc->D, (int)col_tiles, desc->same_bank);
+  else
+    MF_LAUNCH(sqdist_kernel<1>, grid, dim3(256), 0, s, x, nx, y, ny, pivot, out, desc->N, desc->M, desc->D, (int)col_tiles, desc->same_bank);
+  return check_launch("feat_sqdist");
+}
+
+int mf_knn_partial_f32(const float* x, const float* nx, const float* pivot, void* workspace, size_t workspace_bytes, const MfFidelityDesc* desc,
+                       void* stream) {
+  const int rc = fidelity_rules(desc, "knn_partial");
+  if (rc != MF_OK) return rc;
+  MF_REQUIRE(x && nx && pivot && workspace, MF_EINVAL, "knn_partial: bad args");
+  MF_REQUIRE(((uintptr_t)workspace & 15) == 0, MF_EINVAL, "knn_partial: a 16-byte aligned workspace");
+  MF_REQUIRE(workspace_bytes >= knn_bytes(desc), MF_EWORKSPACE, "knn_partial: workspace of %zu bytes, %zu needed", workspace_bytes, knn_bytes(desc));
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(MF_FAM_MISC, s, 2.0 * desc->N * desc->N * desc->D, 4.0 * desc->N * desc->D);
+  const dim3 grid(cdiv(desc->N, TM), desc->splits);
+  if (by16(desc->D, {x, pivot}))
+    MF_LAUNCH(knn_partial_kernel<4>, grid, dim3(256), 0, s, x, nx, pivot, (float*)workspace, desc->N, desc->D, desc->splits);
+  else
+    MF_LAUNCH(knn_partial_kernel<1>, grid, dim3(256), 0, s, x, nx, pivot, (float*)workspace, desc->N, desc->D, desc->splits);
+  return check_launch("knn_partial");
+}
+
+int mf_knn_finish_f32(const void* workspace, float* radii_sq, const MfFidelityDesc* desc, void* stream) {
+  const int rc = fidelity_rules(desc, "knn_finish");
+  if (rc != MF_OK) return rc;
+  MF_REQUIRE(workspace && radii_sq, MF_EINVAL, "knn_finish: bad args");
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(MF_FAM_MISC, s, 0, (double)knn_bytes(desc));
+  MF_LAUNCH(knn_finish_kernel, dim3(cdiv(desc->N, 256)), dim3(256), 0, s, (const float*)workspace, radii_sq, desc->N, desc->splits, desc->knn);
+  return check_launch("knn_finish");
+}
+
+int mf_manifold_partial_f32(const float* ref, const float* nref, const float* radii_sq, const float* query, const float* nquery, const float* pivot,
+                            void* workspace, size_t workspace_bytes, const MfFidelityDesc* desc, void* stream) {
+  const int rc = fidelity_rules(desc, "manifold_partial");
+  if (rc != MF_OK) return rc;
+  MF_REQUIRE(ref && nref && radii_sq && query && nquery && pivot && workspace, MF_EINVAL, "manifold_partial: bad args");
+  MF_REQUIRE(workspace_bytes >= manifold_bytes(desc), MF_EWORKSPACE, "manifold_partial: workspace of %zu bytes, %zu needed", workspace_bytes,
+             manifold_bytes(desc));
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(MF_FAM_MISC, s, 2.0 * desc->N * desc->M * desc->D, 4.0 * ((double)desc->N + desc->M) * desc->D);
+  const dim3 grid(cdiv(desc->M, TM), desc->splits);
+  if (by16(desc->D, {ref, query, pivot}))
+    MF_LAUNCH(manifold_partial_kernel<4>, grid, dim3(256), 0, s, ref, nref, radii_sq, query, nquery, pivot, (uint8_t*)workspace, desc->N, desc->M, desc->D,
+              desc->splits);
+  else
+    MF_LAUNCH(manifold_partial_kernel<1>, grid, dim3(256), 0, s, ref, nref, radii_sq, query, nquery, pivot, (uint8_t*)workspace, desc->N, desc->M, desc->D,
+              desc->splits);
+  return check_launch("manifold_partial");
+}
+
+int mf_manifold_finish_f32(const void* workspace, uint8_t* hit, int32_t* count, const MfFidelityDesc* desc, void* stream) {
+  const int rc = fidelity_rules(desc, "manifold_finish");
+  if (rc != MF_OK) return rc;
+  MF_REQUIRE(workspace && (hit || count), MF_EINVAL, "manifold_finish: bad args");
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(MF_FAM_MISC, s, 0, (double)manifold_bytes(desc));
+  MF_LAUNCH(manifold_finish_kernel, dim3(1), dim3(1024), 0, s, (const uint8_t*)workspace, hit, count, desc->M, desc->splits);
+  return check_launch("manifold_finish");
+}
+
+}  // extern "C"

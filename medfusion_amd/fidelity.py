@@ -1,0 +1,269 @@
+"""Fidelity of a generated set in a feature space: improved precision / recall (k-NN manifolds, Kynkaanniemi et al. 2019) and the Frechet distance,
+the figures the reference's evaluate_images.py logs -- everything after the feature extractor (csrc/fidelity.hip, include/medfusion_hip.h
+MfFidelityDesc).
+
+The definition is stated HERE (README "Fidelity") and equals the reference's in exact arithmetic.  Features real [N, D], fake [M, D], fp32.  The
+pivot c is the fp64 column mean of `real` rounded to fp32, xt = fl32(x - c), n(x) = the fp64 sum of xt_k^2 rounded to fp32,
+    d2(x, y) = max(0, fl32(fl32(n(x) + n(y)) - 2 dot(xt, yt))),     dot: ONE fp32 fmaf chain over k ascending (the fp32 matrix cores).
+The radius of row i of a bank X is r2_i = the (knn + 1)-th smallest of d2(X_i, X_j) over all j, the j = i entry being exactly 0; query j is inside
+the manifold of R when d2(R_i, Q_j) < r2_i for some i (strict, on squared values: no square root on the device).  precision = the share of fake
+rows inside the manifold of real, recall = the share of real rows inside the manifold of fake, both with the pivot of real.  The N x M matrix is
+never materialised (the reference builds it in full and loops over the generated samples in Python).
+
+frechet_distance is host-side fp64 torch: |mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr (S1 S2)^1/2, the last term as the sum of sqrt(max(lambda_k, 0)) over
+the eigenvalues of S1^1/2 S2 S1^1/2 -- two symmetric eigen-decompositions, no general sqrtm, no complex parts.
+
+Every argument error is a ValueError that names the argument, raised before anything touches the device."""
+from __future__ import annotations
+
+import torch
+
+from . import kernels as K
+from . import lib as L
+
+TILE = 128               # rows (and columns) of the distance tile of one workgroup
+SLOTS = 512              # workgroups the MI355X holds at once: two per compute unit (registers and LDS of the fused kernels), 256 units.
+                         # A model: its choice was timed at ONE shape (10 000 x 10 000 x 2048, profiles/fidelity_bench.txt), nowhere else.
+
+
+def plan_splits(rows: int, cols: int) -> int:
+    """How many splits S of the `cols` axis a launch over `rows` x `cols` distances takes.  A workgroup owns one tile of `rows` and walks
+    ceil(col tiles / S) column tiles; the chip runs SLOTS workgroups at a time, so the launch lasts ceil(row tiles * S / SLOTS) rounds of that walk.
+    S minimises rounds x walk -- enough workgroups for the chip when the bank has few rows, and no nearly empty last round -- among 1 .. 16 and
+    at most the number of column tiles; of equal plans the one with the fewest splits (the smallest workspace)."""
+    if rows < 1 or cols < 1:
+        raise ValueError(f"plan_splits: rows={rows} cols={cols}")
+    row_tiles, col_tiles = -(-rows // TILE), -(-cols // TILE)
+    cost = lambda s: -(-row_tiles * s // SLOTS) * -(-col_tiles // s)
+    return min(range(1, min(L.FIDELITY_MAX_SPLITS, col_tiles) + 1), key=lambda s: (cost(s), s))
+
+
+def workspace_bytes(n: int, m: int, splits: int) -> int:
+    """the bytes mf_fidelity_workspace_bytes answers for (N, M, splits): the k-NN partial lists or the manifold's partial flags, whichever is more"""
+    return max(splits * n * L.FIDELITY_LIST * 4, (splits * m + 15) // 16 * 16)
+
+
+# ------------------------------------------------------------------------------------------------ argument rules (host only)
+def _check_bank(name: str, t, min_rows: int = 2) -> None:
+    """the host-side rules of one bank; the device is asked last, by _check_device, when every argument passed these"""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name}: a tensor, got {type(t).__name__}")
+    if t.dim() != 2 or t.shape[1] == 0:
+        raise ValueError(f"{name}: a 2-D [rows, D] tensor of features, got shape {tuple(t.shape)}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name}: fp32, got {t.dtype}")
+    if t.shape[0] < min_rows:
+        raise ValueError(f"{name}: at least {min_rows} row(s), got {t.shape[0]}")
+    if t.shape[0] >= 1 << 24 or t.shape[1] > 65536:
+        raise ValueError(f"{name}: under 2^24 rows of at most 65536 features, got {tuple(t.shape)}")
+
+
+def _check_device(**named) -> None:
+    for name, t in named.items():
+        if not t.is_cuda:
+            raise ValueError(f"{name}: on a ROCm device -- the fidelity kernels have no CPU path, got a {t.device.type} tensor")
+
+
+def _check_same_d(name: str, t: torch.Tensor, first_name: str, first: torch.Tensor) -> None:
+    if t.shape[1] != first.shape[1]:
+        raise ValueError(f"{name}: D = {first.shape[1]} like {first_name}, got {t.shape[1]}")
+    if t.device != first.device:
+        raise ValueError(f"{name}: on the device of {first_name}")
+
+
+def _check_knn(knn, rows: int, bank: str) -> None:
+    if isinstance(knn, bool) or not isinstance(knn, int) or not 1 <= knn <= L.FIDELITY_LIST - 1:
+        raise ValueError(f"knn: an integer in 1 .. {L.FIDELITY_LIST - 1}, got {knn!r}")
+    if knn >= rows:
+        raise ValueError(f"knn: {knn} neighbours need more than the {rows} rows of {bank}")
+
+
+def _check_vector(name: str, v, n: int, like: torch.Tensor) -> None:
+    if not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or v.dim() != 1 or v.shape[0] != n:
+        raise ValueError(f"{name}: an fp32 [{n}] tensor, got {tuple(v.shape) if isinstance(v, torch.Tensor) else type(v).__name__}")
+    if v.device != like.device:
+        raise ValueError(f"{name}: on the device of the features")
+
+
+def _check_splits(splits) -> None:
+    if splits is not None and (isinstance(splits, bool) or not isinstance(splits, int) or not 1 <= splits <= L.FIDELITY_MAX_SPLITS):
+        raise ValueError(f"_splits: None or 1 .. {L.FIDELITY_MAX_SPLITS}, got {splits!r}")
+
+
+def _aligned(t: torch.Tensor) -> torch.Tensor:
+    """the pivot: contiguous and 16-byte aligned, so that it never decides the load path of the banks"""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _pivot(x: torch.Tensor, pivot) -> torch.Tensor:
+    return K.feat_colmean(x) if pivot is None else _aligned(pivot)
+
+
+# ------------------------------------------------------------------------------------------------ the public functions
+def pairwise_sqdist(x: torch.Tensor, y: torch.Tensor = None, *, pivot: torch.Tensor = None) -> torch.Tensor:
+    """d2 between the rows of x [N, D] and of y [M, D] -> [N, M] (y=None: x against itself, the diagonal exactly 0).  pivot=None: the column
+    mean of x.  For tests and small sets: precision_recall never forms this matrix."""
+    _check_bank("x", x)
+    if y is not None:
+        _check_bank("y", y, min_rows=1)
+        _check_same_d("y", y, "x", x)
+    if pivot is not None:
+        _check_vector("pivot", pivot, x.shape[1], x)
+    _check_device(x=x)
+    x = x.contiguous()
+    c = _pivot(x, pivot)
+    nx = K.feat_norms(x, c)
+    if y is None:
+        return K.feat_sqdist(x, nx, x, nx, c, same_bank=True)
+    y = y.contiguous()
+    return K.feat_sqdist(x, nx, y, K.feat_norms(y, c), c)
+
+
+def knn_radii(x: torch.Tensor, knn: int = 3, *, pivot: torch.Tensor = None, squared: bool = False, _splits: int = None) -> torch.Tensor:
+    """the k-NN radius of every row of x -> [N]: the distance to its knn-th neighbour (the (knn + 1)-th smallest with the row itself counted, the
+    reference's topk(knn + 1)); squared=True: r2 as the device holds it, else its square root"""
+    _check_bank("x", x)
+    _check_knn(knn, x.shape[0], "x")
+    _check_splits(_splits)
+    if pivot is not None:
+        _check_vector("pivot", pivot, x.shape[1], x)
+    _check_device(x=x)
+    x = x.contiguous()
+    c = _pivot(x, pivot)
+    r2 = K.knn_radii_sq(x, K.feat_norms(x, c), c, knn, _splits or plan_splits(x.shape[0], x.shape[0]))
+    return r2 if squared else torch.sqrt(r2)
+
+
+def manifold_hits(ref: torch.Tensor, radii_sq: torch.Tensor, query: torch.Tensor, *, pivot: torch.Tensor = None, _splits: int = None) -> torch.Tensor:
+    """is query j inside the manifold of ref: any_i [d2(ref_i, query_j) < radii_sq[i]] -> bool [M].  pivot=None: the column mean of ref."""
+    _check_bank("ref", ref)
+    _check_vector("radii_sq", radii_sq, ref.shape[0], ref)
+    _check_bank("query", query, min_rows=1)
+    _check_same_d("query", query, "ref", ref)
+    _check_splits(_splits)
+    if pivot is not None:
+        _check_vector("pivot", pivot, ref.shape[1], ref)
+    _check_device(ref=ref)
+    ref, query = ref.contiguous(), query.contiguous()
+    c = _pivot(ref, pivot)
+    hit, _ = K.manifold_hits(ref, K.feat_norms(ref, c), radii_sq.contiguous(), query, K.feat_norms(query, c), c,
+                             _splits or plan_splits(query.shape[0], ref.shape[0]))
+    return hit.bool()
+
+
+def _pr_counts(real, fake, knn, splits):
+    """the two hit counts as one int32 [2] device tensor: (fake rows inside real's manifold, real rows inside fake's)"""
+    c = K.feat_colmean(real)
+    nr, nf = K.feat_norms(real, c), K.feat_norms(fake, c)
+    n, m = real.shape[0], fake.shape[0]
+    r2_real = K.knn_radii_sq(real, nr, c, knn, splits or plan_splits(n, n))
+    r2_fake = K.knn_radii_sq(fake, nf, c, knn, splits or plan_splits(m, m))
+    _, in_real = K.manifold_hits(real, nr, r2_real, fake, nf, c, splits or plan_splits(m, n), want_hits=False)
+    _, in_fake = K.manifold_hits(fake, nf, r2_fake, real, nr, c, splits or plan_splits(n, m), want_hits=False)
+    return torch.cat([in_real, in_fake])
+
+
+def precision_recall(real: torch.Tensor, fake: torch.Tensor, knn: int = 3, *, _splits: int = None) -> dict:
+    """improved precision and recall of `fake` against `real` -> {"precision", "recall", "n_real", "n_fake", "knn"}.  Four tiled matrix-core launches (two for the radii, two for the hits),
+    no N x M matrix; the host waits exactly once, for the two counts."""
+    _check_bank("real", real)
+    _check_bank("fake", fake)
+    _check_same_d("fake", fake, "real", real)
+    _check_knn(knn, real.shape[0], "real")
+    _check_knn(knn, fake.shape[0], "fake")
+    _check_splits(_splits)
+    _check_device(real=real)
+    real, fake = real.contiguous(), fake.contiguous()
+    in_real, in_fake = _pr_counts(real, fake, knn, _splits).tolist()          # the one copy to the host
+    return {"precision": in_real / fake.shape[0], "recall": in_fake / real.shape[0], "n_real": int(real.shape[0]), "n_fake": int(fake.shape[0]), "knn": knn}
+
+
+def _moments(name: str, t: torch.Tensor):
+    x = t.to(torch.float64)
+    mu = x.mean(0)
+    xc = x - mu
+    return mu, xc.t() @ xc / (x.shape[0] - 1)
+
+
+def frechet_distance(real: torch.Tensor, fake: torch.Tensor) -> float:
+    """|mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr (S1 S2)^1/2 of the two sets' fp64 means and unbiased covariances -> python float.  Works on CPU tensors
+    too; the two symmetric eigen-decompositions run on the CPU."""
+    _check_bank("real", real)
+    _check_bank("fake", fake)
+    _check_same_d("fake", fake, "real", real)
+    mu1, s1 = _moments("real", real)
+    mu2, s2 = _moments("fake", fake)
+    s1c, s2c = s1.cpu(), s2.cpu()
+    lam, q = torch.linalg.eigh(s1c)
+    root = (q * lam.clamp_min(0).sqrt()) @ q.t()                               # S1^1/2, symmetric
+    inner = root @ s2c @ root
+    lam2 = torch.linalg.eigvalsh((inner + inner.t()) / 2)
+    cross = lam2.clamp_min(0).sqrt().sum()
+    diff = (mu1 - mu2).cpu()
+    return float(diff @ diff + torch.trace(s1c) + torch.trace(s2c) - 2 * cross)
+
+
+# ------------------------------------------------------------------------------------------------ the extractor and the meter
+class EmbedderFeatures:
+    """Features from a latent embedder the user already has (the Inception / VGG weights of the reference's extractor cannot be had): for a VAE
+    the MEAN half of the encoder's moments, for the codebook embedders encode(x), the encoder's output before quantisation -- nothing is drawn,
+    so a noise source's draw_index and torch's generator stay where they were.  pool=p: averaged over p x p cells first; then flattened.  2-D only."""
+
+    def __init__(self, embedder, pool: int = None):
+        if pool is not None and (isinstance(pool, bool) or not isinstance(pool, int) or pool < 1):
+            raise ValueError(f"pool: None or a positive integer, got {pool!r}")
+        self.embedder, self.pool = embedder, pool
+
+    @torch.no_grad()
+    def __call__(self, imgs: torch.Tensor) -> torch.Tensor:
+        if not isinstance(imgs, torch.Tensor) or imgs.dim() != 4:
+            raise ValueError(f"imgs: 2-D images [B, C, H, W], got {tuple(imgs.shape) if isinstance(imgs, torch.Tensor) else type(imgs).__name__}"
+                             + (" (3-D features are not built)" if isinstance(imgs, torch.Tensor) and imgs.dim() == 5 else ""))
+        if imgs.dtype != torch.float32:
+            raise ValueError(f"imgs: fp32, got {imgs.dtype}")
+        if not imgs.is_cuda:
+            raise ValueError(f"imgs: on a ROCm device, got a {imgs.device.type} tensor")
+        model = getattr(self.embedder, "vqvae", self.embedder)              # VQGAN / VAEGAN wrap their autoencoder
+        if hasattr(model, "_encode_z"):
+            z = model.encode(imgs)
+        else:
+            K.SyncWords.reset(imgs.device)
+            moments = K.with_fused_fallback(imgs.device, lambda: model._encode_moments(imgs))
+            z = moments[:, :moments.shape[1] // 2]
+        if self.pool is not None:
+            z = torch.nn.functional.adaptive_avg_pool2d(z, self.pool)
+        return z.reshape(z.shape[0], -1).contiguous()
+
+
+class FidelityMeter:
+    """The reference script's update / compute protocol for FID and precision / recall in one object: update(imgs, real) stores
+    features(imgs).reshape(B, -1) on the device, compute() -> {"fd", "precision", "recall", "n_real", "n_fake", "knn"}."""
+
+    def __init__(self, features, knn: int = 3):
+        if isinstance(knn, bool) or not isinstance(knn, int) or not 1 <= knn <= L.FIDELITY_LIST - 1:
+            raise ValueError(f"knn: an integer in 1 .. {L.FIDELITY_LIST - 1}, got {knn!r}")
+        self.features, self.knn = features, knn
+        self.reset()
+
+    def reset(self) -> None:
+        self._real, self._fake = [], []
+
+    @torch.no_grad()
+    def update(self, imgs: torch.Tensor, real: bool) -> None:
+        f = self.features(imgs)
+        if not isinstance(f, torch.Tensor) or f.dtype != torch.float32:
+            raise ValueError(f"features: the extractor must return an fp32 tensor, got {getattr(f, 'dtype', type(f).__name__)}")
+        (self._real if real else self._fake).append(f.reshape(f.shape[0], -1))
+
+    def banks(self):
+        """the features so far, as two device tensors [N, D] and [M, D]"""
+        if not self._real or not self._fake:
+            raise ValueError("FidelityMeter: update() with real and with generated images first")
+        return torch.cat(self._real), torch.cat(self._fake)
+
+    def compute(self) -> dict:
+        real, fake = self.banks()
+        out = precision_recall(real, fake, self.knn)
+        out["fd"] = frechet_distance(real, fake)
+        return out

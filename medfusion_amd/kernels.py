@@ -1267,6 +1267,106 @@ def ssim_pairs(xbank: torch.Tensor, ybank: torch.Tensor, d: L.MfSsimDesc, sim: O
     L.check(h.mf_ssim_finish_f32(ws.data_ptr(), _ptr(sim), _ptr(cs), _ptr(mse), stride or 1, C.byref(d), stream()), "mf_ssim_finish_f32")
 
 
+def make_fidelity_desc(N: int, M: int, D: int, knn: int = 1, splits: int = 1, same_bank: bool = False) -> L.MfFidelityDesc:
+    return L.MfFidelityDesc(N=N, M=M, D=D, knn=knn, splits=splits, same_bank=int(same_bank))
+
+
+def fidelity_ok(d: L.MfFidelityDesc) -> bool:
+    return bool(L.load().mf_fidelity_ok(C.byref(d)))
+
+
+def fidelity_workspace_bytes(d: L.MfFidelityDesc) -> int:
+    """0 for a descriptor the library refuses (host only)"""
+    return int(L.load().mf_fidelity_workspace_bytes(C.byref(d)))
+
+
+def _feature_bank(what: str, x: torch.Tensor) -> None:
+    _gpu(x)
+    if x.dtype != torch.float32 or x.dim() != 2 or not x.is_contiguous():
+        raise ValueError(f"{what}: a contiguous fp32 [rows, D] bank, got {tuple(x.shape)} {x.dtype}")
+
+
+def _feature_rows(what: str, v: torch.Tensor, n: int) -> None:
+    _gpu(v)
+    if v.dtype != torch.float32 or not v.is_contiguous() or v.numel() != n:
+        raise ValueError(f"{what}: a contiguous fp32 [{n}]")
+
+
+def feat_colmean(x: torch.Tensor) -> torch.Tensor:
+    """[N, D] -> [D]: the fp64 column means rounded to fp32, the pivot of the distances (mf_feat_colmean_f32)"""
+    _feature_bank("feat_colmean", x)
+    out = torch.empty((x.shape[1],), dtype=torch.float32, device=x.device)
+    L.check(L.load().mf_feat_colmean_f32(x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1], stream()), "mf_feat_colmean_f32")
+    return out
+
+
+def feat_norms(x: torch.Tensor, pivot: torch.Tensor) -> torch.Tensor:
+    """[N, D], [D] -> [N]: the fp64 sums of fl32(x - pivot)^2 rounded to fp32 (mf_feat_norms_f32)"""
+    _feature_bank("feat_norms", x)
+    _feature_rows("feat_norms: pivot", pivot, x.shape[1])
+    out = torch.empty((x.shape[0],), dtype=torch.float32, device=x.device)
+    L.check(L.load().mf_feat_norms_f32(x.data_ptr(), pivot.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1], stream()), "mf_feat_norms_f32")
+    return out
+
+
+def feat_sqdist(x: torch.Tensor, nx: torch.Tensor, y: torch.Tensor, ny: torch.Tensor, pivot: torch.Tensor, same_bank: bool = False) -> torch.Tensor:
+    """the [N, M] matrix of squared distances between the rows of x and of y (mf_feat_sqdist_f32); same_bank: y is x, the diagonal exactly 0"""
+    _feature_bank("feat_sqdist", x)
+    _feature_bank("feat_sqdist", y)
+    d = make_fidelity_desc(x.shape[0], y.shape[0], x.shape[1], 1, 1, same_bank)
+    if y.shape[1] != d.D or not fidelity_ok(d):
+        raise ValueError(f"feat_sqdist: banks {tuple(x.shape)} and {tuple(y.shape)}: {L.last_error() if y.shape[1] == d.D else 'D differs'}")
+    _feature_rows("feat_sqdist: nx", nx, d.N)
+    _feature_rows("feat_sqdist: ny", ny, d.M)
+    _feature_rows("feat_sqdist: pivot", pivot, d.D)
+    out = torch.empty((d.N, d.M), dtype=torch.float32, device=x.device)
+    L.check(L.load().mf_feat_sqdist_f32(x.data_ptr(), nx.data_ptr(), y.data_ptr(), ny.data_ptr(), pivot.data_ptr(), out.data_ptr(), C.byref(d), stream()),
+            "mf_feat_sqdist_f32")
+    return out
+
+
+def knn_radii_sq(x: torch.Tensor, nx: torch.Tensor, pivot: torch.Tensor, knn: int, splits: int) -> torch.Tensor:
+    """[N]: the (knn + 1)-th smallest squared distance of every row of x to the rows of x, itself included as 0 (mf_knn_partial_f32 +
+    mf_knn_finish_f32); the matrix is never written"""
+    _feature_bank("knn_radii_sq", x)
+    d = make_fidelity_desc(x.shape[0], x.shape[0], x.shape[1], knn, splits, True)
+    h = L.load()
+    need = h.mf_fidelity_workspace_bytes(C.byref(d))
+    if need == 0:
+        raise ValueError(f"knn_radii_sq: descriptor refused: {L.last_error()}")
+    _feature_rows("knn_radii_sq: nx", nx, d.N)
+    _feature_rows("knn_radii_sq: pivot", pivot, d.D)
+    ws = Workspace.get(need, x.device)
+    out = torch.empty((d.N,), dtype=torch.float32, device=x.device)
+    L.check(h.mf_knn_partial_f32(x.data_ptr(), nx.data_ptr(), pivot.data_ptr(), ws.data_ptr(), ws.numel(), C.byref(d), stream()), "mf_knn_partial_f32")
+    L.check(h.mf_knn_finish_f32(ws.data_ptr(), out.data_ptr(), C.byref(d), stream()), "mf_knn_finish_f32")
+    return out
+
+
+def manifold_hits(ref: torch.Tensor, nref: torch.Tensor, radii_sq: torch.Tensor, query: torch.Tensor, nquery: torch.Tensor, pivot: torch.Tensor,
+                  splits: int, want_hits: bool = True):
+    """-> (hit uint8 [M] or None, count int32 [1]): is query j closer to some ref row i than that row's radius, squared values, strict
+    (mf_manifold_partial_f32 + mf_manifold_finish_f32); the matrix is never written"""
+    _feature_bank("manifold_hits", ref)
+    _feature_bank("manifold_hits", query)
+    d = make_fidelity_desc(ref.shape[0], query.shape[0], ref.shape[1], 1, splits, False)
+    h = L.load()
+    need = h.mf_fidelity_workspace_bytes(C.byref(d)) if query.shape[1] == d.D else 0
+    if need == 0:
+        raise ValueError(f"manifold_hits: banks {tuple(ref.shape)} and {tuple(query.shape)}: {L.last_error() if query.shape[1] == d.D else 'D differs'}")
+    _feature_rows("manifold_hits: nref", nref, d.N)
+    _feature_rows("manifold_hits: radii_sq", radii_sq, d.N)
+    _feature_rows("manifold_hits: nquery", nquery, d.M)
+    _feature_rows("manifold_hits: pivot", pivot, d.D)
+    ws = Workspace.get(need, ref.device)
+    hit = torch.empty((d.M,), dtype=torch.uint8, device=ref.device) if want_hits else None
+    count = torch.empty((1,), dtype=torch.int32, device=ref.device)
+    L.check(h.mf_manifold_partial_f32(ref.data_ptr(), nref.data_ptr(), radii_sq.data_ptr(), query.data_ptr(), nquery.data_ptr(), pivot.data_ptr(),
+                                      ws.data_ptr(), ws.numel(), C.byref(d), stream()), "mf_manifold_partial_f32")
+    L.check(h.mf_manifold_finish_f32(ws.data_ptr(), _ptr(hit), count.data_ptr(), C.byref(d), stream()), "mf_manifold_finish_f32")
+    return hit, count
+
+
 def sched_step_blend(args: L.MfSchedArgs, blend: L.MfSchedBlend, outputs=()) -> None:
     """sched_step with the kept cells of x_t_out replaced by the known latent at the next timestep (mf_sched_step_blend_f32)"""
     _drop_outputs(outputs)

@@ -87,6 +87,13 @@ class MfSsimDesc(C.Structure):
                 + [("taps", C.c_float * SSIM_MAX_K), ("k1", C.c_float), ("k2", C.c_float), ("data_range", C.c_float)])
 
 
+FIDELITY_LIST, FIDELITY_MAX_SPLITS = 16, 16
+
+
+class MfFidelityDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("N", "M", "D", "knn", "splits", "same_bank")] + [("reserved", C.c_int32 * 2)]
+
+
 class MfGnFuse(C.Structure):
     _fields_ = [("gamma", c_fp), ("beta", c_fp), ("residual", c_fp), ("residual_pairs", c_fp), ("res_bound", c_fp), ("res_bound_slots", c_fp),
                 ("emb", c_fp), ("emb_bound", c_fp), ("out", c_fp), ("out_split", c_fp), ("out_bound", c_fp), ("rendezvous", c_fp), ("error_flag", c_fp),
@@ -196,6 +203,15 @@ _SIGS = {
     "mf_ssim_finish_f32": (_I, [c_fp, c_fp, c_fp, c_fp, _I, C.POINTER(MfSsimDesc), c_fp]),
     "mf_avgpool2_planes_f32": (_I, [c_fp, c_fp, _I64, _I, _I, c_fp]),
     "mf_rows_minmax_f32": (_I, [c_fp, c_fp, _I, _I64, c_fp]),
+    "mf_fidelity_ok": (_I, [C.POINTER(MfFidelityDesc)]),
+    "mf_fidelity_workspace_bytes": (_SZ, [C.POINTER(MfFidelityDesc)]),
+    "mf_feat_colmean_f32": (_I, [c_fp, c_fp, _I, _I, c_fp]),
+    "mf_feat_norms_f32": (_I, [c_fp, c_fp, c_fp, _I, _I, c_fp]),
+    "mf_feat_sqdist_f32": (_I, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, C.POINTER(MfFidelityDesc), c_fp]),
+    "mf_knn_partial_f32": (_I, [c_fp, c_fp, c_fp, c_fp, _SZ, C.POINTER(MfFidelityDesc), c_fp]),
+    "mf_knn_finish_f32": (_I, [c_fp, c_fp, C.POINTER(MfFidelityDesc), c_fp]),
+    "mf_manifold_partial_f32": (_I, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, _SZ, C.POINTER(MfFidelityDesc), c_fp]),
+    "mf_manifold_finish_f32": (_I, [c_fp, c_fp, c_fp, C.POINTER(MfFidelityDesc), c_fp]),
     "mf_gather_step_rows3_f32": (_I, [C.POINTER(c_fp), C.POINTER(_I64), C.POINTER(c_fp), _I, c_fp, c_fp, C.c_int32, _I, _I, c_fp]),
     "mf_broadcast_from_table_f32": (_I, [c_fp, c_fp, C.c_int32, c_fp, _I, c_fp]),
     "mf_gather_step_rows_f32": (_I, [c_fp, c_fp, c_fp, C.c_int32, _I, _I64, c_fp, _I, c_fp]),

@@ -1,0 +1,140 @@
+#!/usr/bin/env python3
+"""Fidelity of a generated set against a real one in a feature space: the Frechet distance and improved precision / recall, the figures of the
+reference's evaluate_images.py, computed on the device (medfusion_amd.fidelity).
+
+Each of --real and --fake is a folder of PNG files of one size, or a .pt / .npy file of precomputed [N, D] features (what the reference script's
+commented "Load features" block reads; a .pt holding a list of per-batch tensors is concatenated).  Folders need an extractor:
+--features embedder:CKPT[:pool] takes the encoder of a latent embedder the user already has (VAE; or VQVAE:CKPT, VQGAN:CKPT, VAEGAN:CKPT for the other
+classes), optionally average-pooled to pool x pool cells (medfusion_amd.EmbedderFeatures).  The Inception / VGG weights of the reference's own
+extractor have to be downloaded and are not built: pass feature files computed elsewhere to reproduce FID proper.
+
+  python scripts/evaluate_images.py --real real_ipr.pt --fake fake_ipr.pt --out results/metrics
+  python scripts/evaluate_images.py --real reference/ --fake generated/ --features embedder:runs/.../last_vae.ckpt:4
+
+Writes metrics_<time>.log (Samples Real / Samples Fake / FD / Precision, Recall in the reference's wording) and metrics_<time>.json next to it."""
+import argparse
+import json
+import logging
+import sys
+from datetime import datetime
+from pathlib import Path
+
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+sys.path.insert(1, str(Path(__file__).resolve().parent))      # evaluate_latent_embedder's folder reader
+
+EMBEDDERS = ("VAE", "VQVAE", "VQGAN", "VAEGAN")
+FEATURE_FILES = (".pt", ".npy")
+
+
+def is_feature_file(path) -> bool:
+    return Path(path).suffix in FEATURE_FILES
+
+
+def parse_features(spec: str):
+    """'embedder:CKPT[:pool]' (a VAE) or 'VQVAE:CKPT[:pool]' etc. -> (class name, checkpoint, pool or None)"""
+    parts = spec.split(":")
+    kind = "VAE" if parts[0] == "embedder" else parts[0]
+    if kind not in EMBEDDERS or len(parts) not in (2, 3) or not parts[1]:
+        raise SystemExit(f"--features: embedder:CKPT[:pool] (or one of {', '.join(EMBEDDERS)} in place of 'embedder'), got {spec!r}")
+    pool = None
+    if len(parts) == 3:
+        if not parts[2].isdigit() or int(parts[2]) < 1:
+            raise SystemExit(f"--features: pool is a positive integer, got {parts[2]!r}")
+        pool = int(parts[2])
+    return kind, parts[1], pool
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--real", required=True, help="folder of PNG files, or a .pt / .npy file of [N, D] features")
+    ap.add_argument("--fake", required=True, help="the generated set, likewise")
+    ap.add_argument("--features", default=None, help="embedder:CKPT[:pool] -- needed when a folder is given")
+    ap.add_argument("--knn", type=int, default=3, help="neighbours of the manifold radii (the reference's 3)")
+    ap.add_argument("--batch", type=int, default=100)
+    ap.add_argument("--max-samples", type=int, default=None, help="only the first N files / rows of each set (default: all)")
+    ap.add_argument("--out", default="results/metrics", help="folder of the log and the JSON")
+    args = ap.parse_args(argv)
+    if not 1 <= args.knn <= 15:
+        ap.error("--knn: 1 .. 15")
+    if args.batch < 1:
+        ap.error("--batch: at least 1")
+    if args.max_samples is not None and args.max_samples < 2:
+        ap.error("--max-samples: at least 2")
+    if args.features is not None:
+        parse_features(args.features)
+    elif not (is_feature_file(args.real) and is_feature_file(args.fake)):
+        ap.error("--features embedder:CKPT[:pool] is needed when --real or --fake is a folder of images")
+    return args
+
+
+def load_features(path, max_samples, expect_2d=None):
+    """a .pt / .npy file -> fp32 [N, D] host tensor (`expect_2d`: a tensor to check in place of the file's, for the refusal's test)"""
+    import numpy as np
+    import torch
+    path = Path(path)
+    if expect_2d is not None:
+        t = expect_2d
+    elif path.suffix == ".npy":
+        t = torch.from_numpy(np.load(path))
+    else:
+        t = torch.load(path, map_location="cpu")
+        if isinstance(t, (list, tuple)):
+            t = torch.cat([torch.as_tensor(c) for c in t])
+        t = torch.as_tensor(t)
+    if t.dim() != 2 or t.shape[0] < 2:
+        raise SystemExit(f"{path}: features [N, D] with at least two rows, got shape {tuple(t.shape)}")
+    return t[slice(max_samples)].to(torch.float32).contiguous()
+
+
+def folder_features(folder, extractor, channels, batch, max_samples, device):
+    import torch
+
+    from evaluate_latent_embedder import list_images, load_batch
+    files = list_images(folder, max_samples)
+    return torch.cat([extractor(load_batch(files[lo:lo + batch], channels, device)) for lo in range(0, len(files), batch)])
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    import torch
+
+    import medfusion_amd as M
+
+    device = torch.device("cuda")
+    out = Path(args.out)
+    out.mkdir(parents=True, exist_ok=True)
+    stamp = datetime.now().strftime("%Y_%m_%d_%H%M%S")
+    logger = logging.getLogger("evaluate_images")
+    logger.setLevel(logging.INFO)
+    logger.addHandler(logging.StreamHandler(sys.stdout))
+    logger.addHandler(logging.FileHandler(out / f"metrics_{stamp}.log", "w"))
+
+    extractor, channels, what = None, 3, "precomputed feature files"
+    if args.features is not None and not (is_feature_file(args.real) and is_feature_file(args.fake)):
+        from medfusion_amd.checkpoint import load_module_from_checkpoint
+        kind, ckpt, pool = parse_features(args.features)
+        model = load_module_from_checkpoint(getattr(M, kind), ckpt).to(device).eval()
+        channels = getattr(model, "in_channels", None) or 3
+        extractor = M.EmbedderFeatures(model, pool=pool)
+        what = f"{kind} encoder of {ckpt}" + (f", pooled to {pool} x {pool}" if pool else "")
+    sets = {}
+    for name, src in (("real", args.real), ("fake", args.fake)):
+        if is_feature_file(src):
+            sets[name] = load_features(src, args.max_samples).to(device)
+        else:
+            sets[name] = folder_features(src, extractor, channels, args.batch, args.max_samples, device)
+    real, fake = sets["real"], sets["fake"]
+    logger.info(f"Samples Real: {real.shape[0]}")
+    logger.info(f"Samples Fake: {fake.shape[0]}")
+    res = M.precision_recall(real, fake, args.knn)
+    res["fd"] = M.frechet_distance(real, fake)
+    logger.info("Inception features: not built (needs downloaded weights); pass precomputed feature files")
+    logger.info(f"FD (features: {what}, D = {real.shape[1]}): {res['fd']}")
+    logger.info(f"Precision: {res['precision']}, Recall {res['recall']} ")
+    res.update(real=str(args.real), fake=str(args.fake), features=args.features, feature_width=int(real.shape[1]), inception=None)
+    (out / f"metrics_{stamp}.json").write_text(json.dumps(res, indent=1) + "\n")
+    return res
+
+
+if __name__ == "__main__":
+    main()
