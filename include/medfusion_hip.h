@@ -721,6 +721,46 @@ int mf_ssim_finish_f32(const void* workspace, float* sim, float* cs, float* mse,
 int mf_avgpool2_planes_f32(const float* x, float* y, int64_t planes, int H, int W, void* stream);
 int mf_rows_minmax_f32(const float* x, float* out, int N, int64_t n, void* stream);
 
+/* The same metrics of VOLUMES (additive to ABI 250): SSIM / MS-SSIM / MSE of pairs taken from two banks of fp32 NCDHW volumes, xbank
+ * [Nx][C][D][H][W] and ybank [Ny][C][D][H][W], under the index rules of the 2-D block above (a null index array is the identity; an index outside
+ * its bank makes that pair NaN and reads nothing).
+ *   mf_ssim3d_pairs_f32   ONE scale of all P pairs in one launch.  The window is taps (x) taps (x) taps, VALID positions only: (D - k + 1) x
+ *                         (H - k + 1) x (W - k + 1) windows per channel; per window the cs and ssim of the 2-D block, c1 = (k1 L)^2, c2 = (k2 L)^2,
+ *                         L = data_range or (range_on_device = 1) max(max x - min x, max y - min y) of the pair over the whole volume, from
+ *                         minmax_x [Nx][2] / minmax_y [Ny][2] (mf_rows_minmax_f32 of the scale-0 banks).  A workgroup owns 16 x 16 in-plane
+ *                         window origins over a chunk of 16 origins in depth and marches over the planes under them: each plane is filtered
+ *                         in-plane through LDS, the depth pass keeps a ring of k partial sums per field in registers (fmaf chains in ascending
+ *                         depth).  Second moments are taken about a per-workgroup pivot (its first voxel of x, of y), so a near-constant volume
+ *                         does not cancel.  No intermediate field goes through global memory: the launch stores three fp64 partial sums per
+ *                         workgroup (ssim, cs, and with want_mse (x - y)^2 over the voxels it owns) to the workspace:
+ *                         mf_ssim3d_workspace_bytes(desc) = P C tiles 3 8 bytes, 8-byte aligned.  16-byte loads when W % 4 == 0 and both banks
+ *                         are 16-byte aligned, element by element otherwise: the same bits either way, in sim, cs and mse.
+ *   mf_ssim3d_finish_f32  adds each pair's partials in ascending (channel, tile) order in fp64 and writes sim[p * out_stride], cs[p * out_stride]
+ *                         (the means over all channels and valid positions) and mse[p] (the mean over C D H W; want_mse only) as fp32; any of
+ *                         the three may be null.
+ * No floating-point atomics: the same inputs give the same bits on every launch, and a pair's result depends neither on P nor on its place
+ * among the pairs.  mf_ssim3d_ok / mf_ssim3d_workspace_bytes are host-only (the rules: k odd in 3 .. MF_SSIM_MAX_K, D, H, W >= k,
+ * 0 < P, C <= 65535, banks non-empty, P within an un-indexed bank); every entry point refuses a bad descriptor with MF_EINVAL before any launch.
+ *   mf_avgpool2_volumes_f32  y[pl][oz][oy][ox] = the mean of the 2 x 2 x 2 block at (2 oz, 2 oy, 2 ox) on [planes][D][H][W] -> [planes][D/2][H/2][W/2]
+ *                         (an odd trailing plane, row or column is dropped).  The eight are added one after the other in (depth, row, column)
+ *                         order, ((((((v000 + v001) + v010) + v011) + v100) + v101) + v110) + v111, then multiplied by 1/8. */
+typedef struct MfSsim3dDesc {
+  int32_t P, C, D, H, W;          /* pairs, channels, extents of THIS scale */
+  int32_t Nx, Ny;                 /* rows of the two banks */
+  int32_t k;                      /* taps per axis: odd, 3 .. MF_SSIM_MAX_K */
+  int32_t indexed;                /* bit 0: ix is given, bit 1: iy is given */
+  int32_t want_mse;               /* 1: also sum (x - y)^2 (scale 0) */
+  int32_t range_on_device;        /* 1: L from minmax_x / minmax_y; 0: data_range */
+  float taps[MF_SSIM_MAX_K];      /* the 1-D window, entries past k ignored */
+  float k1, k2, data_range;
+} MfSsim3dDesc;
+int mf_ssim3d_ok(const MfSsim3dDesc* desc);
+size_t mf_ssim3d_workspace_bytes(const MfSsim3dDesc* desc);
+int mf_ssim3d_pairs_f32(const float* xbank, const float* ybank, const int32_t* ix, const int32_t* iy, const float* minmax_x, const float* minmax_y,
+                        void* workspace, size_t workspace_bytes, const MfSsim3dDesc* desc, void* stream);
+int mf_ssim3d_finish_f32(const void* workspace, float* sim, float* cs, float* mse, int out_stride, const MfSsim3dDesc* desc, void* stream);
+int mf_avgpool2_volumes_f32(const float* x, float* y, int64_t planes, int D, int H, int W, void* stream);
+
 /* Improved precision / recall of two feature sets on the device (additive to ABI 250): squared distances between the rows of two contiguous fp32
  * feature banks [rows][D] on the fp32 matrix cores, the k-NN radius of every row of a bank, and the membership of query rows in a bank's manifold
  * -- the last two WITHOUT the rows x rows matrix ever being written.  The definition: xt = fl32(x - pivot), n(x) = the fp64 sum of xt_k^2 rounded

@@ -9,6 +9,8 @@ from . import fidelity, metrics  # noqa: F401
 from .fidelity import (EmbedderFeatures, FidelityMeter, frechet_distance, knn_radii, manifold_hits, pairwise_sqdist,  # noqa: F401
                        precision_recall)
 from .metrics import ReconstructionMeter, ms_ssim, mse, pairwise_ms_ssim, ssim  # noqa: F401
+from .metrics3d import (VolumeReconstructionMeter, betas_for, min_side3d, ms_ssim3d, ms_ssim3d_and_mse, mse3d, pair_range3d,  # noqa: F401
+                        pairwise_ms_ssim3d, pyramid3d, ssim3d)
 from .noise import HostNoise, NoiseSource, PhiloxDeviceNoise, torch_cpu_noise  # noqa: F401
 from .pipeline import DiffusionPipeline, EMAModel  # noqa: F401
 from .scheduler import BasicNoiseScheduler, GaussianNoiseScheduler  # noqa: F401

@@ -1267,6 +1267,64 @@ def ssim_pairs(xbank: torch.Tensor, ybank: torch.Tensor, d: L.MfSsimDesc, sim: O
     L.check(h.mf_ssim_finish_f32(ws.data_ptr(), _ptr(sim), _ptr(cs), _ptr(mse), stride or 1, C.byref(d), stream()), "mf_ssim_finish_f32")
 
 
+def avgpool2_volumes(x: torch.Tensor) -> torch.Tensor:
+    """[N, C, D, H, W] fp32 -> [N, C, D // 2, H // 2, W // 2] by 2 x 2 x 2 means, an odd trailing plane, row or column dropped (mf_avgpool2_volumes_f32)"""
+    _gpu(x)
+    _need_f32(x)
+    x = x.contiguous()
+    n, c, d, h, w = x.shape
+    out = torch.empty((n, c, d // 2, h // 2, w // 2), dtype=torch.float32, device=x.device)
+    L.check(L.load().mf_avgpool2_volumes_f32(x.data_ptr(), out.data_ptr(), n * c, d, h, w, stream()), "mf_avgpool2_volumes_f32")
+    return out
+
+
+def make_ssim3d_desc(P: int, C_: int, D: int, H: int, W: int, Nx: int, Ny: int, taps, k1: float, k2: float, data_range: Optional[float],
+                     indexed: int = 0, want_mse: bool = False) -> L.MfSsim3dDesc:
+    """data_range=None: L of every pair from the banks' min / max rows on the device"""
+    d = L.MfSsim3dDesc(P=P, C=C_, D=D, H=H, W=W, Nx=Nx, Ny=Ny, k=len(taps), indexed=indexed, want_mse=int(want_mse),
+                       range_on_device=int(data_range is None), k1=k1, k2=k2, data_range=0.0 if data_range is None else data_range)
+    for j, v in enumerate(taps[:L.SSIM_MAX_K]):
+        d.taps[j] = v
+    return d
+
+
+def ssim3d_ok(d: L.MfSsim3dDesc) -> bool:
+    return bool(L.load().mf_ssim3d_ok(C.byref(d)))
+
+
+def ssim3d_pairs(xbank: torch.Tensor, ybank: torch.Tensor, d: L.MfSsim3dDesc, sim: Optional[torch.Tensor], cs: Optional[torch.Tensor],
+                 mse: Optional[torch.Tensor] = None, ix: Optional[torch.Tensor] = None, iy: Optional[torch.Tensor] = None,
+                 minmax_x: Optional[torch.Tensor] = None, minmax_y: Optional[torch.Tensor] = None) -> None:
+    """One scale of d.P volume pairs (mf_ssim3d_pairs_f32 + mf_ssim3d_finish_f32): pair p is xbank[ix[p]] against ybank[iy[p]] (contiguous fp32
+    [N, C, D, H, W] banks, int32 indices or None for the identity); sim / cs: fp32 views with one element per pair (any stride), mse: [P]."""
+    _gpu(xbank, ybank, sim, cs, mse, ix, iy, minmax_x, minmax_y)
+    _need_f32(xbank, ybank)
+    want = (d.C, d.D, d.H, d.W)
+    if not (xbank.is_contiguous() and ybank.is_contiguous()) or tuple(xbank.shape[1:]) != want or tuple(ybank.shape[1:]) != want \
+            or xbank.shape[0] != d.Nx or ybank.shape[0] != d.Ny:
+        raise ValueError(f"ssim3d_pairs: contiguous banks [{d.Nx}|{d.Ny}, {d.C}, {d.D}, {d.H}, {d.W}], got {tuple(xbank.shape)} and {tuple(ybank.shape)}")
+    for name, idx in (("ix", ix), ("iy", iy)):
+        if idx is not None and (idx.dtype != torch.int32 or not idx.is_contiguous() or idx.numel() != d.P):
+            raise ValueError(f"ssim3d_pairs: {name} is a contiguous int32 [{d.P}]")
+    stride = None
+    for name, o in (("sim", sim), ("cs", cs)):
+        if o is None:
+            continue
+        if o.dtype != torch.float32 or o.dim() != 1 or o.shape[0] != d.P or (stride is not None and o.stride(0) != stride and d.P > 1):
+            raise ValueError(f"ssim3d_pairs: {name} is an fp32 view of {d.P} elements, of sim's stride")
+        stride = o.stride(0) if d.P > 1 else 1
+    if mse is not None and (mse.dtype != torch.float32 or not mse.is_contiguous() or mse.numel() != d.P):
+        raise ValueError(f"ssim3d_pairs: mse is a contiguous fp32 [{d.P}]")
+    h = L.load()
+    need = h.mf_ssim3d_workspace_bytes(C.byref(d))
+    if need == 0:
+        raise ValueError(f"ssim3d_pairs: descriptor refused: {L.last_error()}")
+    ws = Workspace.get(need, xbank.device)
+    L.check(h.mf_ssim3d_pairs_f32(xbank.data_ptr(), ybank.data_ptr(), _ptr(ix), _ptr(iy), _ptr(minmax_x), _ptr(minmax_y), ws.data_ptr(), ws.numel(),
+                                  C.byref(d), stream()), "mf_ssim3d_pairs_f32")
+    L.check(h.mf_ssim3d_finish_f32(ws.data_ptr(), _ptr(sim), _ptr(cs), _ptr(mse), stride or 1, C.byref(d), stream()), "mf_ssim3d_finish_f32")
+
+
 def make_fidelity_desc(N: int, M: int, D: int, knn: int = 1, splits: int = 1, same_bank: bool = False) -> L.MfFidelityDesc:
     return L.MfFidelityDesc(N=N, M=M, D=D, knn=knn, splits=splits, same_bank=int(same_bank))
 

@@ -87,6 +87,11 @@ class MfSsimDesc(C.Structure):
                 + [("taps", C.c_float * SSIM_MAX_K), ("k1", C.c_float), ("k2", C.c_float), ("data_range", C.c_float)])
 
 
+class MfSsim3dDesc(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("P", "C", "D", "H", "W", "Nx", "Ny", "k", "indexed", "want_mse", "range_on_device")]
+                + [("taps", C.c_float * SSIM_MAX_K), ("k1", C.c_float), ("k2", C.c_float), ("data_range", C.c_float)])
+
+
 FIDELITY_LIST, FIDELITY_MAX_SPLITS = 16, 16
 
 
@@ -203,6 +208,11 @@ _SIGS = {
     "mf_ssim_finish_f32": (_I, [c_fp, c_fp, c_fp, c_fp, _I, C.POINTER(MfSsimDesc), c_fp]),
     "mf_avgpool2_planes_f32": (_I, [c_fp, c_fp, _I64, _I, _I, c_fp]),
     "mf_rows_minmax_f32": (_I, [c_fp, c_fp, _I, _I64, c_fp]),
+    "mf_ssim3d_ok": (_I, [C.POINTER(MfSsim3dDesc)]),
+    "mf_ssim3d_workspace_bytes": (_SZ, [C.POINTER(MfSsim3dDesc)]),
+    "mf_ssim3d_pairs_f32": (_I, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, _SZ, C.POINTER(MfSsim3dDesc), c_fp]),
+    "mf_ssim3d_finish_f32": (_I, [c_fp, c_fp, c_fp, c_fp, _I, C.POINTER(MfSsim3dDesc), c_fp]),
+    "mf_avgpool2_volumes_f32": (_I, [c_fp, c_fp, _I64, _I, _I, _I, c_fp]),
     "mf_fidelity_ok": (_I, [C.POINTER(MfFidelityDesc)]),
     "mf_fidelity_workspace_bytes": (_SZ, [C.POINTER(MfFidelityDesc)]),
     "mf_feat_colmean_f32": (_I, [c_fp, c_fp, _I, _I, c_fp]),
