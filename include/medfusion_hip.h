@@ -806,6 +806,37 @@ int mf_manifold_partial_f32(const float* ref, const float* nref, const float* ra
                             void* workspace, size_t workspace_bytes, const MfFidelityDesc* desc, void* stream);
 int mf_manifold_finish_f32(const void* workspace, uint8_t* hit, int32_t* count, const MfFidelityDesc* desc, void* stream);
 
+/* Nearest neighbours with indices across two banks, the exact distance of listed pairs, and the counting form of the manifold launch (additive to
+ * ABI 250; the same d2, tile and load paths as above).  MfFidelityDesc carries them: N = reference rows, M = query rows, knn = k, same_bank =
+ * the query bank IS the reference bank and every row's own entry is left out (by index: another row with the same features stays a neighbour at 0).
+ *   mf_nn_partial_f32              grid (query tiles of 128, `splits` splits of the reference rows): every query's MF_FIDELITY_LIST smallest pairs
+ *                                  (d2(query_j, ref_i), i) over the split's reference tiles in ascending LEXICOGRAPHIC order -- d2 compared as a
+ *                                  float (-0 counted as +0), then the smaller index i -- as 64-bit keys (the bits of d2 high, i low), (+inf, -1)
+ *                                  where a split holds fewer; [splits][M][MF_FIDELITY_LIST] keys to the workspace.  The indices are unique, so the
+ *                                  order is total: the result cannot depend on the tile, on `splits` or on the order of merging.
+ *   mf_nn_finish_f32               merges the splits in ascending order: d2 [M][k] (fp32, the bits of mf_feat_sqdist_f32(query, ref)) and
+ *                                  index [M][k] (int32), ascending by (d2, index).
+ *   mf_pair_sqdist_f32             out [M][k] = fl32(sum over c of fl32(query[j][c] - ref[index[j][p]][c])^2), the sum in fp64 in a fixed order, one
+ *                                  wave per pair, no pivot: equal rows give exactly 0, the relative error is at most 4 2^-24.  The index is
+ *                                  clamped into the bank before any load; a pair whose index is outside 0 .. N - 1 is stored as +inf.
+ *   mf_manifold_count_partial_f32  as mf_manifold_partial_f32, counting: part[s][j] = #{ i in split s : d2(ref_i, query_j) < radii_sq[i] } (strict),
+ *                                  int32 [splits][M] to the workspace.
+ *   mf_manifold_count_finish_f32   count[j] = the sum over the splits (int32), total = the sum of count[] (int64) by a fixed tree in one
+ *                                  workgroup; either output may be null.  Integer sums: the same bits in any order.
+ * No atomics on global memory.  mf_nn_ok / mf_nn_workspace_bytes are host-only.  The rules of these calls (MF_EINVAL before any launch):
+ * 1 <= k <= MF_FIDELITY_LIST, k <= N (k <= N - 1 with same_bank), same_bank only with M == N (and, for mf_nn_partial_f32, query == ref), 1 <= N, M
+ * < 2^24, 1 <= D <= 65536, 1 <= splits <= MF_FIDELITY_MAX_SPLITS.  The workspace (16-byte aligned) is splits M MF_FIDELITY_LIST 8 bytes; the
+ * counting launches need splits M 4 bytes of it, rounded up to 16.  mf_fidelity_workspace_bytes keeps its meaning. */
+int mf_nn_ok(const MfFidelityDesc* desc);
+size_t mf_nn_workspace_bytes(const MfFidelityDesc* desc);
+int mf_nn_partial_f32(const float* query, const float* nquery, const float* ref, const float* nref, const float* pivot, void* workspace,
+                      size_t workspace_bytes, const MfFidelityDesc* desc, void* stream);
+int mf_nn_finish_f32(const void* workspace, float* d2, int32_t* index, const MfFidelityDesc* desc, void* stream);
+int mf_pair_sqdist_f32(const float* query, const float* ref, const int32_t* index, float* out, const MfFidelityDesc* desc, void* stream);
+int mf_manifold_count_partial_f32(const float* ref, const float* nref, const float* radii_sq, const float* query, const float* nquery,
+                                  const float* pivot, void* workspace, size_t workspace_bytes, const MfFidelityDesc* desc, void* stream);
+int mf_manifold_count_finish_f32(const void* workspace, int32_t* count, int64_t* total, const MfFidelityDesc* desc, void* stream);
+
 /* ------------------------------------------------------------------ built-in launch timing (bench / roofline)
  * When enabled every launch is bracketed by hipEvents on its own stream and attributed to a kernel family.
  * NOT capture-safe; off by default. */

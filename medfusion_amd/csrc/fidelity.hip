@@ -2,6 +2,9 @@
 // the rows of two fp32 feature banks on the fp32 matrix cores, and three things done with a 128 x 128 tile of them while it is still in the
 // accumulators: stored (mf_feat_sqdist_f32), merged into every row's ascending list of its 16 smallest (the k-NN radii), or compared with the
 // rows' radii (manifold membership).  The N x M matrix is never written by the last two.
+// The neighbour family (README "Neighbours") adds two epilogues on the same tile -- every query row's 16 smallest pairs (d2, reference index) across
+// TWO banks as 64-bit keys in lexicographic order (mf_nn_partial_f32 / mf_nn_finish_f32), and the COUNT of the balls a query lies in
+// (mf_manifold_count_*) -- and pair_sqdist_kernel, the exact distance of listed pairs by differences, the sum in fp64 (mf_pair_sqdist_f32).
 //
 // The definition (README "Fidelity"): xt = fl32(x - c) with the pivot c, n(x) = the fp64 sum of xt_k^2 rounded to fp32,
 //   d2(x, y) = max(0, fl32(fl32(n(x) + n(y)) - 2 dot(xt, yt))),   dot = ONE fp32 fmaf chain over k ascending (v_mfma_f32_32x32x2_f32 is that chain).
@@ -29,7 +32,7 @@ constexpr int BUF = 2 * OPER;           // A and B of one chunk
 constexpr int STAGE = 2 * BUF;          // two chunks: 18432 floats
 constexpr int LDT = TM + 1;             // a row of the d2 tile when it goes through LDS (the k-NN selection reads it row by thread)
 constexpr int LIST = MF_FIDELITY_LIST;  // 16 values per row and split
-static_assert(TM * LDT <= STAGE && TM * (LIST + 1) <= STAGE, "the epilogues reuse the staging buffers");
+static_assert(TM * LDT <= STAGE && TM * (LIST + 1) <= STAGE && TM * (2 * LIST + 1) <= STAGE, "the epilogues reuse the staging buffers");
 constexpr int SMEM = STAGE + 2 * TM;    // + the A rows' norms and radii
 
 // One chunk of one operand, global -> registers: 128 rows x 32 k as 1024 groups of four consecutive k, four groups per thread.  The pivot is
@@ -312,6 +315,190 @@ __global__ __launch_bounds__(1024) void manifold_finish_kernel(const uint8_t* __
   if (threadIdx.x == 0 && count) *count = red[0];
 }
 
+// ---- epilogue 4: the k <= 16 nearest reference rows of every query row, values AND indices, across two banks
+// A list entry is the pair (d2, j) as one 64-bit key, the bits of d2 high and the reference index j low: d2 >= 0, so unsigned order of the keys is
+// the lexicographic order (d2 as a float, then the smaller j).  The indices are unique, so the order is total and the k smallest keys of a row are a
+// SET: no tile, split count or order of merging can change them.  -0 becomes +0 before packing (fmaxf(-0, 0) may return either; the raw bits of -0
+// would sort last).  An empty slot is (+inf, -1): above every real entry, a real +inf included.
+typedef unsigned long long nnkey;
+constexpr nnkey NN_EMPTY = 0x7F800000FFFFFFFFull;
+
+__device__ __forceinline__ nnkey nn_key(float d, int j) {
+  unsigned b = __float_as_uint(d);
+  b = b == 0x80000000u ? 0u : b;
+  return ((nnkey)b << 32) | (unsigned)j;
+}
+
+// list_insert on keys
+__device__ __forceinline__ void key_insert(nnkey (&l)[LIST], nnkey v) {
+  if (v < l[LIST - 1]) {
+#pragma unroll
+    for (int p = 0; p < LIST; ++p) {
+      const nnkey lo = l[p] < v ? l[p] : v;
+      v = l[p] < v ? v : l[p];
+      l[p] = lo;
+    }
+  }
+}
+
+// The queries are the tile's ROWS; the reference bank is walked as column tiles over split blockIdx.y, as knn_partial_kernel walks its own bank.
+// The d2 tile goes through LDS, thread (row, half) merges 64 columns into its list, the halves meet at the end.  A column past the end of the bank
+// is never inserted; with exclude_self (one bank) the entry j == i is skipped BY INDEX: another row with the same features stays a neighbour at 0.
+template <int V>
+__global__ __launch_bounds__(256, 2) void nn_partial_kernel(const float* __restrict__ qry, const float* __restrict__ nqry, const float* __restrict__ ref,
+                                                         const float* __restrict__ nref, const float* __restrict__ pivot, nnkey* __restrict__ part, int N,
+                                                         int M, int D, int S, int exclude_self) {
+  __shared__ __attribute__((aligned(16))) float smem[SMEM];
+  const int t = threadIdx.x, row = t & (TM - 1), half = t >> 7;
+  const int a0 = blockIdx.x * TM, s = blockIdx.y;
+  const int col_tiles = (N + TM - 1) / TM;
+  const int cb = (int)((long)s * col_tiles / S), ce = (int)((long)(s + 1) * col_tiles / S);
+  float* na = smem + STAGE;
+  if (t < TM) na[t] = a0 + t < M ? nqry[a0 + t] : 0.f;
+  nnkey l[LIST];
+#pragma unroll
+  for (int p = 0; p < LIST; ++p) l[p] = NN_EMPTY;
+  const int skip = exclude_self ? a0 + row : -1;
+  for (int ct = cb; ct < ce; ++ct) {
+    const int b0 = ct * TM;
+    f32x16 acc[2][2];
+    tile_dot<V>(qry, M, a0, ref, N, b0, D, pivot, smem, acc);
+    float nb[2];
+    column_norms(nref, N, b0, nb);
+    for_each_d2(acc, na, nb, [&](int il, int jl, int, float d) { smem[il * LDT + jl] = d; });
+    __syncthreads();
+    const float* mine = smem + row * LDT + half * 64;
+    const int j0 = b0 + half * 64;
+    for (int c = 0; c < 64; ++c) {
+      const int j = j0 + c;
+      if (j < N && j != skip) key_insert(l, nn_key(mine[c], j));
+    }
+  }
+  __syncthreads();
+  unsigned* words = reinterpret_cast<unsigned*>(smem);      // a row of the hand-over: 2 LIST + 1 words (low, high, low, high, ...)
+  if (half == 1) {
+#pragma unroll
+    for (int p = 0; p < LIST; ++p) {
+      words[row * (2 * LIST + 1) + 2 * p] = (unsigned)l[p];
+      words[row * (2 * LIST + 1) + 2 * p + 1] = (unsigned)(l[p] >> 32);
+    }
+  }
+  __syncthreads();
+  if (half == 0) {
+#pragma unroll
+    for (int p = 0; p < LIST; ++p)
+      key_insert(l, ((nnkey)words[row * (2 * LIST + 1) + 2 * p + 1] << 32) | words[row * (2 * LIST + 1) + 2 * p]);
+    if (a0 + row < M) {
+      nnkey* o = part + ((long)s * M + a0 + row) * LIST;
+#pragma unroll
+      for (int p = 0; p < LIST; ++p) o[p] = l[p];
+    }
+  }
+}
+
+// d2[j][0 .. k) and index[j][0 .. k) of query j: the S partial lists merged in ascending split order, one thread per query row
+__global__ __launch_bounds__(256) void nn_finish_kernel(const nnkey* __restrict__ part, float* __restrict__ d2, int* __restrict__ index, int M, int S,
+                                                        int k) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= M) return;
+  nnkey l[LIST];
+  const nnkey* q = part + (long)i * LIST;
+#pragma unroll
+  for (int p = 0; p < LIST; ++p) l[p] = q[p];
+  for (int s = 1; s < S; ++s) {
+    q = part + ((long)s * M + i) * LIST;
+    for (int p = 0; p < LIST; ++p) key_insert(l, q[p]);
+  }
+#pragma unroll
+  for (int p = 0; p < LIST; ++p)
+    if (p < k) {
+      d2[(long)i * k + p] = __uint_as_float((unsigned)(l[p] >> 32));
+      index[(long)i * k + p] = (int)(unsigned)l[p];
+    }
+}
+
+// The exact distance of listed pairs: out[j][p] = fl32(the fp64 sum over k of fl32(q_jk - r_ik)^2), i = index[j][p].  No pivot: a difference does
+// not move under a shift.  One wave per pair: lane l takes k = l, l + 64, ... ascending, then the fixed shuffle tree of norms_kernel; element loads,
+// so the result does not depend on alignment or place.  The index is clamped into the bank BEFORE the load (a -1 never reaches memory); a pair
+// whose index is outside the bank is stored as +inf.  Equal rows give exactly 0.
+__global__ __launch_bounds__(256) void pair_sqdist_kernel(const float* __restrict__ qry, const float* __restrict__ ref, const int* __restrict__ index,
+                                                          float* __restrict__ out, long pairs, int N, int D, int k) {
+  const int lane = threadIdx.x & 63;
+  const long pair = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (pair >= pairs) return;
+  const int i = index[pair];
+  const float* __restrict__ x = qry + (pair / k) * D;
+  const float* __restrict__ y = ref + (long)min(max(i, 0), N - 1) * D;
+  double s = 0.0;
+  for (int c = lane; c < D; c += 64) {
+    const float v = x[c] - y[c];
+    s += (double)v * (double)v;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if (lane == 0) out[pair] = (unsigned)i < (unsigned)N ? (float)s : INFINITY;
+}
+
+// ---- epilogue 5: the counting form of epilogue 3: count_j = #{ i : d2(R_i, Q_j) < r2_i } over the reference tiles of split blockIdx.y.
+// A lane counts over its registers, tile after tile; the four lanes that own a column (2 waves x 2 halves) are added through LDS.  Integer sums:
+// every order gives the same bits.
+template <int V>
+__global__ __launch_bounds__(256, 2) void manifold_count_partial_kernel(const float* __restrict__ ref, const float* __restrict__ nref,
+                                                                     const float* __restrict__ r2, const float* __restrict__ qry,
+                                                                     const float* __restrict__ nqry, const float* __restrict__ pivot,
+                                                                     int* __restrict__ part, int NR, int M, int D, int S) {
+  __shared__ __attribute__((aligned(16))) float smem[SMEM];
+  const int t = threadIdx.x;
+  const int b0 = blockIdx.x * TM, s = blockIdx.y;
+  const int row_tiles = (NR + TM - 1) / TM;
+  const int rb = (int)((long)s * row_tiles / S), re = (int)((long)(s + 1) * row_tiles / S);
+  float* na = smem + STAGE;
+  float* rad = na + TM;
+  float nb[2];
+  column_norms(nqry, M, b0, nb);
+  int cnt[2] = {0, 0};
+  for (int rt = rb; rt < re; ++rt) {
+    const int a0 = rt * TM;
+    if (t < TM) {
+      const bool in = a0 + t < NR;
+      na[t] = in ? nref[a0 + t] : 0.f;
+      rad[t] = in ? r2[a0 + t] : -1.f;     // d2 >= 0: a row past the end holds nobody
+    }
+    f32x16 acc[2][2];
+    tile_dot<V>(ref, NR, a0, qry, M, b0, D, pivot, smem, acc);
+    for_each_d2(acc, na, nb, [&](int il, int, int n, float d) { cnt[n] += d < rad[il] ? 1 : 0; });
+    __syncthreads();                       // na / rad are rewritten by the next tile
+  }
+  int* sums = reinterpret_cast<int*>(smem);
+  if (t < TM) sums[t] = 0;
+  __syncthreads();
+  const int lane = t & 63, wc = (t >> 6) & 1;
+#pragma unroll
+  for (int n = 0; n < 2; ++n) atomicAdd(&sums[wc * 64 + n * 32 + (lane & 31)], cnt[n]);     // an LDS integer add
+  __syncthreads();
+  if (t < TM && b0 + t < M) part[(long)s * M + b0 + t] = sums[t];
+}
+
+// count[j] = the sum of the S partial counts; total = the sum of count[] as int64, by a fixed tree.  ONE workgroup.
+__global__ __launch_bounds__(1024) void manifold_count_finish_kernel(const int* __restrict__ part, int* __restrict__ count, long long* __restrict__ total,
+                                                                     int M, int S) {
+  __shared__ long long red[1024];
+  long long c = 0;
+  for (int j = threadIdx.x; j < M; j += 1024) {
+    int f = 0;
+    for (int s = 0; s < S; ++s) f += part[(long)s * M + j];
+    if (count) count[j] = f;
+    c += f;
+  }
+  red[threadIdx.x] = c;
+  __syncthreads();
+  for (int o = 512; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && total) *total = red[0];
+}
+
 // n(x) of every row: xt = fl32(x - c), the sum of xt^2 in fp64 -- lane l of the row's wave takes k = l, l + 64, ... ascending, then a fixed shuffle
 // tree -- rounded to fp32.  Four rows per workgroup, one wave each; element loads, so a row's result does not depend on its alignment or place.
 __global__ __launch_bounds__(256) void norms_kernel(const float* __restrict__ x, const float* __restrict__ pivot, float* __restrict__ out, int N, int D) {
@@ -360,6 +547,23 @@ int fidelity_rules(const MfFidelityDesc* d, const char* what) {
   MF_REQUIRE(!d->same_bank || d->M == d->N, MF_EINVAL, "%s: same_bank with N=%d M=%d", what, d->N, d->M);
   return MF_OK;
 }
+
+// the rules of the neighbour search and the counting launches (mf_nn_*, mf_pair_sqdist_f32, mf_manifold_count_*): knn is k, 1 .. 16, and may
+// equal the reference rows (one less with same_bank, where a row is not its own neighbour)
+int nn_rules(const MfFidelityDesc* d, const char* what) {
+  MF_REQUIRE(d != nullptr, MF_EINVAL, "%s: no descriptor", what);
+  MF_REQUIRE(d->N >= 1 && d->N < (1 << 24) && d->M >= 1 && d->M < (1 << 24), MF_EINVAL, "%s: N=%d M=%d (1 .. 2^24 - 1)", what, d->N, d->M);
+  MF_REQUIRE(d->D >= 1 && d->D <= 65536, MF_EINVAL, "%s: D=%d (1 .. 65536)", what, d->D);
+  MF_REQUIRE(d->knn >= 1 && d->knn <= MF_FIDELITY_LIST, MF_EINVAL, "%s: k=%d (1 .. %d)", what, d->knn, MF_FIDELITY_LIST);
+  MF_REQUIRE(d->splits >= 1 && d->splits <= MF_FIDELITY_MAX_SPLITS, MF_EINVAL, "%s: splits=%d (1 .. %d)", what, d->splits, MF_FIDELITY_MAX_SPLITS);
+  MF_REQUIRE((d->same_bank & ~1) == 0, MF_EINVAL, "%s: same_bank is 0 or 1", what);
+  MF_REQUIRE(!d->same_bank || d->M == d->N, MF_EINVAL, "%s: same_bank with N=%d M=%d", what, d->N, d->M);
+  MF_REQUIRE(d->knn <= d->N - d->same_bank, MF_EINVAL, "%s: k=%d of %d reference rows%s", what, d->knn, d->N, d->same_bank ? " (the row itself left out)" : "");
+  return MF_OK;
+}
+
+inline size_t nn_bytes(const MfFidelityDesc* d) { return (size_t)d->splits * d->M * LIST * sizeof(nnkey); }
+inline size_t count_bytes(const MfFidelityDesc* d) { return ((size_t)d->splits * d->M * sizeof(int) + 15) & ~(size_t)15; }
 
 inline size_t knn_bytes(const MfFidelityDesc* d) { return (size_t)d->splits * d->N * LIST * sizeof(float); }
 inline size_t manifold_bytes(const MfFidelityDesc* d) { return ((size_t)d->splits * d->M + 15) & ~(size_t)15; }
@@ -470,6 +674,85 @@ int mf_manifold_finish_f32(const void* workspace, uint8_t* hit, int32_t* count, 
   ProfScope ps(MF_FAM_MISC, s, 0, (double)manifold_bytes(desc));
   MF_LAUNCH(manifold_finish_kernel, dim3(1), dim3(1024), 0, s, (const uint8_t*)workspace, hit, count, desc->M, desc->splits);
   return check_launch("manifold_finish");
+}
+
+int mf_nn_ok(const MfFidelityDesc* desc) { return nn_rules(desc, "nn_ok") == MF_OK ? 1 : 0; }
+
+size_t mf_nn_workspace_bytes(const MfFidelityDesc* desc) {
+  if (nn_rules(desc, "nn_workspace_bytes") != MF_OK) return 0;
+  return nn_bytes(desc);
+}
+
+int mf_nn_partial_f32(const float* query, const float* nquery, const float* ref, const float* nref, const float* pivot, void* workspace,
+                      size_t workspace_bytes, const MfFidelityDesc* desc, void* stream) {
+  const int rc = nn_rules(desc, "nn_partial");
+  if (rc != MF_OK) return rc;
+  MF_REQUIRE(query && nquery && ref && nref && pivot && workspace, MF_EINVAL, "nn_partial: bad args");
+  MF_REQUIRE(!desc->same_bank || (query == ref && nquery == nref), MF_EINVAL, "nn_partial: same_bank with two banks");
+  MF_REQUIRE(((uintptr_t)workspace & 15) == 0, MF_EINVAL, "nn_partial: a 16-byte aligned workspace");
+  MF_REQUIRE(workspace_bytes >= nn_bytes(desc), MF_EWORKSPACE, "nn_partial: workspace of %zu bytes, %zu needed", workspace_bytes, nn_bytes(desc));
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(MF_FAM_MISC, s, 2.0 * desc->N * desc->M * desc->D, 4.0 * ((double)desc->N + desc->M) * desc->D);
+  const dim3 grid(cdiv(desc->M, TM), desc->splits);
+  if (by16(desc->D, {query, ref, pivot}))
+    MF_LAUNCH(nn_partial_kernel<4>, grid, dim3(256), 0, s, query, nquery, ref, nref, pivot, (nnkey*)workspace, desc->N, desc->M, desc->D, desc->splits,
+              desc->same_bank);
+  else
+    MF_LAUNCH(nn_partial_kernel<1>, grid, dim3(256), 0, s, query, nquery, ref, nref, pivot, (nnkey*)workspace, desc->N, desc->M, desc->D, desc->splits,
+              desc->same_bank);
+  return check_launch("nn_partial");
+}
+
+int mf_nn_finish_f32(const void* workspace, float* d2, int32_t* index, const MfFidelityDesc* desc, void* stream) {
+  const int rc = nn_rules(desc, "nn_finish");
+  if (rc != MF_OK) return rc;
+  MF_REQUIRE(workspace && d2 && index, MF_EINVAL, "nn_finish: bad args");
+  MF_REQUIRE(((uintptr_t)workspace & 15) == 0, MF_EINVAL, "nn_finish: a 16-byte aligned workspace");
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(MF_FAM_MISC, s, 0, (double)nn_bytes(desc));
+  MF_LAUNCH(nn_finish_kernel, dim3(cdiv(desc->M, 256)), dim3(256), 0, s, (const nnkey*)workspace, d2, index, desc->M, desc->splits, desc->knn);
+  return check_launch("nn_finish");
+}
+
+int mf_pair_sqdist_f32(const float* query, const float* ref, const int32_t* index, float* out, const MfFidelityDesc* desc, void* stream) {
+  const int rc = nn_rules(desc, "pair_sqdist");
+  if (rc != MF_OK) return rc;
+  MF_REQUIRE(query && ref && index && out, MF_EINVAL, "pair_sqdist: bad args");
+  hipStream_t s = (hipStream_t)stream;
+  const long pairs = (long)desc->M * desc->knn;
+  ProfScope ps(MF_FAM_MISC, s, 3.0 * pairs * desc->D, 8.0 * pairs * desc->D);
+  MF_LAUNCH(pair_sqdist_kernel, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, s, query, ref, index, out, pairs, desc->N, desc->D, desc->knn);
+  return check_launch("pair_sqdist");
+}
+
+int mf_manifold_count_partial_f32(const float* ref, const float* nref, const float* radii_sq, const float* query, const float* nquery,
+                                  const float* pivot, void* workspace, size_t workspace_bytes, const MfFidelityDesc* desc, void* stream) {
+  const int rc = nn_rules(desc, "manifold_count_partial");
+  if (rc != MF_OK) return rc;
+  MF_REQUIRE(ref && nref && radii_sq && query && nquery && pivot && workspace, MF_EINVAL, "manifold_count_partial: bad args");
+  MF_REQUIRE(((uintptr_t)workspace & 15) == 0, MF_EINVAL, "manifold_count_partial: a 16-byte aligned workspace");
+  MF_REQUIRE(workspace_bytes >= count_bytes(desc), MF_EWORKSPACE, "manifold_count_partial: workspace of %zu bytes, %zu needed", workspace_bytes,
+             count_bytes(desc));
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(MF_FAM_MISC, s, 2.0 * desc->N * desc->M * desc->D, 4.0 * ((double)desc->N + desc->M) * desc->D);
+  const dim3 grid(cdiv(desc->M, TM), desc->splits);
+  if (by16(desc->D, {ref, query, pivot}))
+    MF_LAUNCH(manifold_count_partial_kernel<4>, grid, dim3(256), 0, s, ref, nref, radii_sq, query, nquery, pivot, (int*)workspace, desc->N, desc->M,
+              desc->D, desc->splits);
+  else
+    MF_LAUNCH(manifold_count_partial_kernel<1>, grid, dim3(256), 0, s, ref, nref, radii_sq, query, nquery, pivot, (int*)workspace, desc->N, desc->M,
+              desc->D, desc->splits);
+  return check_launch("manifold_count_partial");
+}
+
+int mf_manifold_count_finish_f32(const void* workspace, int32_t* count, int64_t* total, const MfFidelityDesc* desc, void* stream) {
+  const int rc = nn_rules(desc, "manifold_count_finish");
+  if (rc != MF_OK) return rc;
+  MF_REQUIRE(workspace && (count || total), MF_EINVAL, "manifold_count_finish: bad args");
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(MF_FAM_MISC, s, 0, (double)count_bytes(desc));
+  MF_LAUNCH(manifold_count_finish_kernel, dim3(1), dim3(1024), 0, s, (const int*)workspace, count, (long long*)total, desc->M, desc->splits);
+  return check_launch("manifold_count_finish");
 }
 
 }  // extern "C"

@@ -13,6 +13,10 @@ never materialised (the reference builds it in full and loops over the generated
 frechet_distance is host-side fp64 torch: |mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr (S1 S2)^1/2, the last term as the sum of sqrt(max(lambda_k, 0)) over
 the eigenvalues of S1^1/2 S2 S1^1/2 -- two symmetric eigen-decompositions, no general sqrtm, no complex parts.
 
+Neighbours (README "Neighbours"): nearest_neighbours -- the k <= 16 nearest rows of a second bank WITH indices, ordered by (d2, index), optionally
+with the candidates' distances recomputed exactly --, density_coverage (Naeem et al. 2020) and memorization_report (authenticity, copy ratio) on the
+same d2, tile and pivot; the matrix is not materialised by them either.
+
 Every argument error is a ValueError that names the argument, raised before anything touches the device."""
 from __future__ import annotations
 
@@ -179,6 +183,128 @@ def precision_recall(real: torch.Tensor, fake: torch.Tensor, knn: int = 3, *, _s
     return {"precision": in_real / fake.shape[0], "recall": in_fake / real.shape[0], "n_real": int(real.shape[0]), "n_fake": int(fake.shape[0]), "knn": knn}
 
 
+# ------------------------------------------------------------------------------------------------ neighbours (README "Neighbours")
+def nn_workspace_bytes(m: int, splits: int) -> int:
+    """the bytes mf_nn_workspace_bytes answers for M query rows: the partial lists of 16 eight-byte (d2, index) keys per row and split"""
+    return splits * m * L.FIDELITY_LIST * 8
+
+
+def nn_ok(n: int, m: int, d: int, k, splits: int, same_bank: bool = False) -> bool:
+    """the rules of the neighbour calls of the C ABI (mf_nn_ok), restated on the host"""
+    return (1 <= n < 1 << 24 and 1 <= m < 1 << 24 and 1 <= d <= 65536 and 1 <= k <= L.FIDELITY_LIST and 1 <= splits <= L.FIDELITY_MAX_SPLITS
+            and (not same_bank or m == n) and k <= n - int(bool(same_bank)))
+
+
+def _check_k(name: str, k, rows: int, bank: str, leave_one_out: bool = False) -> None:
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= L.FIDELITY_LIST:
+        raise ValueError(f"{name}: an integer in 1 .. {L.FIDELITY_LIST}, got {k!r}")
+    if k > rows - int(leave_one_out):
+        raise ValueError(f"{name}: {k} neighbours need {'more than' if leave_one_out else 'at least'} {k} rows of {bank}, got {rows}")
+
+
+def _search(query, nq, ref, nref, c, k, splits, exclude_self, refine):
+    """-> (d2 fp32 [M, k], index int32 [M, k]) ascending by (d2, index); refine: the k candidates' d2 recomputed exactly and each row sorted again"""
+    d2, index = K.nn_search(query, nq, ref, nref, c, k, splits or plan_splits(query.shape[0], ref.shape[0]), exclude_self)
+    if not refine:
+        return d2, index
+    d2 = K.pair_sqdist(query, ref, index)
+    if k > 1:                                                                  # by (refined value, index): a stable sort by value of the rows in index order
+        index, by_index = torch.sort(index, dim=1, stable=True)
+        d2, by_value = torch.sort(d2.gather(1, by_index), dim=1, stable=True)
+        index = index.gather(1, by_value)
+    return d2, index
+
+
+def nearest_neighbours(query: torch.Tensor, ref: torch.Tensor = None, k: int = 1, *, pivot: torch.Tensor = None, refine: bool = True,
+                       squared: bool = False, _splits: int = None):
+    """The k <= 16 nearest rows of ref [N, D] for every row of query [M, D] -> (dist fp32 [M, k], index int64 [M, k]), nearest first.  ref=None:
+    the bank against itself, every row's own entry left out (by index: a second row with the same features stays a neighbour at distance 0).
+    pivot=None: the column mean of ref (of query when ref is None).  The N x M matrix is never written; nothing synchronises.
+
+    The candidates are the k smallest pairs (d2, index) in lexicographic order -- d2 of pairwise_sqdist compared as a float, then the smaller
+    index: with unique indices a total order, so the result does not depend on the tile, the splits or the place of a row in its bank.
+    refine=False returns those, the values being the bits of pairwise_sqdist.  refine=True recomputes the k candidates' distances exactly --
+    fl32 of the fp64 sum of fl32(x_k - y_k)^2, relative error <= 4 2^-24, equal rows exactly 0 -- and sorts each row again by (refined value,
+    index).  The candidate SET is still chosen on d2, which carries the error E_ij = (D + 8) 2^-24 (n_i + n_j): a true neighbour can be missed
+    only when it lies within E of the k-th.  squared=False returns the square root."""
+    loo = ref is None
+    _check_bank("query", query, min_rows=2 if loo else 1)
+    if not loo:
+        _check_bank("ref", ref, min_rows=1)
+        _check_same_d("ref", ref, "query", query)
+    bank = query if loo else ref
+    _check_k("k", k, bank.shape[0], "query" if loo else "ref", loo)
+    _check_splits(_splits)
+    if pivot is not None:
+        _check_vector("pivot", pivot, query.shape[1], query)
+    _check_device(query=query)
+    query = query.contiguous()
+    ref = query if loo else ref.contiguous()
+    c = _pivot(ref, pivot)
+    nq = K.feat_norms(query, c)
+    nref = nq if loo else K.feat_norms(ref, c)
+    d2, index = _search(query, nq, ref, nref, c, k, _splits, loo, bool(refine))
+    return (d2 if squared else torch.sqrt(d2)), index.long()
+
+
+def density_coverage(real: torch.Tensor, fake: torch.Tensor, knn: int = 5, *, _splits: int = None) -> dict:
+    """density and coverage (Naeem et al. 2020) of `fake` against `real` -> {"density", "coverage", "n_real", "n_fake", "knn"}, on this module's d2
+    and radii with the pivot of real: r2_i = knn_radii(real, knn, squared=True), count_j = #{ i : d2(R_i, F_j) < r2_i },
+    density = sum_j count_j / (knn M), coverage = mean_i [ min_j d2(R_i, F_j) < r2_i ] (strict, squared, unrefined values).  Three matrix-core
+    launches with their finish launches -- radii, counts, the 1-NN of real in fake --, no N x M matrix; the host waits once."""
+    _check_bank("real", real)
+    _check_bank("fake", fake)
+    _check_same_d("fake", fake, "real", real)
+    _check_knn(knn, real.shape[0], "real")
+    _check_splits(_splits)
+    _check_device(real=real)
+    real, fake = real.contiguous(), fake.contiguous()
+    n, m = real.shape[0], fake.shape[0]
+    c = K.feat_colmean(real)
+    nr, nf = K.feat_norms(real, c), K.feat_norms(fake, c)
+    r2 = K.knn_radii_sq(real, nr, c, knn, _splits or plan_splits(n, n))
+    _, total = K.manifold_counts(real, nr, r2, fake, nf, c, _splits or plan_splits(m, n), want_counts=False)
+    nearest, _ = K.nn_search(real, nr, fake, nf, c, 1, _splits or plan_splits(n, m))
+    covered = (nearest[:, 0] < r2).sum()
+    total, covered = torch.stack([total[0], covered]).tolist()                # the one copy to the host
+    return {"density": total / (knn * m), "coverage": covered / n, "n_real": int(n), "n_fake": int(m), "knn": knn}
+
+
+def memorization_report(train: torch.Tensor, fake: torch.Tensor, *, neighbours: int = 10, _splits: int = None) -> dict:
+    """Is a generated row a copy of a training row?  For every row of fake [M, D], as [M] device tensors:
+      nearest_index, nearest_dist  the refined 1-NN in train (nearest_neighbours(fake, train), Euclidean distance),
+      train_gap                    the refined leave-one-out 1-NN distance of THAT training row inside train,
+      authentic                    nearest_dist > train_gap (Alaa et al. 2022),
+      copy_ratio                   nearest_dist / the mean of the refined distances to its `neighbours` nearest training rows (Carlini et al. 2023:
+                                   small means copied; 0 / 0 = NaN when all of them are exact copies),
+    and the float authenticity = mean(authentic).  Two searches, fake -> train with k = neighbours and train -> train leave-one-out with k = 1, with
+    the pivot of train; one host sync, for the float.  Features may be flattened pixels: D <= 65536, one channel of 256 x 256; otherwise pool
+    them (EmbedderFeatures(pool=...))."""
+    _check_bank("train", train)
+    _check_bank("fake", fake, min_rows=1)
+    _check_same_d("fake", fake, "train", train)
+    _check_k("neighbours", neighbours, train.shape[0], "train")
+    _check_splits(_splits)
+    _check_device(train=train)
+    train, fake = train.contiguous(), fake.contiguous()
+    c = K.feat_colmean(train)
+    nt, nf = K.feat_norms(train, c), K.feat_norms(fake, c)
+    d2, index = _search(fake, nf, train, nt, c, neighbours, _splits, False, True)
+    gap2, _ = _search(train, nt, train, nt, c, 1, _splits, True, True)
+    dist = torch.sqrt(d2)
+    nearest_index = index[:, 0].long()
+    nearest_dist = dist[:, 0].contiguous()
+    train_gap = torch.sqrt(gap2[:, 0])[nearest_index]
+    authentic = nearest_dist > train_gap
+    out = {"nearest_index": nearest_index, "nearest_dist": nearest_dist, "train_gap": train_gap, "authentic": authentic,
+           "copy_ratio": nearest_dist / dist.mean(1), "neighbours": neighbours, "n_train": int(train.shape[0]), "n_fake": int(fake.shape[0])}
+    out["authenticity"] = int(authentic.sum()) / fake.shape[0]                # the one copy to the host
+    return out
+
+
+_density_coverage, _memorization_report = density_coverage, memorization_report     # (FidelityMeter.compute has keywords of these names)
+
+
 def _moments(name: str, t: torch.Tensor):
     x = t.to(torch.float64)
     mu = x.mean(0)
@@ -238,7 +364,8 @@ class EmbedderFeatures:
 
 class FidelityMeter:
     """The reference script's update / compute protocol for FID and precision / recall in one object: update(imgs, real) stores
-    features(imgs).reshape(B, -1) on the device, compute() -> {"fd", "precision", "recall", "n_real", "n_fake", "knn"}."""
+    features(imgs).reshape(B, -1) on the device, compute() -> {"fd", "precision", "recall", "n_real", "n_fake", "knn"}; its two switches add
+    density / coverage and the memorisation report."""
 
     def __init__(self, features, knn: int = 3):
         if isinstance(knn, bool) or not isinstance(knn, int) or not 1 <= knn <= L.FIDELITY_LIST - 1:
@@ -262,8 +389,17 @@ class FidelityMeter:
             raise ValueError("FidelityMeter: update() with real and with generated images first")
         return torch.cat(self._real), torch.cat(self._fake)
 
-    def compute(self) -> dict:
+    def compute(self, density_coverage: bool = False, memorization: bool = False) -> dict:
+        """density_coverage=True adds "density" and "coverage" (density_coverage(real, fake, knn)); memorization=True adds "authenticity" and
+        "memorization", the whole memorization_report(real, fake) with the real bank as the training set (10 neighbours, or all the real rows
+        when they are fewer)"""
         real, fake = self.banks()
         out = precision_recall(real, fake, self.knn)
         out["fd"] = frechet_distance(real, fake)
+        if density_coverage:
+            dc = _density_coverage(real, fake, self.knn)
+            out["density"], out["coverage"] = dc["density"], dc["coverage"]
+        if memorization:
+            rep = _memorization_report(real, fake, neighbours=min(10, real.shape[0]))
+            out["authenticity"], out["memorization"] = rep["authenticity"], rep
         return out

@@ -1425,6 +1425,76 @@ def manifold_hits(ref: torch.Tensor, nref: torch.Tensor, radii_sq: torch.Tensor,
     return hit, count
 
 
+def nn_ok(d: L.MfFidelityDesc) -> bool:
+    return bool(L.load().mf_nn_ok(C.byref(d)))
+
+
+def nn_workspace_bytes(d: L.MfFidelityDesc) -> int:
+    """0 for a descriptor the neighbour calls refuse (host only)"""
+    return int(L.load().mf_nn_workspace_bytes(C.byref(d)))
+
+
+def nn_search(query: torch.Tensor, nquery: torch.Tensor, ref: torch.Tensor, nref: torch.Tensor, pivot: torch.Tensor, k: int, splits: int,
+              exclude_self: bool = False):
+    """-> (d2 fp32 [M, k], index int32 [M, k]): the k nearest rows of ref for every row of query, ascending by (d2, index) (mf_nn_partial_f32 +
+    mf_nn_finish_f32); exclude_self: ref IS query and a row is not its own neighbour.  The matrix is never written"""
+    _feature_bank("nn_search", query)
+    _feature_bank("nn_search", ref)
+    d = make_fidelity_desc(ref.shape[0], query.shape[0], ref.shape[1], k, splits, exclude_self)
+    h = L.load()
+    need = h.mf_nn_workspace_bytes(C.byref(d)) if query.shape[1] == d.D else 0
+    if need == 0:
+        raise ValueError(f"nn_search: banks {tuple(query.shape)} and {tuple(ref.shape)}, k={k}: {L.last_error() if query.shape[1] == d.D else 'D differs'}")
+    _feature_rows("nn_search: nquery", nquery, d.M)
+    _feature_rows("nn_search: nref", nref, d.N)
+    _feature_rows("nn_search: pivot", pivot, d.D)
+    ws = Workspace.get(need, ref.device)
+    d2 = torch.empty((d.M, k), dtype=torch.float32, device=ref.device)
+    index = torch.empty((d.M, k), dtype=torch.int32, device=ref.device)
+    L.check(h.mf_nn_partial_f32(query.data_ptr(), nquery.data_ptr(), ref.data_ptr(), nref.data_ptr(), pivot.data_ptr(), ws.data_ptr(), ws.numel(),
+                                C.byref(d), stream()), "mf_nn_partial_f32")
+    L.check(h.mf_nn_finish_f32(ws.data_ptr(), d2.data_ptr(), index.data_ptr(), C.byref(d), stream()), "mf_nn_finish_f32")
+    return d2, index
+
+
+def pair_sqdist(query: torch.Tensor, ref: torch.Tensor, index: torch.Tensor) -> torch.Tensor:
+    """[M, k]: the exact squared distance of query row j and ref row index[j, p], the sum in fp64, rounded once (mf_pair_sqdist_f32)"""
+    _feature_bank("pair_sqdist", query)
+    _feature_bank("pair_sqdist", ref)
+    _gpu(index)
+    if index.dtype != torch.int32 or index.dim() != 2 or index.shape[0] != query.shape[0] or not index.is_contiguous():
+        raise ValueError(f"pair_sqdist: a contiguous int32 [{query.shape[0]}, k] index, got {tuple(index.shape)} {index.dtype}")
+    d = make_fidelity_desc(ref.shape[0], query.shape[0], ref.shape[1], index.shape[1], 1, False)
+    if query.shape[1] != d.D or not nn_ok(d):
+        raise ValueError(f"pair_sqdist: banks {tuple(query.shape)} and {tuple(ref.shape)}, k={d.knn}: {L.last_error() if query.shape[1] == d.D else 'D differs'}")
+    out = torch.empty(tuple(index.shape), dtype=torch.float32, device=ref.device)
+    L.check(L.load().mf_pair_sqdist_f32(query.data_ptr(), ref.data_ptr(), index.data_ptr(), out.data_ptr(), C.byref(d), stream()), "mf_pair_sqdist_f32")
+    return out
+
+
+def manifold_counts(ref: torch.Tensor, nref: torch.Tensor, radii_sq: torch.Tensor, query: torch.Tensor, nquery: torch.Tensor, pivot: torch.Tensor,
+                    splits: int, want_counts: bool = True):
+    """-> (count int32 [M] or None, total int64 [1]): how many ref rows i hold query j inside their ball, d2 < radii_sq[i], strict
+    (mf_manifold_count_partial_f32 + mf_manifold_count_finish_f32); the matrix is never written"""
+    _feature_bank("manifold_counts", ref)
+    _feature_bank("manifold_counts", query)
+    d = make_fidelity_desc(ref.shape[0], query.shape[0], ref.shape[1], 1, splits, False)
+    h = L.load()
+    if query.shape[1] != d.D or not nn_ok(d):
+        raise ValueError(f"manifold_counts: banks {tuple(ref.shape)} and {tuple(query.shape)}: {L.last_error() if query.shape[1] == d.D else 'D differs'}")
+    _feature_rows("manifold_counts: nref", nref, d.N)
+    _feature_rows("manifold_counts: radii_sq", radii_sq, d.N)
+    _feature_rows("manifold_counts: nquery", nquery, d.M)
+    _feature_rows("manifold_counts: pivot", pivot, d.D)
+    ws = Workspace.get((splits * d.M * 4 + 15) // 16 * 16, ref.device)         # int32 [splits][M]: a part of mf_nn_workspace_bytes
+    count = torch.empty((d.M,), dtype=torch.int32, device=ref.device) if want_counts else None
+    total = torch.empty((1,), dtype=torch.int64, device=ref.device)
+    L.check(h.mf_manifold_count_partial_f32(ref.data_ptr(), nref.data_ptr(), radii_sq.data_ptr(), query.data_ptr(), nquery.data_ptr(), pivot.data_ptr(),
+                                            ws.data_ptr(), ws.numel(), C.byref(d), stream()), "mf_manifold_count_partial_f32")
+    L.check(h.mf_manifold_count_finish_f32(ws.data_ptr(), _ptr(count), total.data_ptr(), C.byref(d), stream()), "mf_manifold_count_finish_f32")
+    return count, total
+
+
 def sched_step_blend(args: L.MfSchedArgs, blend: L.MfSchedBlend, outputs=()) -> None:
     """sched_step with the kept cells of x_t_out replaced by the known latent at the next timestep (mf_sched_step_blend_f32)"""
     _drop_outputs(outputs)

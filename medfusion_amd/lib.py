@@ -222,6 +222,13 @@ _SIGS = {
     "mf_knn_finish_f32": (_I, [c_fp, c_fp, C.POINTER(MfFidelityDesc), c_fp]),
     "mf_manifold_partial_f32": (_I, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, _SZ, C.POINTER(MfFidelityDesc), c_fp]),
     "mf_manifold_finish_f32": (_I, [c_fp, c_fp, c_fp, C.POINTER(MfFidelityDesc), c_fp]),
+    "mf_nn_ok": (_I, [C.POINTER(MfFidelityDesc)]),
+    "mf_nn_workspace_bytes": (_SZ, [C.POINTER(MfFidelityDesc)]),
+    "mf_nn_partial_f32": (_I, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, _SZ, C.POINTER(MfFidelityDesc), c_fp]),
+    "mf_nn_finish_f32": (_I, [c_fp, c_fp, c_fp, C.POINTER(MfFidelityDesc), c_fp]),
+    "mf_pair_sqdist_f32": (_I, [c_fp, c_fp, c_fp, c_fp, C.POINTER(MfFidelityDesc), c_fp]),
+    "mf_manifold_count_partial_f32": (_I, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, _SZ, C.POINTER(MfFidelityDesc), c_fp]),
+    "mf_manifold_count_finish_f32": (_I, [c_fp, c_fp, c_fp, C.POINTER(MfFidelityDesc), c_fp]),
     "mf_gather_step_rows3_f32": (_I, [C.POINTER(c_fp), C.POINTER(_I64), C.POINTER(c_fp), _I, c_fp, c_fp, C.c_int32, _I, _I, c_fp]),
     "mf_broadcast_from_table_f32": (_I, [c_fp, c_fp, C.c_int32, c_fp, _I, c_fp]),
     "mf_gather_step_rows_f32": (_I, [c_fp, c_fp, c_fp, C.c_int32, _I, _I64, c_fp, _I, c_fp]),

@@ -11,6 +11,10 @@ extractor have to be downloaded and are not built: pass feature files computed e
   python scripts/evaluate_images.py --real real_ipr.pt --fake fake_ipr.pt --out results/metrics
   python scripts/evaluate_images.py --real reference/ --fake generated/ --features embedder:runs/.../last_vae.ckpt:4
 
+--density-coverage [KNN] adds density / coverage, --memorization [NEIGHBOURS] the authenticity and the quantiles of the copy ratio of the generated set
+against --real as the training set (medfusion_amd.density_coverage, memorization_report; scripts/nearest_train.py lists the suspicious files); both
+are off by default and leave the log and the JSON of a call without them as they were.
+
 Writes metrics_<time>.log (Samples Real / Samples Fake / FD / Precision, Recall in the reference's wording) and metrics_<time>.json next to it."""
 import argparse
 import json
@@ -53,9 +57,17 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=100)
     ap.add_argument("--max-samples", type=int, default=None, help="only the first N files / rows of each set (default: all)")
     ap.add_argument("--out", default="results/metrics", help="folder of the log and the JSON")
+    ap.add_argument("--density-coverage", type=int, nargs="?", const=5, default=None, metavar="KNN",
+                    help="also density / coverage (Naeem et al. 2020) with KNN neighbours (5 when given without a value)")
+    ap.add_argument("--memorization", type=int, nargs="?", const=10, default=None, metavar="NEIGHBOURS",
+                    help="also the authenticity and the copy ratios of the generated set against --real as the training set (10 neighbours when given without a value)")
     args = ap.parse_args(argv)
     if not 1 <= args.knn <= 15:
         ap.error("--knn: 1 .. 15")
+    if args.density_coverage is not None and not 1 <= args.density_coverage <= 15:
+        ap.error("--density-coverage: 1 .. 15")
+    if args.memorization is not None and not 1 <= args.memorization <= 16:
+        ap.error("--memorization: 1 .. 16")
     if args.batch < 1:
         ap.error("--batch: at least 1")
     if args.max_samples is not None and args.max_samples < 2:
@@ -131,6 +143,16 @@ def main(argv=None):
     logger.info("Inception features: not built (needs downloaded weights); pass precomputed feature files")
     logger.info(f"FD (features: {what}, D = {real.shape[1]}): {res['fd']}")
     logger.info(f"Precision: {res['precision']}, Recall {res['recall']} ")
+    if args.density_coverage is not None:
+        dc = M.density_coverage(real, fake, args.density_coverage)
+        res.update(density=dc["density"], coverage=dc["coverage"], density_coverage_knn=args.density_coverage)
+        logger.info(f"Density: {dc['density']}, Coverage {dc['coverage']} (knn = {args.density_coverage})")
+    if args.memorization is not None:
+        rep = M.memorization_report(real, fake, neighbours=args.memorization)
+        q = torch.quantile(rep["copy_ratio"][~torch.isnan(rep["copy_ratio"])].double(), torch.tensor([0.0, 0.01, 0.05, 0.5], dtype=torch.float64, device=device))
+        res.update(authenticity=rep["authenticity"], copy_ratio_quantiles=dict(zip(("min", "q01", "q05", "median"), q.tolist())),
+                   memorization_neighbours=args.memorization)
+        logger.info(f"Authenticity: {rep['authenticity']}, smallest copy ratio {res['copy_ratio_quantiles']['min']} (neighbours = {args.memorization})")
     res.update(real=str(args.real), fake=str(args.fake), features=args.features, feature_width=int(real.shape[1]), inception=None)
     (out / f"metrics_{stamp}.json").write_text(json.dumps(res, indent=1) + "\n")
     return res
