@@ -259,6 +259,13 @@ def _need_f32(*ts):
                                "its fp32 form was never written -- only the fp16-pair convolution and the apply pass (as a residual) can read it")
 
 
+def _f32(what: str, *ts):
+    """the entry reads and writes these by raw pointer as floats (_gpu lets the other dtypes of the library through)"""
+    for t in ts:
+        if t is not None and t.dtype != torch.float32:
+            raise RuntimeError(f"medfusion_amd: {what}: fp32 tensors only, got {t.dtype}")
+
+
 # every mirror attribute a producer may attach (_attach) and a writer must drop (drop_split).  Not mirrors, and left alone by drop_split: `_mf_ver` (the
 # stamp; _fresh clears it), `_mf_wino_site` / `_mf_wino_site_f32` (where to report a wanted transform: they describe the producer, not the values);
 # `_mf_pairs_only` is a flag of the storage that drop_split clears by its own rule.  A new mirror kind goes HERE (tests/test_host_logic_cpu.py checks)
@@ -996,13 +1003,18 @@ def gn_apply(x: torch.Tensor, stats, gamma, beta, G: int, act: int = 1, residual
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], act_in: bool = False, act_out: bool = False,
            out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
     """x [B, In] (row stride may exceed In), w [Out, In] -> [B, Out]."""
-    _gpu(x, w, bias)
+    _gpu(x, w, bias, out)
+    _need_f32(x)
+    _f32("linear", x, w, bias, out)
+    assert x.dim() == 2 and w.dim() == 2, "linear: x [B, In], w [Out, In]"
     b, inn = x.shape
     o = w.shape[0]
     assert w.shape[1] == inn and x.stride(1) == 1 and w.is_contiguous()
+    assert bias is None or (bias.shape == (o,) and bias.is_contiguous()), "linear: bias [Out], contiguous"
     if out is None:
         out = torch.empty((b, o), dtype=torch.float32, device=x.device)
     else:
+        assert out.shape == (b, o) and out.stride(1) == 1, "linear: out [B, Out] with unit column stride"
         drop_split(out)
     rc = L.load().mf_linear_f32(x.data_ptr(), x.stride(0), w.data_ptr(), _ptr(bias), out.data_ptr(), out.stride(0), b, inn, o, int(act_in),
                                 int(act_out), int(accumulate), stream())
@@ -1590,8 +1602,13 @@ def counter_add(counter: torch.Tensor, inc: int = 1) -> None:
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float) -> torch.Tensor:
     """q [B,Nq,C], k/v [B,Nk,C] -> [B,Nq,C]."""
     _gpu(q, k, v)
+    _need_f32(q, k, v)
+    _f32("attention", q, k, v)
+    assert q.dim() == 3 and k.dim() == 3 and q.is_contiguous() and k.is_contiguous() and v.is_contiguous(), "attention: contiguous q [B, Nq, C], k / v [B, Nk, C]"
     b, nq, c = q.shape
     nk = k.shape[1]
+    assert k.shape == (b, nk, c) and v.shape == k.shape, f"attention: k {tuple(k.shape)} and v {tuple(v.shape)} must both be [{b}, Nk, {c}]"
+    assert heads > 0 and c % heads == 0, f"attention: C={c} is no multiple of heads={heads}"
     out = torch.empty_like(q)
     L.check(L.load().mf_attention_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), b, heads, nq, nk, c // heads, scale, stream()),
             "mf_attention_f32")
@@ -1600,7 +1617,10 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, sca
 
 def layernorm(x: torch.Tensor, gamma, beta, eps: float = 1e-5) -> torch.Tensor:
     _gpu(x, gamma, beta)
+    _need_f32(x)
+    _f32("layernorm", x, gamma, beta)
     c = x.shape[-1]
+    assert x.is_contiguous() and gamma.shape == (c,) and beta.shape == (c,) and gamma.is_contiguous() and beta.is_contiguous(), "layernorm: contiguous x [..., C], gamma / beta [C]"
     out = torch.empty_like(x)
     L.check(L.load().mf_layernorm_f32(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), x.numel() // c, c, eps, stream()), "mf_layernorm_f32")
     return out
@@ -1608,6 +1628,9 @@ def layernorm(x: torch.Tensor, gamma, beta, eps: float = 1e-5) -> torch.Tensor:
 
 def geglu(h: torch.Tensor) -> torch.Tensor:
     _gpu(h)
+    _need_f32(h)
+    _f32("geglu", h)
+    assert h.is_contiguous() and h.shape[-1] % 2 == 0, "geglu: contiguous h [..., 2 C]"
     c = h.shape[-1] // 2
     out = torch.empty((*h.shape[:-1], c), dtype=torch.float32, device=h.device)
     L.check(L.load().mf_geglu_f32(h.data_ptr(), out.data_ptr(), h.numel() // (2 * c), c, stream()), "mf_geglu_f32")
