@@ -837,6 +837,47 @@ int mf_manifold_count_partial_f32(const float* ref, const float* nref, const flo
                                   const float* pivot, void* workspace, size_t workspace_bytes, const MfFidelityDesc* desc, void* stream);
 int mf_manifold_count_finish_f32(const void* workspace, int32_t* count, int64_t* total, const MfFidelityDesc* desc, void* stream);
 
+/* Kernel distances: the sum of a kernel k(x, y) over pairs of rows of two feature banks, for the Kernel Inception Distance and the unbiased MMD^2
+ * (additive to ABI 250; the tile and the load paths of the calls above).  The definition:
+ *   MF_KERNEL_POLY  v = fmaf(gamma, dot(x, y), coef0) in fp32, k = v, v v, (v v) v, (v v)(v v) for degree 1 .. 4, every product rounded to fp32; dot is
+ *                   the ONE fp32 fmaf chain over k ascending of the distances, run on xt = fl32(x - pivot) with a pivot of ZEROS passed by the caller
+ *                   (x - 0 is x bit for bit);
+ *   MF_KERNEL_RBF   k = expf(fl32(-gamma d2)) with d2 exactly as above (pivot, norms of mf_feat_norms_f32).
+ * The bits of k(i, j) depend on the two rows, the pivot and the scalars only -- not on the tile, the grid, N, M, the rows' places, the load path or
+ * the subset -- and k(i, j) = k(j, i).
+ *   mf_ksum_partial_f32  grid (the tiles of one subset pair, S subsets): subset s takes rows ia[s][0 .. sa) of bank a [N][D] and ib[s][0 .. sb) of bank
+ *                        b [M][D] (int32 [S][sa], [S][sb]; null: the identity 0 .. sa - 1; an index is clamped into its bank before any load).  The
+ *                        sum of k over each 128 x 128 tile of the sa x sb pairs, in fp64 in a fixed order, goes to the workspace as one double per
+ *                        tile, [S][tiles].  same_bank = 1 or 2 (a == b, na == nb, ia == ib, sb == sa): only the tiles on or above the diagonal are
+ *                        visited, an off-diagonal tile counts twice (exact in fp64); 1 leaves the pairs p == q out, by position, 2 counts them.
+ *                        na, nb: the banks' norms, needed by MF_KERNEL_RBF only (else they may be null).
+ *   mf_ksum_finish_f64   out[s] = the sum of subset s's tile sums in ascending tile order (256 consecutive runs, each ascending, added ascending).
+ *   mf_feat_kernel_f32   out [N][M] = k(x_i, y_j) as fp32, the counterpart of mf_feat_sqdist_f32 (S, sa, sb and same_bank are checked, not used).
+ * No atomics: the same bits on every launch, and a gathered subset gives the bits of the same call on its materialised rows.  mf_ksum_ok and
+ * mf_ksum_workspace_bytes are host-only.  The rules (MF_EINVAL before any launch): 1 <= N, M < 2^24, 1 <= D <= 65536, 1 <= S <= 65535, 1 <= sa <= N,
+ * 1 <= sb <= M, degree 1 .. 4 (poly), gamma finite and positive, coef0 finite, same_bank only with M == N and sb == sa, reserved 0, at most 2^31 - 1
+ * tiles per subset pair.  The workspace (16-byte aligned) is 8 bytes per visited tile -- S ceil(sa / 128) ceil(sb / 128), or S T (T + 1) / 2 with
+ * T = ceil(sa / 128) for same_bank -- rounded up to 16. */
+#define MF_KERNEL_POLY 0
+#define MF_KERNEL_RBF 1
+typedef struct MfKernelSumDesc {
+  int32_t N, M, D;                /* rows of bank a, rows of bank b, features per row */
+  int32_t S;                      /* subsets, 1 .. 65535 */
+  int32_t sa, sb;                 /* rows of a subset in bank a (<= N) and in bank b (<= M) */
+  int32_t kernel;                 /* MF_KERNEL_POLY, MF_KERNEL_RBF */
+  int32_t degree;                 /* 1 .. 4 (MF_KERNEL_POLY) */
+  float gamma, coef0;
+  int32_t same_bank;              /* 0: two banks; 1: one bank, the pairs p == q left out; 2: one bank, all pairs */
+  int32_t reserved;               /* 0 */
+} MfKernelSumDesc;
+int mf_ksum_ok(const MfKernelSumDesc* desc);
+size_t mf_ksum_workspace_bytes(const MfKernelSumDesc* desc);
+int mf_ksum_partial_f32(const float* a, const float* na, const int32_t* ia, const float* b, const float* nb, const int32_t* ib, const float* pivot,
+                        void* workspace, size_t workspace_bytes, const MfKernelSumDesc* desc, void* stream);
+int mf_ksum_finish_f64(const void* workspace, double* out, const MfKernelSumDesc* desc, void* stream);
+int mf_feat_kernel_f32(const float* x, const float* nx, const float* y, const float* ny, const float* pivot, float* out, const MfKernelSumDesc* desc,
+                       void* stream);
+
 /* ------------------------------------------------------------------ built-in launch timing (bench / roofline)
  * When enabled every launch is bracketed by hipEvents on its own stream and attributed to a kernel family.
  * NOT capture-safe; off by default. */

@@ -5,6 +5,9 @@
 // The neighbour family (README "Neighbours") adds two epilogues on the same tile -- every query row's 16 smallest pairs (d2, reference index) across
 // TWO banks as 64-bit keys in lexicographic order (mf_nn_partial_f32 / mf_nn_finish_f32), and the COUNT of the balls a query lies in
 // (mf_manifold_count_*) -- and pair_sqdist_kernel, the exact distance of listed pairs by differences, the sum in fp64 (mf_pair_sqdist_f32).
+// The kernel distances (README "Kernel distances", MfKernelSumDesc) add two more: the fp64 SUM of a kernel k(x, y) -- polynomial or Gaussian -- over
+// a tile of a pair of row subsets gathered through index lists (mf_ksum_partial_f32 / mf_ksum_finish_f64: KID and the unbiased MMD^2), and k stored
+// as a matrix (mf_feat_kernel_f32).
 //
 // The definition (README "Fidelity"): xt = fl32(x - c) with the pivot c, n(x) = the fp64 sum of xt_k^2 rounded to fp32,
 //   d2(x, y) = max(0, fl32(fl32(n(x) + n(y)) - 2 dot(xt, yt))),   dot = ONE fp32 fmaf chain over k ascending (v_mfma_f32_32x32x2_f32 is that chain).
@@ -535,6 +538,244 @@ __global__ __launch_bounds__(256) void colmean_kernel(const float* __restrict__ 
   }
 }
 
+// ---- the kernel distances (README "Kernel distances", MfKernelSumDesc): k(x, y) of the tile's dot products, summed while still in the accumulators
+// poly: v = fmaf(gamma, dot(x, y), c0), k = v, v v, (v v) v, (v v)(v v) for degree 1 .. 4, every product rounded to fp32 (the unit is built with
+// -ffp-contract=off); the callers pass a pivot of zeros: x - 0 is x bit for bit.  rbf: k = expf(fl32(-gamma d2)) with d2 exactly as for_each_d2
+// forms it.  Nothing else enters: the bits of k(i, j) depend on the two rows, the pivot and the scalars, and k(i, j) = k(j, i) (the fmaf chain's
+// products and the sum of the two norms commute).
+struct KernelParams {
+  int kind, degree;
+  float gamma, coef0;
+};
+
+__device__ __forceinline__ float kernel_value(const KernelParams& kp, float dot, float na, float nb) {
+  if (kp.kind == MF_KERNEL_RBF) {
+    const float s = na + nb;
+    const float d2 = fmaxf(s - 2.f * dot, 0.f);
+    return expf(-(kp.gamma * d2));
+  }
+  const float v = fmaf(kp.gamma, dot, kp.coef0);
+  const float v2 = v * v;
+  return kp.degree == 1 ? v : kp.degree == 2 ? v2 : kp.degree == 3 ? v2 * v : v2 * v2;
+}
+
+// k of every element this lane holds, handed to f(local row, local column, k): for_each_d2's walk, in its order
+template <class F>
+__device__ __forceinline__ void for_each_k(const f32x16 (&acc)[2][2], const KernelParams& kp, const float* __restrict__ na, const float (&nb)[2], F f) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wr = wave >> 1, wc = wave & 1, j = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int il = wr * 64 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, jl = wc * 64 + n * 32 + j;
+        f(il, jl, kernel_value(kp, acc[m][n][r], na[il], nb[n]));
+      }
+}
+
+// The four rows of one operand that thread t stages in every chunk (load_chunk's rows t / 8 + 32 q), looked up ONCE per tile: the row of the
+// subset is gathered through `list` (null: the identity), the index clamped into the bank before it is ever used as an address; a row past the
+// end of the subset takes the last one's address and is masked.
+__device__ __forceinline__ void gather_rows(const float* __restrict__ bank, int rows, const int* __restrict__ list, int count, int r0, int D, int t,
+                                            const float* (&ptr)[4], bool (&in)[4]) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int r = r0 + ((t + 256 * q) >> 3);
+    in[q] = r < count;
+    const int rc = min(r, count - 1);
+    const int g = list ? min(max(list[rc], 0), rows - 1) : rc;
+    ptr[q] = bank + (long)g * D;
+  }
+}
+
+// load_chunk through the gathered row addresses: the same values, the same masks, every load issued unconditionally from a clamped address
+template <int V>
+__device__ __forceinline__ void load_chunk_rows(const float* const (&ptr)[4], const bool (&rin)[4], int D, int k0, const float* __restrict__ pivot, int t,
+                                                f32x4 (&reg)[4]) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int k = k0 + ((t + 256 * q) & 7) * 4;
+    const float* __restrict__ p = ptr[q];
+    f32x4 v;
+    if (V == 4) {
+      const int kc = min(k, D - 4);
+      const f32x4 d = *reinterpret_cast<const f32x4*>(p + kc) - *reinterpret_cast<const f32x4*>(pivot + kc);
+      const bool in = rin[q] && k < D;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = in ? d[e] : 0.f;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int kc = min(k + e, D - 1);
+        const float d = p[kc] - pivot[kc];
+        v[e] = (rin[q] && k + e < D) ? d : 0.f;
+      }
+    }
+    reg[q] = v;
+  }
+}
+
+// tile_dot over gathered rows: the same staging, the same chain of matrix instructions over k ascending, so the same bits per pair of rows
+template <int V>
+__device__ __forceinline__ void tile_dot_rows(const float* const (&pa)[4], const bool (&ina)[4], const float* const (&pb)[4], const bool (&inb)[4], int D,
+                                              const float* __restrict__ pivot, float* __restrict__ smem, f32x16 (&acc)[2][2]) {
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wr = wave >> 1, wc = wave & 1, j = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
+  f32x4 ra[4], rb[4];
+  const int chunks = (D + BK - 1) / BK;
+  load_chunk_rows<V>(pa, ina, D, 0, pivot, t, ra);
+  load_chunk_rows<V>(pb, inb, D, 0, pivot, t, rb);
+  __syncthreads();
+  store_chunk(smem, t, ra);
+  store_chunk(smem + OPER, t, rb);
+  __syncthreads();
+  for (int c = 0; c < chunks; ++c) {
+    const float* cur = smem + (c & 1) * BUF;
+    const bool more = c + 1 < chunks;
+    if (more) {
+      load_chunk_rows<V>(pa, ina, D, (c + 1) * BK, pivot, t, ra);
+      load_chunk_rows<V>(pb, inb, D, (c + 1) * BK, pivot, t, rb);
+    }
+    const float* As = cur + (wr * 64 + j) * LDK + 4 * h;
+    const float* Bs = cur + OPER + (wc * 64 + j) * LDK + 4 * h;
+#pragma unroll
+    for (int g = 0; g < BK / 8; ++g) {
+      const f32x4 fa0 = *reinterpret_cast<const f32x4*>(As + 8 * g), fa1 = *reinterpret_cast<const f32x4*>(As + 32 * LDK + 8 * g);
+      const f32x4 fb0 = *reinterpret_cast<const f32x4*>(Bs + 8 * g), fb1 = *reinterpret_cast<const f32x4*>(Bs + 32 * LDK + 8 * g);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa0[s], fb0[s], acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa0[s], fb1[s], acc[0][1], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa1[s], fb0[s], acc[1][0], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa1[s], fb1[s], acc[1][1], 0, 0, 0);
+      }
+    }
+    if (more) {
+      float* nxt = smem + ((c + 1) & 1) * BUF;
+      store_chunk(nxt, t, ra);
+      store_chunk(nxt + OPER, t, rb);
+    }
+    __syncthreads();
+  }
+}
+
+// tile `id` of the upper triangle of T x T tiles, rows ascending and ct >= rt ascending inside a row: row rt starts at rt T - rt (rt - 1) / 2
+__device__ __forceinline__ void triangle_tile(long id, int T, int& rt, int& ct) {
+  const double b = 2.0 * T + 1.0;
+  long r = (long)((b - sqrt(b * b - 8.0 * (double)id)) * 0.5);
+  r = r < 0 ? 0 : (r > T - 1 ? T - 1 : r);
+  while (r > 0 && r * T - r * (r - 1) / 2 > id) --r;
+  while (r + 1 < T && (r + 1) * T - (r + 1) * r / 2 <= id) ++r;
+  rt = (int)r;
+  ct = (int)(r + id - (r * T - r * (r - 1) / 2));
+}
+
+// ---- epilogue 6: the SUM of k over one tile of one subset pair.  grid (the tiles of a subset pair, S subsets); subset s takes rows ia[s][0 .. sa) of
+// bank A and ib[s][0 .. sb) of bank B (null: the identity).  Every lane adds its 64 elements in fp64 in for_each_k's order, the 256 lanes meet in
+// LDS by a fixed tree, one fp64 per tile goes to part[s][tile].  same (A is B, ia is ib): only the tiles with ct >= rt exist, an off-diagonal tile
+// is stored twice over (exact in fp64), and with same == 1 a diagonal tile leaves p == q out, by position.  No atomics; the order is fixed in
+// subset-local coordinates, so a gathered subset gives the bits of the same call on its materialised rows.
+template <int V>
+__global__ __launch_bounds__(256, 2) void ksum_partial_kernel(const float* __restrict__ a, const float* __restrict__ na, const int* __restrict__ ia,
+                                                           const float* __restrict__ b, const float* __restrict__ nb, const int* __restrict__ ib,
+                                                           const float* __restrict__ pivot, double* __restrict__ part, int N, int M, int D, int sa, int sb,
+                                                           int col_tiles, int tiles, int same, KernelParams kp) {
+  __shared__ __attribute__((aligned(16))) float smem[SMEM];
+  const int t = threadIdx.x, s = blockIdx.y;
+  int rt, ct;
+  if (same) {
+    triangle_tile(blockIdx.x, col_tiles, rt, ct);
+  } else {
+    rt = blockIdx.x / col_tiles;
+    ct = blockIdx.x - rt * col_tiles;
+  }
+  const int a0 = rt * TM, b0 = ct * TM;
+  const int* la = ia ? ia + (long)s * sa : nullptr;
+  const int* lb = ib ? ib + (long)s * sb : nullptr;
+  float* nas = smem + STAGE;
+  if (t < TM) {
+    const int r = min(a0 + t, sa - 1);
+    const int g = la ? min(max(la[r], 0), N - 1) : r;
+    nas[t] = (na && a0 + t < sa) ? na[g] : 0.f;
+  }
+  float nbs[2];
+  {
+    const int lane = t & 63, wc = (t >> 6) & 1;
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+      const int c = b0 + wc * 64 + n * 32 + (lane & 31), r = min(c, sb - 1);
+      const int g = lb ? min(max(lb[r], 0), M - 1) : r;
+      nbs[n] = (nb && c < sb) ? nb[g] : 0.f;
+    }
+  }
+  const float* pa[4];
+  const float* pb[4];
+  bool ina[4], inb[4];
+  gather_rows(a, N, la, sa, a0, D, t, pa, ina);
+  gather_rows(b, M, lb, sb, b0, D, t, pb, inb);
+  f32x16 acc[2][2];
+  tile_dot_rows<V>(pa, ina, pb, inb, D, pivot, smem, acc);
+  const bool skip_diag = same == 1 && rt == ct;
+  double sum = 0.0;
+  for_each_k(acc, kp, nas, nbs, [&](int il, int jl, float k) {
+    const bool in = a0 + il < sa && b0 + jl < sb && !(skip_diag && il == jl);
+    sum += in ? (double)k : 0.0;
+  });
+  double* red = reinterpret_cast<double*>(smem);      // (tile_dot_rows left with a barrier: the staging buffers are free)
+  red[t] = sum;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (t < o) red[t] += red[t + o];
+    __syncthreads();
+  }
+  if (t == 0) part[(long)s * tiles + blockIdx.x] = (same && rt != ct) ? 2.0 * red[0] : red[0];
+}
+
+// out[s] = the sum of subset s's tile sums: thread t of the subset's workgroup adds the t-th run of ceil(tiles / 256) consecutive tiles in ascending
+// order, thread 0 then adds the 256 runs in ascending order -- ascending tile order throughout, the same bits on every launch
+__global__ __launch_bounds__(256) void ksum_finish_kernel(const double* __restrict__ part, double* __restrict__ out, int tiles) {
+  __shared__ double red[256];
+  const int t = threadIdx.x, run = (tiles + 255) / 256;
+  const double* p = part + (long)blockIdx.x * tiles;
+  double s = 0.0;
+  const long lo = (long)t * run, hi = min(lo + run, (long)tiles);
+  for (long i = lo; i < hi; ++i) s += p[i];
+  red[t] = s;
+  __syncthreads();
+  if (t == 0) {
+    double a = red[0];
+    for (int i = 1; i < 256; ++i) a += red[i];
+    out[blockIdx.x] = a;
+  }
+}
+
+// ---- epilogue 7: the matrix of k itself, sqdist_kernel's counterpart (tile_dot as it is; for tests and kernel_matrix())
+template <int V>
+__global__ __launch_bounds__(256) void kernel_matrix_kernel(const float* __restrict__ x, const float* __restrict__ nx, const float* __restrict__ y,
+                                                            const float* __restrict__ ny, const float* __restrict__ pivot, float* __restrict__ out, int N,
+                                                            int M, int D, int col_tiles, KernelParams kp) {
+  __shared__ __attribute__((aligned(16))) float smem[SMEM];
+  const int t = threadIdx.x;
+  const int rt = blockIdx.x / col_tiles, ct = blockIdx.x - rt * col_tiles;
+  const int a0 = rt * TM, b0 = ct * TM;
+  float* na = smem + STAGE;
+  if (t < TM) na[t] = (nx && a0 + t < N) ? nx[a0 + t] : 0.f;
+  f32x16 acc[2][2];
+  tile_dot<V>(x, N, a0, y, M, b0, D, pivot, smem, acc);
+  float nb[2] = {0.f, 0.f};
+  if (ny) column_norms(ny, M, b0, nb);
+  for_each_k(acc, kp, na, nb, [&](int il, int jl, float k) {
+    const int ig = a0 + il, jg = b0 + jl;
+    if (ig < N && jg < M) out[(long)ig * M + jg] = k;
+  });
+}
+
 // the descriptor's rules, on the host, before any launch
 int fidelity_rules(const MfFidelityDesc* d, const char* what) {
   MF_REQUIRE(d != nullptr, MF_EINVAL, "%s: no descriptor", what);
@@ -573,6 +814,32 @@ inline bool by16(int D, std::initializer_list<const void*> ptrs) {
   for (const void* p : ptrs) bits |= (uintptr_t)p;
   return D % 4 == 0 && (bits & 15) == 0;
 }
+
+// the rules of the kernel sums and the kernel matrix (mf_ksum_*, mf_feat_kernel_f32)
+int ksum_rules(const MfKernelSumDesc* d, const char* what) {
+  MF_REQUIRE(d != nullptr, MF_EINVAL, "%s: no descriptor", what);
+  MF_REQUIRE(d->N >= 1 && d->N < (1 << 24) && d->M >= 1 && d->M < (1 << 24), MF_EINVAL, "%s: N=%d M=%d (1 .. 2^24 - 1)", what, d->N, d->M);
+  MF_REQUIRE(d->D >= 1 && d->D <= 65536, MF_EINVAL, "%s: D=%d (1 .. 65536)", what, d->D);
+  MF_REQUIRE(d->S >= 1 && d->S <= 65535, MF_EINVAL, "%s: S=%d (1 .. 65535)", what, d->S);
+  MF_REQUIRE(d->sa >= 1 && d->sa <= d->N && d->sb >= 1 && d->sb <= d->M, MF_EINVAL, "%s: sa=%d sb=%d (1 .. N=%d, 1 .. M=%d)", what, d->sa, d->sb, d->N,
+             d->M);
+  MF_REQUIRE(d->kernel == MF_KERNEL_POLY || d->kernel == MF_KERNEL_RBF, MF_EINVAL, "%s: kernel=%d (0 poly, 1 rbf)", what, d->kernel);
+  MF_REQUIRE(d->kernel != MF_KERNEL_POLY || (d->degree >= 1 && d->degree <= 4), MF_EINVAL, "%s: degree=%d (1 .. 4)", what, d->degree);
+  MF_REQUIRE(std::isfinite(d->gamma) && d->gamma > 0.f, MF_EINVAL, "%s: gamma=%g (finite, positive)", what, (double)d->gamma);
+  MF_REQUIRE(std::isfinite(d->coef0), MF_EINVAL, "%s: coef0=%g (finite)", what, (double)d->coef0);
+  MF_REQUIRE(d->same_bank >= 0 && d->same_bank <= 2, MF_EINVAL, "%s: same_bank is 0, 1 or 2", what);
+  MF_REQUIRE(!d->same_bank || (d->M == d->N && d->sb == d->sa), MF_EINVAL, "%s: same_bank with N=%d M=%d sa=%d sb=%d", what, d->N, d->M, d->sa, d->sb);
+  MF_REQUIRE(d->reserved == 0, MF_EINVAL, "%s: reserved is 0", what);
+  return MF_OK;
+}
+
+// the tiles one subset pair visits: all of them, or the upper triangle with its diagonal
+inline long ksum_tiles(const MfKernelSumDesc* d) {
+  const long ta = cdiv(d->sa, TM), tb = cdiv(d->sb, TM);
+  return d->same_bank ? ta * (ta + 1) / 2 : ta * tb;
+}
+inline size_t ksum_bytes(const MfKernelSumDesc* d) { return ((size_t)d->S * (size_t)ksum_tiles(d) * sizeof(double) + 15) & ~(size_t)15; }
+inline KernelParams kernel_params(const MfKernelSumDesc* d) { return KernelParams{d->kernel, d->degree, d->gamma, d->coef0}; }
 
 }  // namespace
 
@@ -753,6 +1020,73 @@ int mf_manifold_count_finish_f32(const void* workspace, int32_t* count, int64_t*
   ProfScope ps(MF_FAM_MISC, s, 0, (double)count_bytes(desc));
   MF_LAUNCH(manifold_count_finish_kernel, dim3(1), dim3(1024), 0, s, (const int*)workspace, count, (long long*)total, desc->M, desc->splits);
   return check_launch("manifold_count_finish");
+}
+
+int mf_ksum_ok(const MfKernelSumDesc* desc) { return ksum_rules(desc, "ksum_ok") == MF_OK && ksum_tiles(desc) <= 0x7fffffffL ? 1 : 0; }
+
+size_t mf_ksum_workspace_bytes(const MfKernelSumDesc* desc) {
+  if (ksum_rules(desc, "ksum_workspace_bytes") != MF_OK) return 0;
+  if (ksum_tiles(desc) > 0x7fffffffL) {
+    set_error("ksum_workspace_bytes: %ld tiles per subset pair", ksum_tiles(desc));
+    return 0;
+  }
+  return ksum_bytes(desc);
+}
+
+int mf_ksum_partial_f32(const float* a, const float* na, const int32_t* ia, const float* b, const float* nb, const int32_t* ib, const float* pivot,
+                        void* workspace, size_t workspace_bytes, const MfKernelSumDesc* desc, void* stream) {
+  const int rc = ksum_rules(desc, "ksum_partial");
+  if (rc != MF_OK) return rc;
+  MF_REQUIRE(a && b && pivot && workspace, MF_EINVAL, "ksum_partial: bad args");
+  MF_REQUIRE(desc->kernel != MF_KERNEL_RBF || (na && nb), MF_EINVAL, "ksum_partial: the rbf kernel needs the norms of both banks");
+  MF_REQUIRE(!desc->same_bank || (a == b && na == nb && ia == ib), MF_EINVAL, "ksum_partial: same_bank with two banks or two index lists");
+  MF_REQUIRE(((uintptr_t)workspace & 15) == 0, MF_EINVAL, "ksum_partial: a 16-byte aligned workspace");
+  const long tiles = ksum_tiles(desc);
+  MF_REQUIRE(tiles <= 0x7fffffffL, MF_EINVAL, "ksum_partial: %ld tiles per subset pair", tiles);
+  MF_REQUIRE(workspace_bytes >= ksum_bytes(desc), MF_EWORKSPACE, "ksum_partial: workspace of %zu bytes, %zu needed", workspace_bytes, ksum_bytes(desc));
+  hipStream_t s = (hipStream_t)stream;
+  const double pairs = (double)desc->S * desc->sa * desc->sb * (desc->same_bank ? 0.5 : 1.0);
+  ProfScope ps(MF_FAM_MISC, s, 2.0 * pairs * desc->D, 4.0 * desc->S * ((double)desc->sa + desc->sb) * desc->D);
+  const dim3 grid((unsigned)tiles, (unsigned)desc->S);
+  const int col_tiles = cdiv(desc->sb, TM);
+  if (by16(desc->D, {a, b, pivot}))
+    MF_LAUNCH(ksum_partial_kernel<4>, grid, dim3(256), 0, s, a, na, ia, b, nb, ib, pivot, (double*)workspace, desc->N, desc->M, desc->D, desc->sa, desc->sb,
+              col_tiles, (int)tiles, desc->same_bank, kernel_params(desc));
+  else
+    MF_LAUNCH(ksum_partial_kernel<1>, grid, dim3(256), 0, s, a, na, ia, b, nb, ib, pivot, (double*)workspace, desc->N, desc->M, desc->D, desc->sa, desc->sb,
+              col_tiles, (int)tiles, desc->same_bank, kernel_params(desc));
+  return check_launch("ksum_partial");
+}
+
+int mf_ksum_finish_f64(const void* workspace, double* out, const MfKernelSumDesc* desc, void* stream) {
+  const int rc = ksum_rules(desc, "ksum_finish");
+  if (rc != MF_OK) return rc;
+  MF_REQUIRE(workspace && out, MF_EINVAL, "ksum_finish: bad args");
+  MF_REQUIRE(((uintptr_t)workspace & 15) == 0, MF_EINVAL, "ksum_finish: a 16-byte aligned workspace");
+  const long tiles = ksum_tiles(desc);
+  MF_REQUIRE(tiles <= 0x7fffffffL, MF_EINVAL, "ksum_finish: %ld tiles per subset pair", tiles);
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(MF_FAM_MISC, s, 0, (double)ksum_bytes(desc));
+  MF_LAUNCH(ksum_finish_kernel, dim3((unsigned)desc->S), dim3(256), 0, s, (const double*)workspace, out, (int)tiles);
+  return check_launch("ksum_finish");
+}
+
+int mf_feat_kernel_f32(const float* x, const float* nx, const float* y, const float* ny, const float* pivot, float* out, const MfKernelSumDesc* desc,
+                       void* stream) {
+  const int rc = ksum_rules(desc, "feat_kernel");
+  if (rc != MF_OK) return rc;
+  MF_REQUIRE(x && y && pivot && out, MF_EINVAL, "feat_kernel: bad args");
+  MF_REQUIRE(desc->kernel != MF_KERNEL_RBF || (nx && ny), MF_EINVAL, "feat_kernel: the rbf kernel needs the norms of both banks");
+  const long row_tiles = cdiv(desc->N, TM), col_tiles = cdiv(desc->M, TM);
+  MF_REQUIRE(row_tiles * col_tiles <= 0x7fffffffL, MF_EINVAL, "feat_kernel: %ld x %ld tiles", row_tiles, col_tiles);
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(MF_FAM_MISC, s, 2.0 * desc->N * desc->M * desc->D, 4.0 * ((double)desc->N * desc->M + ((double)desc->N + desc->M) * desc->D));
+  const dim3 grid((unsigned)(row_tiles * col_tiles));
+  if (by16(desc->D, {x, y, pivot}))
+    MF_LAUNCH(kernel_matrix_kernel<4>, grid, dim3(256), 0, s, x, nx, y, ny, pivot, out, desc->N, desc->M, desc->D, (int)col_tiles, kernel_params(desc));
+  else
+    MF_LAUNCH(kernel_matrix_kernel<1>, grid, dim3(256), 0, s, x, nx, y, ny, pivot, out, desc->N, desc->M, desc->D, (int)col_tiles, kernel_params(desc));
+  return check_launch("feat_kernel");
 }
 
 }  // extern "C"

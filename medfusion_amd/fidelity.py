@@ -17,6 +17,10 @@ Neighbours (README "Neighbours"): nearest_neighbours -- the k <= 16 nearest rows
 with the candidates' distances recomputed exactly --, density_coverage (Naeem et al. 2020) and memorization_report (authenticity, copy ratio) on the
 same d2, tile and pivot; the matrix is not materialised by them either.
 
+Kernel distances (README "Kernel distances"): kid -- the Kernel Inception Distance, the mean and spread of the unbiased MMD^2 under
+(gamma x.y + coef0)^degree over seeded subsets --, mmd2 of the full sets under a polynomial or Gaussian kernel, and kernel_matrix; the sums of k are
+taken on the same tile while it is in the accumulators (MfKernelSumDesc), all subsets of a term in one launch, the matrix never materialised.
+
 Every argument error is a ValueError that names the argument, raised before anything touches the device."""
 from __future__ import annotations
 
@@ -302,7 +306,179 @@ def memorization_report(train: torch.Tensor, fake: torch.Tensor, *, neighbours: 
     return out
 
 
+# ------------------------------------------------------------------------------------------------ kernel distances (README "Kernel distances")
+KERNELS = {"poly": L.KERNEL_POLY, "rbf": L.KERNEL_RBF}
+
+
+def _kernel_scalars(kernel, degree, gamma, coef0, D: int):
+    """the host-side rules of the kernel's name and scalars -> (kind, degree, gamma, coef0), gamma and coef0 as the fp32 numbers the device uses;
+    gamma=None: 1 / D taken in fp64 and rounded to fp32 (poly only)"""
+    import ctypes
+    import math
+    if kernel not in KERNELS:
+        raise ValueError(f"kernel: 'poly' or 'rbf', got {kernel!r}")
+    if isinstance(degree, bool) or not isinstance(degree, int) or not 1 <= degree <= 4:
+        raise ValueError(f"degree: an integer in 1 .. 4, got {degree!r}")
+    if gamma is None:
+        if kernel == "rbf":
+            raise ValueError("gamma: the rbf kernel needs a bandwidth (no median heuristic is built), got None")
+        gamma = 1.0 / D
+    if isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not math.isfinite(gamma) or gamma <= 0:
+        raise ValueError(f"gamma: None or a finite positive number, got {gamma!r}")
+    if isinstance(coef0, bool) or not isinstance(coef0, (int, float)) or not math.isfinite(coef0):
+        raise ValueError(f"coef0: a finite number, got {coef0!r}")
+    gamma32, coef32 = ctypes.c_float(gamma).value, ctypes.c_float(coef0).value
+    if not math.isfinite(gamma32) or gamma32 <= 0 or not math.isfinite(coef32):
+        raise ValueError(f"gamma: {gamma!r} and coef0: {coef0!r} must be finite (and gamma positive) as fp32 numbers")
+    return KERNELS[kernel], degree, gamma32, coef32
+
+
+def _kernel_operands(kind: int, first: torch.Tensor, pivot, *banks):
+    """-> (pivot, the norms of every bank or None): poly runs on the rows themselves -- a pivot of zeros --, rbf on the column mean of `first`"""
+    if kind == L.KERNEL_POLY:
+        c = torch.zeros((first.shape[1],), dtype=torch.float32, device=first.device) if pivot is None else _aligned(pivot)
+        return c, [None] * len(banks)
+    c = _pivot(first, pivot)
+    return c, [K.feat_norms(b, c) for b in banks]
+
+
+def kernel_matrix(x: torch.Tensor, y: torch.Tensor = None, *, kernel: str = "poly", degree: int = 3, gamma: float = None, coef0: float = 1.0,
+                  pivot: torch.Tensor = None) -> torch.Tensor:
+    """k between the rows of x [N, D] and of y [M, D] -> fp32 [N, M] (y=None: x against itself; the diagonal is k(x_i, x_i), not special).
+    kernel="poly": (gamma x.y + coef0)^degree, gamma=None: 1 / D; kernel="rbf": exp(-gamma d2) on pairwise_sqdist's d2.  pivot=None: zeros for
+    poly (the rows as they are), the column mean of x for rbf.  For tests and small sets: mmd2 and kid never form this matrix."""
+    _check_bank("x", x, min_rows=1)
+    if y is not None:
+        _check_bank("y", y, min_rows=1)
+        _check_same_d("y", y, "x", x)
+    kind, degree, gamma, coef0 = _kernel_scalars(kernel, degree, gamma, coef0, x.shape[1])
+    if pivot is not None:
+        _check_vector("pivot", pivot, x.shape[1], x)
+    _check_device(x=x)
+    x = x.contiguous()
+    y = x if y is None else y.contiguous()
+    c, (nx, ny) = _kernel_operands(kind, x, pivot, x, y)
+    return K.feat_kernel(x, nx, y, ny, c, K.make_ksum_desc(x.shape[0], y.shape[0], x.shape[1], kernel=kind, degree=degree, gamma=gamma, coef0=coef0))
+
+
+def _ksum_tiles(sa: int, sb: int, same: bool) -> int:
+    ta, tb = -(-sa // TILE), -(-sb // TILE)
+    return ta * (ta + 1) // 2 if same else ta * tb
+
+
+def ksum_workspace_bytes(subsets: int, sa: int, sb: int, same_bank: bool = False) -> int:
+    """the bytes mf_ksum_workspace_bytes answers: 8 per visited tile, rounded up to 16"""
+    return (subsets * _ksum_tiles(sa, sb, same_bank) * 8 + 15) // 16 * 16
+
+
+def _three_sums(real, fake, ia, ib, S, sa, sb, scalars, diag: bool):
+    """-> fp64 [S] x 3: the sums of k over (X, X), (Y, Y) and (X, Y) of every subset; diag: the p == q pairs of the same-bank terms are counted"""
+    kind, degree, gamma, coef0 = scalars
+    n, m, D = real.shape[0], fake.shape[0], real.shape[1]
+    c, (nr, nf) = _kernel_operands(kind, real, None, real, fake)
+    kw = dict(kernel=kind, degree=degree, gamma=gamma, coef0=coef0)
+    same = 2 if diag else 1
+    sxx = K.kernel_sums(real, nr, ia, real, nr, ia, c, K.make_ksum_desc(n, n, D, S, sa, sa, same_bank=same, **kw))
+    syy = K.kernel_sums(fake, nf, ib, fake, nf, ib, c, K.make_ksum_desc(m, m, D, S, sb, sb, same_bank=same, **kw))
+    sxy = K.kernel_sums(real, nr, ia, fake, nf, ib, c, K.make_ksum_desc(n, m, D, S, sa, sb, **kw))
+    return sxx, syy, sxy
+
+
+def _mmd2_of_sums(sxx, syy, sxy, n: int, m: int, unbiased: bool):
+    """-> (MMD^2, the three means), fp64 on the device: sxx / (n (n - 1)) + syy / (m (m - 1)) - 2 sxy / (n m); biased: n^2 and m^2"""
+    kxx = sxx / float(n * (n - 1) if unbiased else n * n)
+    kyy = syy / float(m * (m - 1) if unbiased else m * m)
+    kxy = sxy / float(n * m)
+    return kxx + kyy - 2.0 * kxy, (kxx, kyy, kxy)
+
+
+def _check_mmd_banks(real, fake) -> None:
+    _check_bank("real", real)
+    _check_bank("fake", fake)
+    _check_same_d("fake", fake, "real", real)
+
+
+def mmd2(real: torch.Tensor, fake: torch.Tensor, *, kernel: str = "poly", degree: int = 3, gamma: float = None, coef0: float = 1.0,
+         unbiased: bool = True, return_terms: bool = False):
+    """The squared maximum mean discrepancy of the FULL sets under k -> a 0-dim fp64 device tensor:
+    sum_{i != j} k(x_i, x_j) / (n (n - 1)) + sum_{i != j} k(y_i, y_j) / (m (m - 1)) - 2 sum_{ij} k(x_i, y_j) / (n m); unbiased=False counts the
+    diagonals and divides by n^2 and m^2.  Three matrix-core launches with their finish launches -- the same-bank terms over the upper triangle of
+    tiles only --, every sum in fp64 in a fixed order, no N x M matrix, and nothing waits for the device.  return_terms=True: (mmd2, {"kxx", "kyy",
+    "kxy"}), the three means as 0-dim fp64 device tensors.  rbf: the pivot is the column mean of real, gamma must be given."""
+    _check_mmd_banks(real, fake)
+    scalars = _kernel_scalars(kernel, degree, gamma, coef0, real.shape[1])
+    _check_device(real=real)
+    real, fake = real.contiguous(), fake.contiguous()
+    n, m = real.shape[0], fake.shape[0]
+    sums = _three_sums(real, fake, None, None, 1, n, m, scalars, diag=not unbiased)
+    value, (kxx, kyy, kxy) = _mmd2_of_sums(*sums, n, m, bool(unbiased))
+    value = value[0]
+    return (value, {"kxx": kxx[0], "kyy": kyy[0], "kxy": kxy[0]}) if return_terms else value
+
+
+def draw_subsets(n: int, m: int, subsets: int, subset_size: int, seed: int = 0):
+    """The index lists of kid -> (ia, ib), int32 [subsets, subset_size] on the host.  ONE host generator of its own, seeded with `seed`; for subset
+    s = 0, 1, ... in turn it draws torch.randperm(n), whose first subset_size entries are row s of ia, then torch.randperm(m), whose first
+    subset_size entries are row s of ib.  No repeats inside a subset; the subsets are independent draws; torch's global generator is not touched."""
+    g = torch.Generator().manual_seed(seed)
+    ia, ib = [], []
+    for _ in range(subsets):
+        ia.append(torch.randperm(n, generator=g)[:subset_size])
+        ib.append(torch.randperm(m, generator=g)[:subset_size])
+    return torch.stack(ia).to(torch.int32), torch.stack(ib).to(torch.int32)
+
+
+def _check_kid(subsets, subset_size, seed, n: int, m: int) -> None:
+    if subsets is not None and (isinstance(subsets, bool) or not isinstance(subsets, int) or not 1 <= subsets <= L.KSUM_MAX_SUBSETS):
+        raise ValueError(f"subsets: None or an integer in 1 .. {L.KSUM_MAX_SUBSETS}, got {subsets!r}")
+    if subsets is not None and (isinstance(subset_size, bool) or not isinstance(subset_size, int) or not 2 <= subset_size <= min(n, m)):
+        raise ValueError(f"subset_size: an integer in 2 .. min(N, M) = {min(n, m)}, got {subset_size!r}")
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < (1 << 62):
+        raise ValueError(f"seed: a non-negative integer, got {seed!r}")
+
+
+def kid(real: torch.Tensor, fake: torch.Tensor, *, subsets: int = 100, subset_size: int = 1000, degree: int = 3, gamma: float = None, coef0: float = 1.0,
+        seed: int = 0) -> dict:
+    """The Kernel Inception Distance (Binkowski et al. 2018) -> {"kid_mean", "kid_std", "subsets", "subset_size", "n_real", "n_fake"}: the mean and
+    the POPULATION standard deviation of the unbiased MMD^2 under (gamma x.y + coef0)^degree over `subsets` pairs of subsets of `subset_size` rows
+    (draw_subsets: a seeded host randperm per subset and bank).  The index lists go to the device once as int32 [S, s]; every term of ALL subsets is
+    one gathering launch plus its finish launch; the host waits once, for the two figures.  subsets=None: mmd2 of the full sets, the estimate of
+    the lowest variance, with kid_std None.  Nothing is drawn from torch's global generator or from a noise source."""
+    _check_mmd_banks(real, fake)
+    scalars = _kernel_scalars("poly", degree, gamma, coef0, real.shape[1])
+    n, m = real.shape[0], fake.shape[0]
+    _check_kid(subsets, subset_size, seed, n, m)
+    _check_device(real=real)
+    real, fake = real.contiguous(), fake.contiguous()
+    if subsets is None:
+        value = _mmd2_of_sums(*_three_sums(real, fake, None, None, 1, n, m, scalars, diag=False), n, m, True)[0]
+        return {"kid_mean": value.tolist()[0], "kid_std": None, "subsets": None, "subset_size": None, "n_real": int(n), "n_fake": int(m)}
+    ia, ib = (t.to(real.device) for t in draw_subsets(n, m, subsets, subset_size, seed))
+    values = _mmd2_of_sums(*_three_sums(real, fake, ia, ib, subsets, subset_size, subset_size, scalars, diag=False), subset_size, subset_size, True)[0]
+    mean, std = torch.stack([values.mean(), values.std(unbiased=False)]).tolist()           # the one copy to the host
+    return {"kid_mean": mean, "kid_std": std, "subsets": subsets, "subset_size": subset_size, "n_real": int(n), "n_fake": int(m)}
+
+
+def plan_kid(n: int, m: int, subsets, subset_size) -> dict:
+    """What kid(real [n, D], fake [m, D], subsets, subset_size) launches -> {"launches", "workgroups", "workspace_bytes", "index_bytes",
+    "matrix_bytes"}, host only.  workgroups: one per visited tile -- the same-bank terms visit the T (T + 1) / 2 tiles on or above the diagonal --;
+    workspace_bytes: the largest of the three launches' (they share it); matrix_bytes: the three fp32 matrices of the materialised form."""
+    for name, v in (("n", n), ("m", m)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 2 <= v < 1 << 24:
+            raise ValueError(f"{name}: an integer in 2 .. 2^24 - 1, got {v!r}")
+    _check_kid(subsets, subset_size, 0, n, m)
+    S, sa, sb = (1, n, m) if subsets is None else (subsets, subset_size, subset_size)
+    terms = (("real x real", sa, sa, True), ("fake x fake", sb, sb, True), ("real x fake", sa, sb, False))
+    groups = {name: S * _ksum_tiles(a, b, same) for name, a, b, same in terms}
+    launches = [f"ksum_partial_kernel: {name}, {S} subset(s) of {a} x {b} rows, {groups[name]} workgroups" + (" (upper triangle of tiles)" if same else "")
+                for name, a, b, same in terms]
+    return {"launches": [x for line in launches for x in (line, "ksum_finish_kernel: " + line.split(":")[1].split(",")[0].strip())],
+            "workgroups": groups, "workspace_bytes": max(ksum_workspace_bytes(S, a, b, same) for _, a, b, same in terms),
+            "index_bytes": 0 if subsets is None else 2 * S * subset_size * 4, "matrix_bytes": S * (sa * sa + sb * sb + sa * sb) * 4}
+
+
 _density_coverage, _memorization_report = density_coverage, memorization_report     # (FidelityMeter.compute has keywords of these names)
+_kid = kid
 
 
 def _moments(name: str, t: torch.Tensor):
@@ -367,10 +543,14 @@ class FidelityMeter:
     features(imgs).reshape(B, -1) on the device, compute() -> {"fd", "precision", "recall", "n_real", "n_fake", "knn"}; its two switches add
     density / coverage and the memorisation report."""
 
-    def __init__(self, features, knn: int = 3):
+    def __init__(self, features, knn: int = 3, kid=False):
+        """kid=True, or a dict of kid()'s keyword arguments, makes compute() add "kid_mean", "kid_std", "kid_subsets" and "kid_subset_size" (the
+        switch lives here: compute()'s own keywords are those of the neighbour figures); without it compute() returns what it always did"""
         if isinstance(knn, bool) or not isinstance(knn, int) or not 1 <= knn <= L.FIDELITY_LIST - 1:
             raise ValueError(f"knn: an integer in 1 .. {L.FIDELITY_LIST - 1}, got {knn!r}")
-        self.features, self.knn = features, knn
+        if not isinstance(kid, (bool, dict)) or (isinstance(kid, dict) and not set(kid) <= {"subsets", "subset_size", "degree", "gamma", "coef0", "seed"}):
+            raise ValueError(f"kid: False, True or a dict of kid()'s keyword arguments, got {kid!r}")
+        self.features, self.knn, self.kid = features, knn, kid
         self.reset()
 
     def reset(self) -> None:
@@ -402,4 +582,10 @@ class FidelityMeter:
         if memorization:
             rep = _memorization_report(real, fake, neighbours=min(10, real.shape[0]))
             out["authenticity"], out["memorization"] = rep["authenticity"], rep
+        if self.kid:
+            kw = dict(self.kid) if isinstance(self.kid, dict) else {}
+            if kw.get("subsets", 100) is not None:
+                kw.setdefault("subset_size", min(1000, real.shape[0], fake.shape[0]))      # (kid()'s 1000 where the banks hold that many rows)
+            res = _kid(real, fake, **kw)
+            out.update(kid_mean=res["kid_mean"], kid_std=res["kid_std"], kid_subsets=res["subsets"], kid_subset_size=res["subset_size"])
         return out

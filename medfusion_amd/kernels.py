@@ -1507,6 +1507,71 @@ def manifold_counts(ref: torch.Tensor, nref: torch.Tensor, radii_sq: torch.Tenso
     return count, total
 
 
+def make_ksum_desc(N: int, M: int, D: int, S: int = 1, sa: int = None, sb: int = None, kernel: int = L.KERNEL_POLY, degree: int = 3,
+                   gamma: float = 1.0, coef0: float = 1.0, same_bank: int = 0) -> L.MfKernelSumDesc:
+    """sa / sb None: the whole bank"""
+    return L.MfKernelSumDesc(N=N, M=M, D=D, S=S, sa=N if sa is None else sa, sb=M if sb is None else sb, kernel=kernel, degree=degree, gamma=gamma,
+                             coef0=coef0, same_bank=int(same_bank), reserved=0)
+
+
+def ksum_ok(d: L.MfKernelSumDesc) -> bool:
+    return bool(L.load().mf_ksum_ok(C.byref(d)))
+
+
+def ksum_workspace_bytes(d: L.MfKernelSumDesc) -> int:
+    """0 for a descriptor the kernel sums refuse (host only)"""
+    return int(L.load().mf_ksum_workspace_bytes(C.byref(d)))
+
+
+def _index_lists(what: str, index, S: int, rows: int, like: torch.Tensor) -> None:
+    if index is None:
+        return
+    _gpu(index)
+    if index.dtype != torch.int32 or not index.is_contiguous() or tuple(index.shape) != (S, rows) or index.device != like.device:
+        raise ValueError(f"{what}: a contiguous int32 [{S}, {rows}] index list on the banks' device, got {tuple(index.shape)} {index.dtype}")
+
+
+def kernel_sums(a: torch.Tensor, na, ia, b: torch.Tensor, nb, ib, pivot: torch.Tensor, d: L.MfKernelSumDesc) -> torch.Tensor:
+    """fp64 [S]: the sum of k over the pairs of rows ia[s] of a and ib[s] of b (mf_ksum_partial_f32 + mf_ksum_finish_f64); na / nb: the norms, for
+    the rbf kernel; ia / ib None: the identity.  The matrix is never written"""
+    _feature_bank("kernel_sums", a)
+    _feature_bank("kernel_sums", b)
+    h = L.load()
+    fits = a.shape == (d.N, d.D) and b.shape == (d.M, d.D)
+    need = h.mf_ksum_workspace_bytes(C.byref(d)) if fits else 0
+    if need == 0:
+        raise ValueError(f"kernel_sums: banks {tuple(a.shape)} and {tuple(b.shape)}: {L.last_error() if fits else 'not the shapes of the descriptor'}")
+    _feature_rows("kernel_sums: pivot", pivot, d.D)
+    if d.kernel == L.KERNEL_RBF:
+        _feature_rows("kernel_sums: na", na, d.N)
+        _feature_rows("kernel_sums: nb", nb, d.M)
+    _index_lists("kernel_sums: ia", ia, d.S, d.sa, a)
+    _index_lists("kernel_sums: ib", ib, d.S, d.sb, b)
+    ws = Workspace.get(need, a.device)
+    out = torch.empty((d.S,), dtype=torch.float64, device=a.device)
+    L.check(h.mf_ksum_partial_f32(a.data_ptr(), _ptr(na), _ptr(ia), b.data_ptr(), _ptr(nb), _ptr(ib), pivot.data_ptr(), ws.data_ptr(), ws.numel(),
+                                  C.byref(d), stream()), "mf_ksum_partial_f32")
+    L.check(h.mf_ksum_finish_f64(ws.data_ptr(), out.data_ptr(), C.byref(d), stream()), "mf_ksum_finish_f64")
+    return out
+
+
+def feat_kernel(x: torch.Tensor, nx, y: torch.Tensor, ny, pivot: torch.Tensor, d: L.MfKernelSumDesc) -> torch.Tensor:
+    """the [N, M] matrix of k between the rows of x and of y (mf_feat_kernel_f32); nx / ny: the norms, for the rbf kernel"""
+    _feature_bank("feat_kernel", x)
+    _feature_bank("feat_kernel", y)
+    fits = x.shape == (d.N, d.D) and y.shape == (d.M, d.D)
+    if not fits or not ksum_ok(d):
+        raise ValueError(f"feat_kernel: banks {tuple(x.shape)} and {tuple(y.shape)}: {L.last_error() if fits else 'not the shapes of the descriptor'}")
+    _feature_rows("feat_kernel: pivot", pivot, d.D)
+    if d.kernel == L.KERNEL_RBF:
+        _feature_rows("feat_kernel: nx", nx, d.N)
+        _feature_rows("feat_kernel: ny", ny, d.M)
+    out = torch.empty((d.N, d.M), dtype=torch.float32, device=x.device)
+    L.check(L.load().mf_feat_kernel_f32(x.data_ptr(), _ptr(nx), y.data_ptr(), _ptr(ny), pivot.data_ptr(), out.data_ptr(), C.byref(d), stream()),
+            "mf_feat_kernel_f32")
+    return out
+
+
 def sched_step_blend(args: L.MfSchedArgs, blend: L.MfSchedBlend, outputs=()) -> None:
     """sched_step with the kept cells of x_t_out replaced by the known latent at the next timestep (mf_sched_step_blend_f32)"""
     _drop_outputs(outputs)

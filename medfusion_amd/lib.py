@@ -99,6 +99,15 @@ class MfFidelityDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("N", "M", "D", "knn", "splits", "same_bank")] + [("reserved", C.c_int32 * 2)]
 
 
+KERNEL_POLY, KERNEL_RBF = 0, 1
+KSUM_MAX_SUBSETS = 65535
+
+
+class MfKernelSumDesc(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("N", "M", "D", "S", "sa", "sb", "kernel", "degree")] + [("gamma", C.c_float), ("coef0", C.c_float)]
+                + [("same_bank", C.c_int32), ("reserved", C.c_int32)])
+
+
 class MfGnFuse(C.Structure):
     _fields_ = [("gamma", c_fp), ("beta", c_fp), ("residual", c_fp), ("residual_pairs", c_fp), ("res_bound", c_fp), ("res_bound_slots", c_fp),
                 ("emb", c_fp), ("emb_bound", c_fp), ("out", c_fp), ("out_split", c_fp), ("out_bound", c_fp), ("rendezvous", c_fp), ("error_flag", c_fp),
@@ -229,6 +238,11 @@ _SIGS = {
     "mf_pair_sqdist_f32": (_I, [c_fp, c_fp, c_fp, c_fp, C.POINTER(MfFidelityDesc), c_fp]),
     "mf_manifold_count_partial_f32": (_I, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, _SZ, C.POINTER(MfFidelityDesc), c_fp]),
     "mf_manifold_count_finish_f32": (_I, [c_fp, c_fp, c_fp, C.POINTER(MfFidelityDesc), c_fp]),
+    "mf_ksum_ok": (_I, [C.POINTER(MfKernelSumDesc)]),
+    "mf_ksum_workspace_bytes": (_SZ, [C.POINTER(MfKernelSumDesc)]),
+    "mf_ksum_partial_f32": (_I, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, _SZ, C.POINTER(MfKernelSumDesc), c_fp]),
+    "mf_ksum_finish_f64": (_I, [c_fp, c_fp, C.POINTER(MfKernelSumDesc), c_fp]),
+    "mf_feat_kernel_f32": (_I, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, C.POINTER(MfKernelSumDesc), c_fp]),
     "mf_gather_step_rows3_f32": (_I, [C.POINTER(c_fp), C.POINTER(_I64), C.POINTER(c_fp), _I, c_fp, c_fp, C.c_int32, _I, _I, c_fp]),
     "mf_broadcast_from_table_f32": (_I, [c_fp, c_fp, C.c_int32, c_fp, _I, c_fp]),
     "mf_gather_step_rows_f32": (_I, [c_fp, c_fp, c_fp, C.c_int32, _I, _I64, c_fp, _I, c_fp]),

@@ -13,7 +13,9 @@ extractor have to be downloaded and are not built: pass feature files computed e
 
 --density-coverage [KNN] adds density / coverage, --memorization [NEIGHBOURS] the authenticity and the quantiles of the copy ratio of the generated set
 against --real as the training set (medfusion_amd.density_coverage, memorization_report; scripts/nearest_train.py lists the suspicious files); both
-are off by default and leave the log and the JSON of a call without them as they were.
+are off by default and leave the log and the JSON of a call without them as they were.  --kid [SUBSETS] adds the Kernel Inception Distance
+(medfusion_amd.kid: the mean and the spread of the unbiased MMD^2 over SUBSETS pairs of subsets of --kid-subset-size rows; smaller sets fall back
+to subsets of min(N, M) rows, with a notice in the log); off by default likewise.
 
 Writes metrics_<time>.log (Samples Real / Samples Fake / FD / Precision, Recall in the reference's wording) and metrics_<time>.json next to it."""
 import argparse
@@ -61,7 +63,14 @@ def parse_args(argv=None):
                     help="also density / coverage (Naeem et al. 2020) with KNN neighbours (5 when given without a value)")
     ap.add_argument("--memorization", type=int, nargs="?", const=10, default=None, metavar="NEIGHBOURS",
                     help="also the authenticity and the copy ratios of the generated set against --real as the training set (10 neighbours when given without a value)")
+    ap.add_argument("--kid", type=int, nargs="?", const=100, default=None, metavar="SUBSETS",
+                    help="also the Kernel Inception Distance over SUBSETS pairs of subsets (100 when given without a value)")
+    ap.add_argument("--kid-subset-size", type=int, default=1000, metavar="ROWS", help="rows of a subset of --kid (at most the rows of the smaller set)")
     args = ap.parse_args(argv)
+    if args.kid is not None and not 1 <= args.kid <= 65535:
+        ap.error("--kid: 1 .. 65535 subsets")
+    if args.kid_subset_size < 2:
+        ap.error("--kid-subset-size: at least 2")
     if not 1 <= args.knn <= 15:
         ap.error("--knn: 1 .. 15")
     if args.density_coverage is not None and not 1 <= args.density_coverage <= 15:
@@ -119,7 +128,7 @@ def main(argv=None):
     logger = logging.getLogger("evaluate_images")
     logger.setLevel(logging.INFO)
     logger.addHandler(logging.StreamHandler(sys.stdout))
-    logger.addHandler(logging.FileHandler(out / f"metrics_{stamp}.log", "w"))
+    logger.addHandler(logging.FileHandler(out / f"metrics_{stamp}.log", "w", encoding="utf-8"))      # (the KID line is not ASCII; the others are)
 
     extractor, channels, what = None, 3, "precomputed feature files"
     if args.features is not None and not (is_feature_file(args.real) and is_feature_file(args.fake)):
@@ -153,6 +162,14 @@ def main(argv=None):
         res.update(authenticity=rep["authenticity"], copy_ratio_quantiles=dict(zip(("min", "q01", "q05", "median"), q.tolist())),
                    memorization_neighbours=args.memorization)
         logger.info(f"Authenticity: {rep['authenticity']}, smallest copy ratio {res['copy_ratio_quantiles']['min']} (neighbours = {args.memorization})")
+    if args.kid is not None:
+        size = args.kid_subset_size
+        if size > min(real.shape[0], fake.shape[0]):
+            size = min(real.shape[0], fake.shape[0])
+            logger.info(f"KID: the sets hold fewer than {args.kid_subset_size} rows, subsets of {size} rows instead")
+        kid = M.kid(real, fake, subsets=args.kid, subset_size=size)
+        res.update(kid_mean=kid["kid_mean"], kid_std=kid["kid_std"], kid_subsets=args.kid, kid_subset_size=size)
+        logger.info(f"KID: {kid['kid_mean']} ± {kid['kid_std']} ({args.kid} × {size})")
     res.update(real=str(args.real), fake=str(args.fake), features=args.features, feature_width=int(real.shape[1]), inception=None)
     (out / f"metrics_{stamp}.json").write_text(json.dumps(res, indent=1) + "\n")
     return res
