@@ -14,6 +14,10 @@
 // There is no split-K: the bits of d2(i, j) depend on the two rows and the pivot only -- not on the tile, the grid, N, M or the rows' places in
 // their banks -- and d2(i, j) of (x, y) is d2(j, i) of (y, x).  No atomics anywhere: the column / row splits of the k-NN and manifold launches write
 // partial lists / flags to a workspace, and a finish launch merges them in ascending split order.
+// The structure: ONE K loop (tile_dot, with its loader load_chunk) over two row sources -- BankRows, a contiguous bank, or GatheredRows, a subset
+// through an index list; ONE walk of the accumulators (for_each_acc) that hands every dot product to an epilogue, which makes it a value (d2_value,
+// kernel_value); ONE body per kind of epilogue -- store_tile (d2 or k as a matrix), list_partial (the ValueList or the KeyList policy),
+// manifold_partial (flags or counts) -- under kernels that keep their own names.  Every promise above is a statement about that one loop.
 // Built without packed fp32 like metrics.hip (medfusion_amd/build.py): the staging subtraction and the epilogues are plain fp32 VALU work.
 #include "common.h"
 
@@ -35,22 +39,62 @@ constexpr int BUF = 2 * OPER;           // A and B of one chunk
 constexpr int STAGE = 2 * BUF;          // two chunks: 18432 floats
 constexpr int LDT = TM + 1;             // a row of the d2 tile when it goes through LDS (the k-NN selection reads it row by thread)
 constexpr int LIST = MF_FIDELITY_LIST;  // 16 values per row and split
-static_assert(TM * LDT <= STAGE && TM * (LIST + 1) <= STAGE && TM * (2 * LIST + 1) <= STAGE, "the epilogues reuse the staging buffers");
 constexpr int SMEM = STAGE + 2 * TM;    // + the A rows' norms and radii
+
+// A row source tells thread t where the q-th of the four rows it stages in every chunk (the tile's row (t + 256 q) / 8) lies, and whether that row
+// exists: the address is always inside the bank, a row past the end takes the last one's address and is masked.
+// BankRows: rows r0 .. of a contiguous bank.  The address is formed from the three scalars at every use: nothing per row is held in registers
+// across the K loop (the list kernels have none to spare).
+struct BankRows {
+  const float* __restrict__ bank;
+  int rows, r0;
+  __device__ __forceinline__ const float* row(int q, int t, int D, bool& in) const {
+    const int r = r0 + ((t + 256 * q) >> 3);
+    in = r < rows;
+    return bank + (long)min(r, rows - 1) * D;
+  }
+};
+
+// GatheredRows: rows of a subset, looked up ONCE per tile by gather_rows() below and held as four addresses and four flags
+struct GatheredRows {
+  const float* ptr[4];
+  bool in[4];
+  __device__ __forceinline__ const float* row(int q, int, int, bool& in_q) const {
+    in_q = in[q];
+    return ptr[q];
+  }
+};
+
+// row r of a subset of `count` rows as a row of the bank: gathered through `list` (null: the identity), clamped into the subset before the
+// list is read and into the bank before the index is ever used as an address
+__device__ __forceinline__ int gather_index(const int* __restrict__ list, int r, int count, int rows) {
+  const int rc = min(r, count - 1);
+  return list ? min(max(list[rc], 0), rows - 1) : rc;
+}
+
+__device__ __forceinline__ GatheredRows gather_rows(const float* __restrict__ bank, int rows, const int* __restrict__ list, int count, int r0, int D, int t) {
+  GatheredRows g;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int r = r0 + ((t + 256 * q) >> 3);
+    g.in[q] = r < count;
+    g.ptr[q] = bank + (long)gather_index(list, r, count, rows) * D;
+  }
+  return g;
+}
 
 // One chunk of one operand, global -> registers: 128 rows x 32 k as 1024 groups of four consecutive k, four groups per thread.  The pivot is
 // subtracted here; zeros past the last row and past D (a zero row adds fma(0, 0, acc) = acc to the chain: nothing).  V = 4: sixteen-byte loads
 // (D % 4 == 0: a group is inside or outside as a whole); V = 1: element by element.  The same values either way.  Every load is issued
 // UNCONDITIONALLY from an address clamped into the bank and masked afterwards by a select: a branch around a load makes the compiler wait for
 // each load before the next one, eight memory round trips per chunk instead of one.
-template <int V>
-__device__ __forceinline__ void load_chunk(const float* __restrict__ bank, int rows, int r0, int D, int k0, const float* __restrict__ pivot, int t,
-                                           f32x4 (&reg)[4]) {
+template <int V, class Rows>
+__device__ __forceinline__ void load_chunk(const Rows& src, int D, int k0, const float* __restrict__ pivot, int t, f32x4 (&reg)[4]) {
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    const int idx = t + 256 * q, row = idx >> 3, k = k0 + (idx & 7) * 4;
-    const bool row_in = r0 + row < rows;
-    const float* __restrict__ p = bank + (long)min(r0 + row, rows - 1) * D;
+    const int k = k0 + ((t + 256 * q) & 7) * 4;
+    bool row_in;
+    const float* __restrict__ p = src.row(q, t, D, row_in);
     f32x4 v;
     if (V == 4) {
       const int kc = min(k, D - 4);
@@ -82,13 +126,14 @@ __device__ __forceinline__ void store_chunk(float* __restrict__ dst, int t, cons
   }
 }
 
-// acc[m][n] = the dot products of A rows a0 + wr 64 + m 32 + (0 .. 31) with B rows b0 + wc 64 + n 32 + (0 .. 31), wave (wr, wc) of the 2 x 2 waves.
+// acc[m][n] = the dot products of rows wr 64 + m 32 + (0 .. 31) of source A with rows wc 64 + n 32 + (0 .. 31) of source B, wave (wr, wc) of the
+// 2 x 2 waves.  THE K loop of this unit: every d2 and every k is a value of this one chain, whatever the sources are.
 // K goes through LDS in chunks of BK, two buffers: the next chunk's global loads are in flight while this one is multiplied, and are written to
 // the other buffer behind it -- one barrier per chunk.  Enters with a barrier (smem may still be read as the previous tile's d2) and leaves with
 // one (smem is free again).
-template <int V>
-__device__ __forceinline__ void tile_dot(const float* __restrict__ A, int NA, int a0, const float* __restrict__ B, int NB, int b0, int D,
-                                         const float* __restrict__ pivot, float* __restrict__ smem, f32x16 (&acc)[2][2]) {
+template <int V, class RowsA, class RowsB>
+__device__ __forceinline__ void tile_dot(const RowsA& A, const RowsB& B, int D, const float* __restrict__ pivot, float* __restrict__ smem,
+                                         f32x16 (&acc)[2][2]) {
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wr = wave >> 1, wc = wave & 1, j = lane & 31, h = lane >> 5;
 #pragma unroll
   for (int m = 0; m < 2; ++m)
@@ -98,8 +143,8 @@ __device__ __forceinline__ void tile_dot(const float* __restrict__ A, int NA, in
       for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
   f32x4 ra[4], rb[4];
   const int chunks = (D + BK - 1) / BK;
-  load_chunk<V>(A, NA, a0, D, 0, pivot, t, ra);
-  load_chunk<V>(B, NB, b0, D, 0, pivot, t, rb);
+  load_chunk<V>(A, D, 0, pivot, t, ra);
+  load_chunk<V>(B, D, 0, pivot, t, rb);
   __syncthreads();
   store_chunk(smem, t, ra);
   store_chunk(smem + OPER, t, rb);
@@ -108,8 +153,8 @@ __device__ __forceinline__ void tile_dot(const float* __restrict__ A, int NA, in
     const float* cur = smem + (c & 1) * BUF;
     const bool more = c + 1 < chunks;
     if (more) {
-      load_chunk<V>(A, NA, a0, D, (c + 1) * BK, pivot, t, ra);
-      load_chunk<V>(B, NB, b0, D, (c + 1) * BK, pivot, t, rb);
+      load_chunk<V>(A, D, (c + 1) * BK, pivot, t, ra);
+      load_chunk<V>(B, D, (c + 1) * BK, pivot, t, rb);
     }
     const float* As = cur + (wr * 64 + j) * LDK + 4 * h;
     const float* Bs = cur + OPER + (wc * 64 + j) * LDK + 4 * h;
@@ -134,136 +179,273 @@ __device__ __forceinline__ void tile_dot(const float* __restrict__ A, int NA, in
   }
 }
 
-// d2 of every element this lane holds, handed to f(local row, local column, d2).  Accumulator layout of the 32 x 32 instruction: the lane's
-// column is lane & 31, register r is row (r & 3) + 8 (r >> 2) + 4 (lane >> 5).  na: the A rows' norms in LDS; nb: the norms of the lane's two columns.
+// Every element this lane holds, handed to f(local row, local column, n, dot): n tells which of the lane's two columns it is.  The one place that
+// knows the accumulator layout of the 32 x 32 instruction: the lane's column is lane & 31, register r is row (r & 3) + 8 (r >> 2) + 4 (lane >> 5).
 template <class F>
-__device__ __forceinline__ void for_each_d2(const f32x16 (&acc)[2][2], const float* __restrict__ na, const float (&nb)[2], F f) {
+__device__ __forceinline__ void for_each_acc(const f32x16 (&acc)[2][2], F f) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wr = wave >> 1, wc = wave & 1, j = lane & 31, h = lane >> 5;
 #pragma unroll
   for (int m = 0; m < 2; ++m)
 #pragma unroll
     for (int n = 0; n < 2; ++n)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int il = wr * 64 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, jl = wc * 64 + n * 32 + j;
-        const float s = na[il] + nb[n];
-        f(il, jl, n, fmaxf(s - 2.f * acc[m][n][r], 0.f));
-      }
+      for (int r = 0; r < 16; ++r) f(wr * 64 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, wc * 64 + n * 32 + j, n, acc[m][n][r]);
 }
 
+// the value functions of an element: its two rows' norms and their dot product in, d2 or k out
+__device__ __forceinline__ float d2_value(float na, float nb, float dot) {
+  const float s = na + nb;
+  return fmaxf(s - 2.f * dot, 0.f);
+}
+
+// The kernel distances (README "Kernel distances", MfKernelSumDesc): poly: v = fmaf(gamma, dot(x, y), c0), k = v, v v, (v v) v, (v v)(v v) for
+// degree 1 .. 4, every product rounded to fp32 (the unit is built with -ffp-contract=off); the callers pass a pivot of zeros: x - 0 is x bit for
+// bit.  rbf: k = expf(fl32(-gamma d2)) of d2_value.  Nothing else enters: the bits of k(i, j) depend on the two rows, the pivot and the scalars,
+// and k(i, j) = k(j, i) (the fmaf chain's products and the sum of the two norms commute).
+struct KernelParams {
+  int kind, degree;
+  float gamma, coef0;
+};
+
+__device__ __forceinline__ float kernel_value(const KernelParams& kp, float na, float nb, float dot) {
+  if (kp.kind == MF_KERNEL_RBF) return expf(-(kp.gamma * d2_value(na, nb, dot)));
+  const float v = fmaf(kp.gamma, dot, kp.coef0);
+  const float v2 = v * v;
+  return kp.degree == 1 ? v : kp.degree == 2 ? v2 : kp.degree == 3 ? v2 * v : v2 * v2;
+}
+
+// the norms of the lane's two columns; zeros past the end, and for a kernel that needs no norms (nb null)
 __device__ __forceinline__ void column_norms(const float* __restrict__ nb, int NB, int b0, float (&out)[2]) {
   const int lane = threadIdx.x & 63, wc = (threadIdx.x >> 6) & 1;
 #pragma unroll
   for (int n = 0; n < 2; ++n) {
     const int jg = b0 + wc * 64 + n * 32 + (lane & 31);
-    out[n] = jg < NB ? nb[jg] : 0.f;
+    out[n] = (nb && jg < NB) ? nb[jg] : 0.f;
   }
 }
 
-// ---- epilogue 1: the matrix itself
-template <int V>
-__global__ __launch_bounds__(256) void sqdist_kernel(const float* __restrict__ x, const float* __restrict__ nx, const float* __restrict__ y,
-                                                     const float* __restrict__ ny, const float* __restrict__ pivot, float* __restrict__ out, int N, int M,
-                                                     int D, int col_tiles, int same_bank) {
+// ---- epilogue 1: the tile's values stored as a matrix: out[i][j] = value(i, j, n(x_i), n(y_j), dot)
+template <int V, class Value>
+__device__ __forceinline__ void store_tile(const float* __restrict__ x, const float* __restrict__ nx, const float* __restrict__ y,
+                                           const float* __restrict__ ny, const float* __restrict__ pivot, float* __restrict__ out, int N, int M, int D,
+                                           int col_tiles, Value value) {
   __shared__ __attribute__((aligned(16))) float smem[SMEM];
   const int t = threadIdx.x;
   const int rt = blockIdx.x / col_tiles, ct = blockIdx.x - rt * col_tiles;
   const int a0 = rt * TM, b0 = ct * TM;
   float* na = smem + STAGE;
-  if (t < TM) na[t] = a0 + t < N ? nx[a0 + t] : 0.f;
+  if (t < TM) na[t] = (nx && a0 + t < N) ? nx[a0 + t] : 0.f;
   f32x16 acc[2][2];
-  tile_dot<V>(x, N, a0, y, M, b0, D, pivot, smem, acc);
+  tile_dot<V>(BankRows{x, N, a0}, BankRows{y, M, b0}, D, pivot, smem, acc);
   float nb[2];
   column_norms(ny, M, b0, nb);
-  for_each_d2(acc, na, nb, [&](int il, int jl, int, float d) {
+  for_each_acc(acc, [&](int il, int jl, int n, float dot) {
     const int ig = a0 + il, jg = b0 + jl;
-    if (ig < N && jg < M) out[(long)ig * M + jg] = (same_bank && ig == jg) ? 0.f : d;
+    if (ig < N && jg < M) out[(long)ig * M + jg] = value(ig, jg, na[il], nb[n], dot);
   });
 }
 
-// the ascending list of the 16 smallest values seen: v goes in where it belongs, the largest falls out
-__device__ __forceinline__ void list_insert(float (&l)[LIST], float v) {
+// d2; with same_bank the diagonal is exactly 0
+template <int V>
+__global__ __launch_bounds__(256) void sqdist_kernel(const float* __restrict__ x, const float* __restrict__ nx, const float* __restrict__ y,
+                                                     const float* __restrict__ ny, const float* __restrict__ pivot, float* __restrict__ out, int N, int M,
+                                                     int D, int col_tiles, int same_bank) {
+  store_tile<V>(x, nx, y, ny, pivot, out, N, M, D, col_tiles, [=](int ig, int jg, float na, float nb, float dot) {
+    const float d = d2_value(na, nb, dot);
+    return (same_bank && ig == jg) ? 0.f : d;
+  });
+}
+
+// k (for tests and kernel_matrix()); the polynomial kernel's norms may be null
+template <int V>
+__global__ __launch_bounds__(256) void kernel_matrix_kernel(const float* __restrict__ x, const float* __restrict__ nx, const float* __restrict__ y,
+                                                            const float* __restrict__ ny, const float* __restrict__ pivot, float* __restrict__ out, int N,
+                                                            int M, int D, int col_tiles, KernelParams kp) {
+  store_tile<V>(x, nx, y, ny, pivot, out, N, M, D, col_tiles, [=](int, int, float na, float nb, float dot) { return kernel_value(kp, na, nb, dot); });
+}
+
+// ---- epilogue 2: every row's ascending list of its 16 smallest entries over the column tiles of split blockIdx.y
+// An entry is a value -- d2 alone, float order: ties cannot matter (the k-NN radii) -- or a key: the pair (d2, j) as 64 bits, the bits of d2 high and
+// the reference index j low (the neighbour search).  d2 >= 0, so unsigned order of the keys is the lexicographic order (d2 as a float, then the
+// smaller j).  The indices are unique, so that order is total and the k smallest keys of a row are a SET: no tile, split count or order of merging
+// can change them.  -0 becomes +0 before packing (fmaxf(-0, 0) may return either; the raw bits of -0 would sort last).  An empty slot is
+// (+inf, -1): above every real entry, a real +inf included.
+typedef unsigned long long nnkey;
+constexpr nnkey NN_EMPTY = 0x7F800000FFFFFFFFull;
+
+__device__ __forceinline__ nnkey nn_key(float d, int j) {
+  unsigned b = __float_as_uint(d);
+  b = b == 0x80000000u ? 0u : b;
+  return ((nnkey)b << 32) | (unsigned)j;
+}
+
+__device__ __forceinline__ float list_min(float a, float b) { return fminf(a, b); }
+__device__ __forceinline__ float list_max(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ nnkey list_min(nnkey a, nnkey b) { return a < b ? a : b; }
+__device__ __forceinline__ nnkey list_max(nnkey a, nnkey b) { return a < b ? b : a; }
+
+// v goes in where it belongs, the largest falls out
+template <class E>
+__device__ __forceinline__ void list_insert(E (&l)[LIST], E v) {
   if (v < l[LIST - 1]) {
 #pragma unroll
     for (int p = 0; p < LIST; ++p) {
-      const float lo = fminf(l[p], v);
-      v = fmaxf(l[p], v);
+      const E lo = list_min(l[p], v);
+      v = list_max(l[p], v);
       l[p] = lo;
     }
   }
 }
 
-// ---- epilogue 2: every row's 16 smallest d2 over the column tiles of split blockIdx.y (the row itself counts, as exactly 0)
-// After each column tile the d2 tile goes to LDS (the accumulator layout spreads a row over lanes and registers); thread (row, half) merges 64 of
-// the row's 128 values into its own list, the two halves meet at the end.  Only values are kept: ties cannot matter.
-template <int V>
-__global__ __launch_bounds__(256, 2) void knn_partial_kernel(const float* __restrict__ x, const float* __restrict__ nx, const float* __restrict__ pivot,
-                                                          float* __restrict__ part, int N, int D, int S) {
+// What the two kinds of list do differently.  staged: what the tile in LDS holds for query row ig and reference row jg; takes: whether column j
+// is inserted at all; WORDS: a row of the hand-over between the two halves, in 4-byte words (odd: no bank conflicts); store: the row's list to
+// the workspace.
+struct ValueList {      // the bank against itself: the row itself counts, as exactly 0; a column past the end is +inf
+  typedef float Entry;
+  static constexpr int WORDS = LIST + 1;
+  static __device__ __forceinline__ Entry empty() { return INFINITY; }
+  static __device__ __forceinline__ float staged(int ig, int jg, int refs, float d) { return jg >= refs ? INFINITY : (ig == jg ? 0.f : d); }
+  static __device__ __forceinline__ bool takes(int, int, int) { return true; }
+  static __device__ __forceinline__ Entry entry(float d, int) { return d; }
+  static __device__ __forceinline__ void put(float* w, int p, Entry e) { w[p] = e; }
+  static __device__ __forceinline__ Entry get(const float* w, int p) { return w[p]; }
+  static __device__ __forceinline__ void store(Entry* __restrict__ o, const Entry (&l)[LIST]) {
+#pragma unroll
+    for (int p = 0; p < LIST; p += 4) *reinterpret_cast<f32x4*>(o + p) = f32x4{l[p], l[p + 1], l[p + 2], l[p + 3]};
+  }
+};
+
+struct KeyList {        // a column past the end of the bank is never inserted; with exclude_self the entry j == i is skipped BY INDEX: another
+  typedef nnkey Entry;  // row with the same features stays a neighbour at 0
+  static constexpr int WORDS = 2 * LIST + 1;      // (low, high, low, high, ...)
+  static __device__ __forceinline__ Entry empty() { return NN_EMPTY; }
+  static __device__ __forceinline__ float staged(int, int, int, float d) { return d; }
+  static __device__ __forceinline__ bool takes(int j, int refs, int skip) { return j < refs && j != skip; }
+  static __device__ __forceinline__ Entry entry(float d, int j) { return nn_key(d, j); }
+  static __device__ __forceinline__ void put(float* w, int p, Entry e) {
+    reinterpret_cast<unsigned*>(w)[2 * p] = (unsigned)e;
+    reinterpret_cast<unsigned*>(w)[2 * p + 1] = (unsigned)(e >> 32);
+  }
+  static __device__ __forceinline__ Entry get(const float* w, int p) {
+    return ((nnkey)reinterpret_cast<const unsigned*>(w)[2 * p + 1] << 32) | reinterpret_cast<const unsigned*>(w)[2 * p];
+  }
+  static __device__ __forceinline__ void store(Entry* __restrict__ o, const Entry (&l)[LIST]) {
+#pragma unroll
+    for (int p = 0; p < LIST; ++p) o[p] = l[p];
+  }
+};
+static_assert(TM * LDT <= STAGE && TM * ValueList::WORDS <= STAGE && TM * KeyList::WORDS <= STAGE, "the epilogues reuse the staging buffers");
+
+// The queries are the tile's ROWS (workgroup blockIdx.x takes 128 of them); the reference bank is walked as column tiles.  After each column tile
+// the d2 tile goes to LDS (the accumulator layout spreads a row over lanes and registers); thread (row, half) merges 64 of the row's 128 columns
+// into its own list, the two halves meet at the end.  part: [S][queries][LIST].  skip: the reference index left out of row a0 + row, or -1.
+template <int V, class L>
+__device__ __forceinline__ void list_partial(const float* __restrict__ qry, const float* __restrict__ nqry, int queries, const float* __restrict__ ref,
+                                             const float* __restrict__ nref, int refs, const float* __restrict__ pivot,
+                                             typename L::Entry* __restrict__ part, int D, int S, bool skip_self) {
+  typedef typename L::Entry Entry;
   __shared__ __attribute__((aligned(16))) float smem[SMEM];
   const int t = threadIdx.x, row = t & (TM - 1), half = t >> 7;
   const int a0 = blockIdx.x * TM, s = blockIdx.y;
-  const int col_tiles = (N + TM - 1) / TM;
+  const int col_tiles = (refs + TM - 1) / TM;
   const int cb = (int)((long)s * col_tiles / S), ce = (int)((long)(s + 1) * col_tiles / S);
   float* na = smem + STAGE;
-  if (t < TM) na[t] = a0 + t < N ? nx[a0 + t] : 0.f;
-  float l[LIST];
+  if (t < TM) na[t] = a0 + t < queries ? nqry[a0 + t] : 0.f;
+  Entry l[LIST];
 #pragma unroll
-  for (int p = 0; p < LIST; ++p) l[p] = INFINITY;
+  for (int p = 0; p < LIST; ++p) l[p] = L::empty();
+  const int skip = skip_self ? a0 + row : -1;
   for (int ct = cb; ct < ce; ++ct) {
     const int b0 = ct * TM;
     f32x16 acc[2][2];
-    tile_dot<V>(x, N, a0, x, N, b0, D, pivot, smem, acc);
+    tile_dot<V>(BankRows{qry, queries, a0}, BankRows{ref, refs, b0}, D, pivot, smem, acc);
     float nb[2];
-    column_norms(nx, N, b0, nb);
-    for_each_d2(acc, na, nb, [&](int il, int jl, int, float d) {
-      const int ig = a0 + il, jg = b0 + jl;
-      smem[il * LDT + jl] = jg >= N ? INFINITY : (ig == jg ? 0.f : d);
+    column_norms(nref, refs, b0, nb);
+    for_each_acc(acc, [&](int il, int jl, int n, float dot) {
+      smem[il * LDT + jl] = L::staged(a0 + il, b0 + jl, refs, d2_value(na[il], nb[n], dot));
     });
     __syncthreads();
     const float* mine = smem + row * LDT + half * 64;
-    for (int c = 0; c < 64; ++c) list_insert(l, mine[c]);
+    const int j0 = b0 + half * 64;
+    for (int c = 0; c < 64; ++c)
+      if (L::takes(j0 + c, refs, skip)) list_insert(l, L::entry(mine[c], j0 + c));
   }
   __syncthreads();
+  float* hand = smem + row * L::WORDS;
   if (half == 1) {
 #pragma unroll
-    for (int p = 0; p < LIST; ++p) smem[row * (LIST + 1) + p] = l[p];
+    for (int p = 0; p < LIST; ++p) L::put(hand, p, l[p]);
   }
   __syncthreads();
   if (half == 0) {
 #pragma unroll
-    for (int p = 0; p < LIST; ++p) list_insert(l, smem[row * (LIST + 1) + p]);
-    if (a0 + row < N) {
-      float* o = part + ((long)s * N + a0 + row) * LIST;
-#pragma unroll
-      for (int p = 0; p < LIST; p += 4) *reinterpret_cast<f32x4*>(o + p) = f32x4{l[p], l[p + 1], l[p + 2], l[p + 3]};
-    }
+    for (int p = 0; p < LIST; ++p) list_insert(l, L::get(hand, p));
+    if (a0 + row < queries) L::store(part + ((long)s * queries + a0 + row) * LIST, l);
   }
 }
 
-// r2[i] = the (knn + 1)-th smallest of row i: the S partial lists merged in ascending split order, one thread per row
+// the k-NN radii: every row's 16 smallest d2 inside its own bank
+template <int V>
+__global__ __launch_bounds__(256, 2) void knn_partial_kernel(const float* __restrict__ x, const float* __restrict__ nx, const float* __restrict__ pivot,
+                                                          float* __restrict__ part, int N, int D, int S) {
+  list_partial<V, ValueList>(x, nx, N, x, nx, N, pivot, part, D, S, false);
+}
+
+// the neighbour search: the k <= 16 nearest of the N reference rows of every one of the M query rows, values AND indices, across two banks
+template <int V>
+__global__ __launch_bounds__(256, 2) void nn_partial_kernel(const float* __restrict__ qry, const float* __restrict__ nqry, const float* __restrict__ ref,
+                                                         const float* __restrict__ nref, const float* __restrict__ pivot, nnkey* __restrict__ part, int N,
+                                                         int M, int D, int S, int exclude_self) {
+  list_partial<V, KeyList>(qry, nqry, M, ref, nref, N, pivot, part, D, S, exclude_self != 0);
+}
+
+// row i's S partial lists merged in ascending split order into l
+template <class E>
+__device__ __forceinline__ void merge_partials(const E* __restrict__ part, int i, int rows, int S, E (&l)[LIST]) {
+  const E* q = part + (long)i * LIST;
+#pragma unroll
+  for (int p = 0; p < LIST; ++p) l[p] = q[p];
+  for (int s = 1; s < S; ++s) {
+    q = part + ((long)s * rows + i) * LIST;
+    for (int p = 0; p < LIST; ++p) list_insert(l, q[p]);
+  }
+}
+
+// r2[i] = the (knn + 1)-th smallest of row i, one thread per row
 __global__ __launch_bounds__(256) void knn_finish_kernel(const float* __restrict__ part, float* __restrict__ r2, int N, int S, int knn) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
   float l[LIST];
-  const float* q = part + (long)i * LIST;
-#pragma unroll
-  for (int p = 0; p < LIST; ++p) l[p] = q[p];
-  for (int s = 1; s < S; ++s) {
-    q = part + ((long)s * N + i) * LIST;
-    for (int p = 0; p < LIST; ++p) list_insert(l, q[p]);
-  }
+  merge_partials(part, i, N, S, l);
   float v = l[0];
 #pragma unroll
   for (int p = 1; p < LIST; ++p) v = p == knn ? l[p] : v;
   r2[i] = v;
 }
 
-// ---- epilogue 3: is query j inside any reference row's ball?  hit_j = any_i [d2(R_i, Q_j) < r2_i], strict, over the reference tiles of split blockIdx.y.
-// The queries are the tile's COLUMNS: a lane owns two of them for the whole launch and ORs over its registers, tile after tile.
-template <int V>
-__global__ __launch_bounds__(256, 2) void manifold_partial_kernel(const float* __restrict__ ref, const float* __restrict__ nref, const float* __restrict__ r2,
-                                                               const float* __restrict__ qry, const float* __restrict__ nqry,
-                                                               const float* __restrict__ pivot, uint8_t* __restrict__ part, int NR, int M, int D, int S) {
+// d2[j][0 .. k) and index[j][0 .. k) of query j, one thread per query row
+__global__ __launch_bounds__(256) void nn_finish_kernel(const nnkey* __restrict__ part, float* __restrict__ d2, int* __restrict__ index, int M, int S,
+                                                        int k) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= M) return;
+  nnkey l[LIST];
+  merge_partials(part, i, M, S, l);
+#pragma unroll
+  for (int p = 0; p < LIST; ++p)
+    if (p < k) {
+      d2[(long)i * k + p] = __uint_as_float((unsigned)(l[p] >> 32));
+      index[(long)i * k + p] = (int)(unsigned)l[p];
+    }
+}
+
+// ---- epilogue 3: which reference rows' balls is query j inside?  [d2(R_i, Q_j) < r2_i], strict, over the reference tiles of split blockIdx.y: ANY of
+// them as a flag (Count false), or their NUMBER (Count true).  The queries are the tile's COLUMNS: a lane owns two of them for the whole launch
+// and ORs / counts over its registers, tile after tile; the four lanes that own a column (2 waves x 2 halves) meet in LDS -- a plain store of 1
+// (several lanes may store the same 1), or an LDS integer add (integer sums: every order gives the same bits).
+template <int V, bool Count>
+__device__ __forceinline__ void manifold_partial(const float* __restrict__ ref, const float* __restrict__ nref, const float* __restrict__ r2,
+                                                 const float* __restrict__ qry, const float* __restrict__ nqry, const float* __restrict__ pivot,
+                                                 std::conditional_t<Count, int, uint8_t>* __restrict__ part, int NR, int M, int D, int S) {
   __shared__ __attribute__((aligned(16))) float smem[SMEM];
   const int t = threadIdx.x;
   const int b0 = blockIdx.x * TM, s = blockIdx.y;
@@ -273,31 +455,65 @@ __global__ __launch_bounds__(256, 2) void manifold_partial_kernel(const float* _
   float* rad = na + TM;
   float nb[2];
   column_norms(nqry, M, b0, nb);
-  bool hit[2] = {false, false};
+  std::conditional_t<Count, int, bool> in[2] = {};
   for (int rt = rb; rt < re; ++rt) {
     const int a0 = rt * TM;
     if (t < TM) {
-      const bool in = a0 + t < NR;
-      na[t] = in ? nref[a0 + t] : 0.f;
-      rad[t] = in ? r2[a0 + t] : -1.f;     // d2 >= 0: a row past the end holds nobody
+      const bool row_in = a0 + t < NR;
+      na[t] = row_in ? nref[a0 + t] : 0.f;
+      rad[t] = row_in ? r2[a0 + t] : -1.f;     // d2 >= 0: a row past the end holds nobody
     }
     f32x16 acc[2][2];
-    tile_dot<V>(ref, NR, a0, qry, M, b0, D, pivot, smem, acc);
-    for_each_d2(acc, na, nb, [&](int il, int, int n, float d) { hit[n] = hit[n] || d < rad[il]; });
+    tile_dot<V>(BankRows{ref, NR, a0}, BankRows{qry, M, b0}, D, pivot, smem, acc);
+    for_each_acc(acc, [&](int il, int, int n, float dot) {
+      const bool inside = d2_value(na[il], nb[n], dot) < rad[il];
+      if constexpr (Count) in[n] += inside ? 1 : 0;
+      else in[n] = in[n] || inside;
+    });
     __syncthreads();                       // na / rad are rewritten by the next tile
   }
-  int* flags = reinterpret_cast<int*>(smem);
-  if (t < TM) flags[t] = 0;
+  int* cols = reinterpret_cast<int*>(smem);
+  if (t < TM) cols[t] = 0;
   __syncthreads();
   const int lane = t & 63, wc = (t >> 6) & 1;
 #pragma unroll
-  for (int n = 0; n < 2; ++n)
-    if (hit[n]) flags[wc * 64 + n * 32 + (lane & 31)] = 1;    // (several lanes may store the same 1)
+  for (int n = 0; n < 2; ++n) {
+    int* col = &cols[wc * 64 + n * 32 + (lane & 31)];
+    if constexpr (Count) atomicAdd(col, in[n]);
+    else if (in[n]) *col = 1;
+  }
   __syncthreads();
-  if (t < TM && b0 + t < M) part[(long)s * M + b0 + t] = (uint8_t)flags[t];
+  if (t < TM && b0 + t < M) part[(long)s * M + b0 + t] = cols[t];
 }
 
-// hit[j] = the OR of the S partial flags in ascending split order; count = their number, by a fixed tree.  ONE workgroup.
+template <int V>
+__global__ __launch_bounds__(256, 2) void manifold_partial_kernel(const float* __restrict__ ref, const float* __restrict__ nref, const float* __restrict__ r2,
+                                                               const float* __restrict__ qry, const float* __restrict__ nqry,
+                                                               const float* __restrict__ pivot, uint8_t* __restrict__ part, int NR, int M, int D, int S) {
+  manifold_partial<V, false>(ref, nref, r2, qry, nqry, pivot, part, NR, M, D, S);
+}
+
+template <int V>
+__global__ __launch_bounds__(256, 2) void manifold_count_partial_kernel(const float* __restrict__ ref, const float* __restrict__ nref,
+                                                                     const float* __restrict__ r2, const float* __restrict__ qry,
+                                                                     const float* __restrict__ nqry, const float* __restrict__ pivot,
+                                                                     int* __restrict__ part, int NR, int M, int D, int S) {
+  manifold_partial<V, true>(ref, nref, r2, qry, nqry, pivot, part, NR, M, D, S);
+}
+
+// the sum of the 1024 threads' c by a fixed tree, as thread 0 sees it.  ONE workgroup of 1024.
+template <class T>
+__device__ __forceinline__ T tree_sum_1024(T* red, T c) {
+  red[threadIdx.x] = c;
+  __syncthreads();
+  for (int o = 512; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// hit[j] = the OR of the S partial flags in ascending split order; count = their number
 __global__ __launch_bounds__(1024) void manifold_finish_kernel(const uint8_t* __restrict__ part, uint8_t* __restrict__ hit, int* __restrict__ count, int M,
                                                                int S) {
   __shared__ int red[1024];
@@ -309,180 +525,11 @@ __global__ __launch_bounds__(1024) void manifold_finish_kernel(const uint8_t* __
     if (hit) hit[j] = f;
     c += f;
   }
-  red[threadIdx.x] = c;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && count) *count = red[0];
+  c = tree_sum_1024(red, c);
+  if (threadIdx.x == 0 && count) *count = c;
 }
 
-// ---- epilogue 4: the k <= 16 nearest reference rows of every query row, values AND indices, across two banks
-// A list entry is the pair (d2, j) as one 64-bit key, the bits of d2 high and the reference index j low: d2 >= 0, so unsigned order of the keys is
-// the lexicographic order (d2 as a float, then the smaller j).  The indices are unique, so the order is total and the k smallest keys of a row are a
-// SET: no tile, split count or order of merging can change them.  -0 becomes +0 before packing (fmaxf(-0, 0) may return either; the raw bits of -0
-// would sort last).  An empty slot is (+inf, -1): above every real entry, a real +inf included.
-typedef unsigned long long nnkey;
-constexpr nnkey NN_EMPTY = 0x7F800000FFFFFFFFull;
-
-__device__ __forceinline__ nnkey nn_key(float d, int j) {
-  unsigned b = __float_as_uint(d);
-  b = b == 0x80000000u ? 0u : b;
-  return ((nnkey)b << 32) | (unsigned)j;
-}
-
-// list_insert on keys
-__device__ __forceinline__ void key_insert(nnkey (&l)[LIST], nnkey v) {
-  if (v < l[LIST - 1]) {
-#pragma unroll
-    for (int p = 0; p < LIST; ++p) {
-      const nnkey lo = l[p] < v ? l[p] : v;
-      v = l[p] < v ? v : l[p];
-      l[p] = lo;
-    }
-  }
-}
-
-// The queries are the tile's ROWS; the reference bank is walked as column tiles over split blockIdx.y, as knn_partial_kernel walks its own bank.
-// The d2 tile goes through LDS, thread (row, half) merges 64 columns into its list, the halves meet at the end.  A column past the end of the bank
-// is never inserted; with exclude_self (one bank) the entry j == i is skipped BY INDEX: another row with the same features stays a neighbour at 0.
-template <int V>
-__global__ __launch_bounds__(256, 2) void nn_partial_kernel(const float* __restrict__ qry, const float* __restrict__ nqry, const float* __restrict__ ref,
-                                                         const float* __restrict__ nref, const float* __restrict__ pivot, nnkey* __restrict__ part, int N,
-                                                         int M, int D, int S, int exclude_self) {
-  __shared__ __attribute__((aligned(16))) float smem[SMEM];
-  const int t = threadIdx.x, row = t & (TM - 1), half = t >> 7;
-  const int a0 = blockIdx.x * TM, s = blockIdx.y;
-  const int col_tiles = (N + TM - 1) / TM;
-  const int cb = (int)((long)s * col_tiles / S), ce = (int)((long)(s + 1) * col_tiles / S);
-  float* na = smem + STAGE;
-  if (t < TM) na[t] = a0 + t < M ? nqry[a0 + t] : 0.f;
-  nnkey l[LIST];
-#pragma unroll
-  for (int p = 0; p < LIST; ++p) l[p] = NN_EMPTY;
-  const int skip = exclude_self ? a0 + row : -1;
-  for (int ct = cb; ct < ce; ++ct) {
-    const int b0 = ct * TM;
-    f32x16 acc[2][2];
-    tile_dot<V>(qry, M, a0, ref, N, b0, D, pivot, smem, acc);
-    float nb[2];
-    column_norms(nref, N, b0, nb);
-    for_each_d2(acc, na, nb, [&](int il, int jl, int, float d) { smem[il * LDT + jl] = d; });
-    __syncthreads();
-    const float* mine = smem + row * LDT + half * 64;
-    const int j0 = b0 + half * 64;
-    for (int c = 0; c < 64; ++c) {
-      const int j = j0 + c;
-      if (j < N && j != skip) key_insert(l, nn_key(mine[c], j));
-    }
-  }
-  __syncthreads();
-  unsigned* words = reinterpret_cast<unsigned*>(smem);      // a row of the hand-over: 2 LIST + 1 words (low, high, low, high, ...)
-  if (half == 1) {
-#pragma unroll
-    for (int p = 0; p < LIST; ++p) {
-      words[row * (2 * LIST + 1) + 2 * p] = (unsigned)l[p];
-      words[row * (2 * LIST + 1) + 2 * p + 1] = (unsigned)(l[p] >> 32);
-    }
-  }
-  __syncthreads();
-  if (half == 0) {
-#pragma unroll
-    for (int p = 0; p < LIST; ++p)
-      key_insert(l, ((nnkey)words[row * (2 * LIST + 1) + 2 * p + 1] << 32) | words[row * (2 * LIST + 1) + 2 * p]);
-    if (a0 + row < M) {
-      nnkey* o = part + ((long)s * M + a0 + row) * LIST;
-#pragma unroll
-      for (int p = 0; p < LIST; ++p) o[p] = l[p];
-    }
-  }
-}
-
-// d2[j][0 .. k) and index[j][0 .. k) of query j: the S partial lists merged in ascending split order, one thread per query row
-__global__ __launch_bounds__(256) void nn_finish_kernel(const nnkey* __restrict__ part, float* __restrict__ d2, int* __restrict__ index, int M, int S,
-                                                        int k) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= M) return;
-  nnkey l[LIST];
-  const nnkey* q = part + (long)i * LIST;
-#pragma unroll
-  for (int p = 0; p < LIST; ++p) l[p] = q[p];
-  for (int s = 1; s < S; ++s) {
-    q = part + ((long)s * M + i) * LIST;
-    for (int p = 0; p < LIST; ++p) key_insert(l, q[p]);
-  }
-#pragma unroll
-  for (int p = 0; p < LIST; ++p)
-    if (p < k) {
-      d2[(long)i * k + p] = __uint_as_float((unsigned)(l[p] >> 32));
-      index[(long)i * k + p] = (int)(unsigned)l[p];
-    }
-}
-
-// The exact distance of listed pairs: out[j][p] = fl32(the fp64 sum over k of fl32(q_jk - r_ik)^2), i = index[j][p].  No pivot: a difference does
-// not move under a shift.  One wave per pair: lane l takes k = l, l + 64, ... ascending, then the fixed shuffle tree of norms_kernel; element loads,
-// so the result does not depend on alignment or place.  The index is clamped into the bank BEFORE the load (a -1 never reaches memory); a pair
-// whose index is outside the bank is stored as +inf.  Equal rows give exactly 0.
-__global__ __launch_bounds__(256) void pair_sqdist_kernel(const float* __restrict__ qry, const float* __restrict__ ref, const int* __restrict__ index,
-                                                          float* __restrict__ out, long pairs, int N, int D, int k) {
-  const int lane = threadIdx.x & 63;
-  const long pair = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (pair >= pairs) return;
-  const int i = index[pair];
-  const float* __restrict__ x = qry + (pair / k) * D;
-  const float* __restrict__ y = ref + (long)min(max(i, 0), N - 1) * D;
-  double s = 0.0;
-  for (int c = lane; c < D; c += 64) {
-    const float v = x[c] - y[c];
-    s += (double)v * (double)v;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  if (lane == 0) out[pair] = (unsigned)i < (unsigned)N ? (float)s : INFINITY;
-}
-
-// ---- epilogue 5: the counting form of epilogue 3: count_j = #{ i : d2(R_i, Q_j) < r2_i } over the reference tiles of split blockIdx.y.
-// A lane counts over its registers, tile after tile; the four lanes that own a column (2 waves x 2 halves) are added through LDS.  Integer sums:
-// every order gives the same bits.
-template <int V>
-__global__ __launch_bounds__(256, 2) void manifold_count_partial_kernel(const float* __restrict__ ref, const float* __restrict__ nref,
-                                                                     const float* __restrict__ r2, const float* __restrict__ qry,
-                                                                     const float* __restrict__ nqry, const float* __restrict__ pivot,
-                                                                     int* __restrict__ part, int NR, int M, int D, int S) {
-  __shared__ __attribute__((aligned(16))) float smem[SMEM];
-  const int t = threadIdx.x;
-  const int b0 = blockIdx.x * TM, s = blockIdx.y;
-  const int row_tiles = (NR + TM - 1) / TM;
-  const int rb = (int)((long)s * row_tiles / S), re = (int)((long)(s + 1) * row_tiles / S);
-  float* na = smem + STAGE;
-  float* rad = na + TM;
-  float nb[2];
-  column_norms(nqry, M, b0, nb);
-  int cnt[2] = {0, 0};
-  for (int rt = rb; rt < re; ++rt) {
-    const int a0 = rt * TM;
-    if (t < TM) {
-      const bool in = a0 + t < NR;
-      na[t] = in ? nref[a0 + t] : 0.f;
-      rad[t] = in ? r2[a0 + t] : -1.f;     // d2 >= 0: a row past the end holds nobody
-    }
-    f32x16 acc[2][2];
-    tile_dot<V>(ref, NR, a0, qry, M, b0, D, pivot, smem, acc);
-    for_each_d2(acc, na, nb, [&](int il, int, int n, float d) { cnt[n] += d < rad[il] ? 1 : 0; });
-    __syncthreads();                       // na / rad are rewritten by the next tile
-  }
-  int* sums = reinterpret_cast<int*>(smem);
-  if (t < TM) sums[t] = 0;
-  __syncthreads();
-  const int lane = t & 63, wc = (t >> 6) & 1;
-#pragma unroll
-  for (int n = 0; n < 2; ++n) atomicAdd(&sums[wc * 64 + n * 32 + (lane & 31)], cnt[n]);     // an LDS integer add
-  __syncthreads();
-  if (t < TM && b0 + t < M) part[(long)s * M + b0 + t] = sums[t];
-}
-
-// count[j] = the sum of the S partial counts; total = the sum of count[] as int64, by a fixed tree.  ONE workgroup.
+// count[j] = the sum of the S partial counts; total = the sum of count[] as int64
 __global__ __launch_bounds__(1024) void manifold_count_finish_kernel(const int* __restrict__ part, int* __restrict__ count, long long* __restrict__ total,
                                                                      int M, int S) {
   __shared__ long long red[1024];
@@ -493,30 +540,41 @@ __global__ __launch_bounds__(1024) void manifold_count_finish_kernel(const int* 
     if (count) count[j] = f;
     c += f;
   }
-  red[threadIdx.x] = c;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && total) *total = red[0];
+  c = tree_sum_1024(red, c);
+  if (threadIdx.x == 0 && total) *total = c;
 }
 
-// n(x) of every row: xt = fl32(x - c), the sum of xt^2 in fp64 -- lane l of the row's wave takes k = l, l + 64, ... ascending, then a fixed shuffle
-// tree -- rounded to fp32.  Four rows per workgroup, one wave each; element loads, so a row's result does not depend on its alignment or place.
-__global__ __launch_bounds__(256) void norms_kernel(const float* __restrict__ x, const float* __restrict__ pivot, float* __restrict__ out, int N, int D) {
-  const int lane = threadIdx.x & 63;
-  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= N) return;
-  const float* __restrict__ p = x + row * D;
+// The fp64 sum over k of fl32(x_k - y_k)^2, in every lane of the wave: lane l takes k = l, l + 64, ... ascending, then a fixed shuffle tree.
+// Element loads, so the result does not depend on the rows' alignment or place.
+__device__ __forceinline__ double wave_sqsum(const float* __restrict__ x, const float* __restrict__ y, int D) {
   double s = 0.0;
-  for (int k = lane; k < D; k += 64) {
-    const float v = p[k] - pivot[k];
+  for (int k = threadIdx.x & 63; k < D; k += 64) {
+    const float v = x[k] - y[k];
     s += (double)v * (double)v;
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  if (lane == 0) out[row] = (float)s;
+  return s;
+}
+
+// n(x) of every row: xt = fl32(x - c), the sum of xt^2 by wave_sqsum, rounded to fp32.  Four rows per workgroup, one wave each.
+__global__ __launch_bounds__(256) void norms_kernel(const float* __restrict__ x, const float* __restrict__ pivot, float* __restrict__ out, int N, int D) {
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= N) return;
+  const double s = wave_sqsum(x + row * D, pivot, D);
+  if ((threadIdx.x & 63) == 0) out[row] = (float)s;
+}
+
+// The exact distance of listed pairs: out[j][p] = fl32(wave_sqsum of q_j and r_i), i = index[j][p].  No pivot: a difference does not move under a
+// shift.  One wave per pair.  The index is clamped into the bank BEFORE the load (a -1 never reaches memory); a pair whose index is outside the
+// bank is stored as +inf.  Equal rows give exactly 0.
+__global__ __launch_bounds__(256) void pair_sqdist_kernel(const float* __restrict__ qry, const float* __restrict__ ref, const int* __restrict__ index,
+                                                          float* __restrict__ out, long pairs, int N, int D, int k) {
+  const long pair = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (pair >= pairs) return;
+  const int i = index[pair];
+  const double s = wave_sqsum(qry + (pair / k) * D, ref + (long)min(max(i, 0), N - 1) * D, D);
+  if ((threadIdx.x & 63) == 0) out[pair] = (unsigned)i < (unsigned)N ? (float)s : INFINITY;
 }
 
 // c[k] = the mean of column k in fp64, rounded to fp32.  A workgroup takes 32 columns; thread (column, phase p of 8) adds rows p, p + 8, ... in
@@ -538,133 +596,6 @@ __global__ __launch_bounds__(256) void colmean_kernel(const float* __restrict__ 
   }
 }
 
-// ---- the kernel distances (README "Kernel distances", MfKernelSumDesc): k(x, y) of the tile's dot products, summed while still in the accumulators
-// poly: v = fmaf(gamma, dot(x, y), c0), k = v, v v, (v v) v, (v v)(v v) for degree 1 .. 4, every product rounded to fp32 (the unit is built with
-// -ffp-contract=off); the callers pass a pivot of zeros: x - 0 is x bit for bit.  rbf: k = expf(fl32(-gamma d2)) with d2 exactly as for_each_d2
-// forms it.  Nothing else enters: the bits of k(i, j) depend on the two rows, the pivot and the scalars, and k(i, j) = k(j, i) (the fmaf chain's
-// products and the sum of the two norms commute).
-struct KernelParams {
-  int kind, degree;
-  float gamma, coef0;
-};
-
-__device__ __forceinline__ float kernel_value(const KernelParams& kp, float dot, float na, float nb) {
-  if (kp.kind == MF_KERNEL_RBF) {
-    const float s = na + nb;
-    const float d2 = fmaxf(s - 2.f * dot, 0.f);
-    return expf(-(kp.gamma * d2));
-  }
-  const float v = fmaf(kp.gamma, dot, kp.coef0);
-  const float v2 = v * v;
-  return kp.degree == 1 ? v : kp.degree == 2 ? v2 : kp.degree == 3 ? v2 * v : v2 * v2;
-}
-
-// k of every element this lane holds, handed to f(local row, local column, k): for_each_d2's walk, in its order
-template <class F>
-__device__ __forceinline__ void for_each_k(const f32x16 (&acc)[2][2], const KernelParams& kp, const float* __restrict__ na, const float (&nb)[2], F f) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wr = wave >> 1, wc = wave & 1, j = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int n = 0; n < 2; ++n)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int il = wr * 64 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, jl = wc * 64 + n * 32 + j;
-        f(il, jl, kernel_value(kp, acc[m][n][r], na[il], nb[n]));
-      }
-}
-
-// The four rows of one operand that thread t stages in every chunk (load_chunk's rows t / 8 + 32 q), looked up ONCE per tile: the row of the
-// subset is gathered through `list` (null: the identity), the index clamped into the bank before it is ever used as an address; a row past the
-// end of the subset takes the last one's address and is masked.
-__device__ __forceinline__ void gather_rows(const float* __restrict__ bank, int rows, const int* __restrict__ list, int count, int r0, int D, int t,
-                                            const float* (&ptr)[4], bool (&in)[4]) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int r = r0 + ((t + 256 * q) >> 3);
-    in[q] = r < count;
-    const int rc = min(r, count - 1);
-    const int g = list ? min(max(list[rc], 0), rows - 1) : rc;
-    ptr[q] = bank + (long)g * D;
-  }
-}
-
-// load_chunk through the gathered row addresses: the same values, the same masks, every load issued unconditionally from a clamped address
-template <int V>
-__device__ __forceinline__ void load_chunk_rows(const float* const (&ptr)[4], const bool (&rin)[4], int D, int k0, const float* __restrict__ pivot, int t,
-                                                f32x4 (&reg)[4]) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int k = k0 + ((t + 256 * q) & 7) * 4;
-    const float* __restrict__ p = ptr[q];
-    f32x4 v;
-    if (V == 4) {
-      const int kc = min(k, D - 4);
-      const f32x4 d = *reinterpret_cast<const f32x4*>(p + kc) - *reinterpret_cast<const f32x4*>(pivot + kc);
-      const bool in = rin[q] && k < D;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = in ? d[e] : 0.f;
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int kc = min(k + e, D - 1);
-        const float d = p[kc] - pivot[kc];
-        v[e] = (rin[q] && k + e < D) ? d : 0.f;
-      }
-    }
-    reg[q] = v;
-  }
-}
-
-// tile_dot over gathered rows: the same staging, the same chain of matrix instructions over k ascending, so the same bits per pair of rows
-template <int V>
-__device__ __forceinline__ void tile_dot_rows(const float* const (&pa)[4], const bool (&ina)[4], const float* const (&pb)[4], const bool (&inb)[4], int D,
-                                              const float* __restrict__ pivot, float* __restrict__ smem, f32x16 (&acc)[2][2]) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wr = wave >> 1, wc = wave & 1, j = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int n = 0; n < 2; ++n)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
-  f32x4 ra[4], rb[4];
-  const int chunks = (D + BK - 1) / BK;
-  load_chunk_rows<V>(pa, ina, D, 0, pivot, t, ra);
-  load_chunk_rows<V>(pb, inb, D, 0, pivot, t, rb);
-  __syncthreads();
-  store_chunk(smem, t, ra);
-  store_chunk(smem + OPER, t, rb);
-  __syncthreads();
-  for (int c = 0; c < chunks; ++c) {
-    const float* cur = smem + (c & 1) * BUF;
-    const bool more = c + 1 < chunks;
-    if (more) {
-      load_chunk_rows<V>(pa, ina, D, (c + 1) * BK, pivot, t, ra);
-      load_chunk_rows<V>(pb, inb, D, (c + 1) * BK, pivot, t, rb);
-    }
-    const float* As = cur + (wr * 64 + j) * LDK + 4 * h;
-    const float* Bs = cur + OPER + (wc * 64 + j) * LDK + 4 * h;
-#pragma unroll
-    for (int g = 0; g < BK / 8; ++g) {
-      const f32x4 fa0 = *reinterpret_cast<const f32x4*>(As + 8 * g), fa1 = *reinterpret_cast<const f32x4*>(As + 32 * LDK + 8 * g);
-      const f32x4 fb0 = *reinterpret_cast<const f32x4*>(Bs + 8 * g), fb1 = *reinterpret_cast<const f32x4*>(Bs + 32 * LDK + 8 * g);
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa0[s], fb0[s], acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa0[s], fb1[s], acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa1[s], fb0[s], acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa1[s], fb1[s], acc[1][1], 0, 0, 0);
-      }
-    }
-    if (more) {
-      float* nxt = smem + ((c + 1) & 1) * BUF;
-      store_chunk(nxt, t, ra);
-      store_chunk(nxt + OPER, t, rb);
-    }
-    __syncthreads();
-  }
-}
-
 // tile `id` of the upper triangle of T x T tiles, rows ascending and ct >= rt ascending inside a row: row rt starts at rt T - rt (rt - 1) / 2
 __device__ __forceinline__ void triangle_tile(long id, int T, int& rt, int& ct) {
   const double b = 2.0 * T + 1.0;
@@ -677,7 +608,7 @@ __device__ __forceinline__ void triangle_tile(long id, int T, int& rt, int& ct) 
 }
 
 // ---- epilogue 6: the SUM of k over one tile of one subset pair.  grid (the tiles of a subset pair, S subsets); subset s takes rows ia[s][0 .. sa) of
-// bank A and ib[s][0 .. sb) of bank B (null: the identity).  Every lane adds its 64 elements in fp64 in for_each_k's order, the 256 lanes meet in
+// bank A and ib[s][0 .. sb) of bank B (null: the identity).  Every lane adds its 64 elements in fp64 in for_each_acc's order, the 256 lanes meet in
 // LDS by a fixed tree, one fp64 per tile goes to part[s][tile].  same (A is B, ia is ib): only the tiles with ct >= rt exist, an off-diagonal tile
 // is stored twice over (exact in fp64), and with same == 1 a diagonal tile leaves p == q out, by position.  No atomics; the order is fixed in
 // subset-local coordinates, so a gathered subset gives the bits of the same call on its materialised rows.
@@ -699,35 +630,25 @@ __global__ __launch_bounds__(256, 2) void ksum_partial_kernel(const float* __res
   const int* la = ia ? ia + (long)s * sa : nullptr;
   const int* lb = ib ? ib + (long)s * sb : nullptr;
   float* nas = smem + STAGE;
-  if (t < TM) {
-    const int r = min(a0 + t, sa - 1);
-    const int g = la ? min(max(la[r], 0), N - 1) : r;
-    nas[t] = (na && a0 + t < sa) ? na[g] : 0.f;
-  }
+  if (t < TM) nas[t] = (na && a0 + t < sa) ? na[gather_index(la, a0 + t, sa, N)] : 0.f;
   float nbs[2];
   {
     const int lane = t & 63, wc = (t >> 6) & 1;
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
-      const int c = b0 + wc * 64 + n * 32 + (lane & 31), r = min(c, sb - 1);
-      const int g = lb ? min(max(lb[r], 0), M - 1) : r;
-      nbs[n] = (nb && c < sb) ? nb[g] : 0.f;
+      const int c = b0 + wc * 64 + n * 32 + (lane & 31);
+      nbs[n] = (nb && c < sb) ? nb[gather_index(lb, c, sb, M)] : 0.f;
     }
   }
-  const float* pa[4];
-  const float* pb[4];
-  bool ina[4], inb[4];
-  gather_rows(a, N, la, sa, a0, D, t, pa, ina);
-  gather_rows(b, M, lb, sb, b0, D, t, pb, inb);
   f32x16 acc[2][2];
-  tile_dot_rows<V>(pa, ina, pb, inb, D, pivot, smem, acc);
+  tile_dot<V>(gather_rows(a, N, la, sa, a0, D, t), gather_rows(b, M, lb, sb, b0, D, t), D, pivot, smem, acc);
   const bool skip_diag = same == 1 && rt == ct;
   double sum = 0.0;
-  for_each_k(acc, kp, nas, nbs, [&](int il, int jl, float k) {
+  for_each_acc(acc, [&](int il, int jl, int n, float dot) {
     const bool in = a0 + il < sa && b0 + jl < sb && !(skip_diag && il == jl);
-    sum += in ? (double)k : 0.0;
+    sum += in ? (double)kernel_value(kp, nas[il], nbs[n], dot) : 0.0;
   });
-  double* red = reinterpret_cast<double*>(smem);      // (tile_dot_rows left with a barrier: the staging buffers are free)
+  double* red = reinterpret_cast<double*>(smem);      // (tile_dot left with a barrier: the staging buffers are free)
   red[t] = sum;
   __syncthreads();
   for (int o = 128; o > 0; o >>= 1) {
@@ -755,50 +676,37 @@ __global__ __launch_bounds__(256) void ksum_finish_kernel(const double* __restri
   }
 }
 
-// ---- epilogue 7: the matrix of k itself, sqdist_kernel's counterpart (tile_dot as it is; for tests and kernel_matrix())
-template <int V>
-__global__ __launch_bounds__(256) void kernel_matrix_kernel(const float* __restrict__ x, const float* __restrict__ nx, const float* __restrict__ y,
-                                                            const float* __restrict__ ny, const float* __restrict__ pivot, float* __restrict__ out, int N,
-                                                            int M, int D, int col_tiles, KernelParams kp) {
-  __shared__ __attribute__((aligned(16))) float smem[SMEM];
-  const int t = threadIdx.x;
-  const int rt = blockIdx.x / col_tiles, ct = blockIdx.x - rt * col_tiles;
-  const int a0 = rt * TM, b0 = ct * TM;
-  float* na = smem + STAGE;
-  if (t < TM) na[t] = (nx && a0 + t < N) ? nx[a0 + t] : 0.f;
-  f32x16 acc[2][2];
-  tile_dot<V>(x, N, a0, y, M, b0, D, pivot, smem, acc);
-  float nb[2] = {0.f, 0.f};
-  if (ny) column_norms(ny, M, b0, nb);
-  for_each_k(acc, kp, na, nb, [&](int il, int jl, float k) {
-    const int ig = a0 + il, jg = b0 + jl;
-    if (ig < N && jg < M) out[(long)ig * M + jg] = k;
-  });
+// the rules every descriptor of this unit shares, on the host, before any launch: the banks' sizes ...
+int bank_rules(const char* what, int N, int M, int D) {
+  MF_REQUIRE(N >= 1 && N < (1 << 24) && M >= 1 && M < (1 << 24), MF_EINVAL, "%s: N=%d M=%d (1 .. 2^24 - 1)", what, N, M);
+  MF_REQUIRE(D >= 1 && D <= 65536, MF_EINVAL, "%s: D=%d (1 .. 65536)", what, D);
+  return MF_OK;
 }
 
-// the descriptor's rules, on the host, before any launch
-int fidelity_rules(const MfFidelityDesc* d, const char* what) {
-  MF_REQUIRE(d != nullptr, MF_EINVAL, "%s: no descriptor", what);
-  MF_REQUIRE(d->N >= 1 && d->N < (1 << 24) && d->M >= 1 && d->M < (1 << 24), MF_EINVAL, "%s: N=%d M=%d (1 .. 2^24 - 1)", what, d->N, d->M);
-  MF_REQUIRE(d->D >= 1 && d->D <= 65536, MF_EINVAL, "%s: D=%d (1 .. 65536)", what, d->D);
-  MF_REQUIRE(d->knn >= 1 && d->knn <= MF_FIDELITY_LIST - 1, MF_EINVAL, "%s: knn=%d (1 .. %d)", what, d->knn, MF_FIDELITY_LIST - 1);
-  MF_REQUIRE(d->knn < d->N, MF_EINVAL, "%s: knn=%d needs more than %d rows", what, d->knn, d->N);
+// ... and, of an MfFidelityDesc, the splits and the same_bank flag
+int split_rules(const MfFidelityDesc* d, const char* what) {
   MF_REQUIRE(d->splits >= 1 && d->splits <= MF_FIDELITY_MAX_SPLITS, MF_EINVAL, "%s: splits=%d (1 .. %d)", what, d->splits, MF_FIDELITY_MAX_SPLITS);
   MF_REQUIRE((d->same_bank & ~1) == 0, MF_EINVAL, "%s: same_bank is 0 or 1", what);
   MF_REQUIRE(!d->same_bank || d->M == d->N, MF_EINVAL, "%s: same_bank with N=%d M=%d", what, d->N, d->M);
   return MF_OK;
 }
 
+// the rules of precision / recall (mf_feat_sqdist_f32, mf_knn_*, mf_manifold_partial / finish)
+int fidelity_rules(const MfFidelityDesc* d, const char* what) {
+  MF_REQUIRE(d != nullptr, MF_EINVAL, "%s: no descriptor", what);
+  if (const int rc = bank_rules(what, d->N, d->M, d->D)) return rc;
+  MF_REQUIRE(d->knn >= 1 && d->knn <= MF_FIDELITY_LIST - 1, MF_EINVAL, "%s: knn=%d (1 .. %d)", what, d->knn, MF_FIDELITY_LIST - 1);
+  MF_REQUIRE(d->knn < d->N, MF_EINVAL, "%s: knn=%d needs more than %d rows", what, d->knn, d->N);
+  return split_rules(d, what);
+}
+
 // the rules of the neighbour search and the counting launches (mf_nn_*, mf_pair_sqdist_f32, mf_manifold_count_*): knn is k, 1 .. 16, and may
 // equal the reference rows (one less with same_bank, where a row is not its own neighbour)
 int nn_rules(const MfFidelityDesc* d, const char* what) {
   MF_REQUIRE(d != nullptr, MF_EINVAL, "%s: no descriptor", what);
-  MF_REQUIRE(d->N >= 1 && d->N < (1 << 24) && d->M >= 1 && d->M < (1 << 24), MF_EINVAL, "%s: N=%d M=%d (1 .. 2^24 - 1)", what, d->N, d->M);
-  MF_REQUIRE(d->D >= 1 && d->D <= 65536, MF_EINVAL, "%s: D=%d (1 .. 65536)", what, d->D);
+  if (const int rc = bank_rules(what, d->N, d->M, d->D)) return rc;
   MF_REQUIRE(d->knn >= 1 && d->knn <= MF_FIDELITY_LIST, MF_EINVAL, "%s: k=%d (1 .. %d)", what, d->knn, MF_FIDELITY_LIST);
-  MF_REQUIRE(d->splits >= 1 && d->splits <= MF_FIDELITY_MAX_SPLITS, MF_EINVAL, "%s: splits=%d (1 .. %d)", what, d->splits, MF_FIDELITY_MAX_SPLITS);
-  MF_REQUIRE((d->same_bank & ~1) == 0, MF_EINVAL, "%s: same_bank is 0 or 1", what);
-  MF_REQUIRE(!d->same_bank || d->M == d->N, MF_EINVAL, "%s: same_bank with N=%d M=%d", what, d->N, d->M);
+  if (const int rc = split_rules(d, what)) return rc;
   MF_REQUIRE(d->knn <= d->N - d->same_bank, MF_EINVAL, "%s: k=%d of %d reference rows%s", what, d->knn, d->N, d->same_bank ? " (the row itself left out)" : "");
   return MF_OK;
 }
@@ -809,17 +717,21 @@ inline size_t count_bytes(const MfFidelityDesc* d) { return ((size_t)d->splits *
 inline size_t knn_bytes(const MfFidelityDesc* d) { return (size_t)d->splits * d->N * LIST * sizeof(float); }
 inline size_t manifold_bytes(const MfFidelityDesc* d) { return ((size_t)d->splits * d->M + 15) & ~(size_t)15; }
 
-inline bool by16(int D, std::initializer_list<const void*> ptrs) {
+// f(V) with V = 4 as a constant where every row of every bank can be loaded sixteen bytes at a time, V = 1 otherwise: the caller launches kernel<V>
+template <class F>
+inline void with_load_width(int D, std::initializer_list<const void*> ptrs, F f) {
   uintptr_t bits = 0;
   for (const void* p : ptrs) bits |= (uintptr_t)p;
-  return D % 4 == 0 && (bits & 15) == 0;
+  if (D % 4 == 0 && (bits & 15) == 0)
+    f(std::integral_constant<int, 4>{});
+  else
+    f(std::integral_constant<int, 1>{});
 }
 
 // the rules of the kernel sums and the kernel matrix (mf_ksum_*, mf_feat_kernel_f32)
 int ksum_rules(const MfKernelSumDesc* d, const char* what) {
   MF_REQUIRE(d != nullptr, MF_EINVAL, "%s: no descriptor", what);
-  MF_REQUIRE(d->N >= 1 && d->N < (1 << 24) && d->M >= 1 && d->M < (1 << 24), MF_EINVAL, "%s: N=%d M=%d (1 .. 2^24 - 1)", what, d->N, d->M);
-  MF_REQUIRE(d->D >= 1 && d->D <= 65536, MF_EINVAL, "%s: D=%d (1 .. 65536)", what, d->D);
+  if (const int rc = bank_rules(what, d->N, d->M, d->D)) return rc;
   MF_REQUIRE(d->S >= 1 && d->S <= 65535, MF_EINVAL, "%s: S=%d (1 .. 65535)", what, d->S);
   MF_REQUIRE(d->sa >= 1 && d->sa <= d->N && d->sb >= 1 && d->sb <= d->M, MF_EINVAL, "%s: sa=%d sb=%d (1 .. N=%d, 1 .. M=%d)", what, d->sa, d->sb, d->N,
              d->M);
@@ -880,10 +792,10 @@ int mf_feat_sqdist_f32(const float* x, const float* nx, const float* y, const fl
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(MF_FAM_MISC, s, 2.0 * desc->N * desc->M * desc->D, 4.0 * ((double)desc->N * desc->M + ((double)desc->N + desc->M) * desc->D));
   const dim3 grid((unsigned)(row_tiles * col_tiles));
-  if (by16(desc->D, {x, y, pivot}))
-    MF_LAUNCH(sqdist_kernel<4>, grid, dim3(256), 0, s, x, nx, y, ny, pivot, out, desc->N, desc->M, desc->D, (int)col_tiles, desc->same_bank);
-  else
-    MF_LAUNCH(sqdist_kernel<1>, grid, dim3(256), 0, s, x, nx, y, ny, pivot, out, desc->N, desc->M, desc->D, (int)col_tiles, desc->same_bank);
+  with_load_width(desc->D, {x, y, pivot}, [&](auto v) {
+    MF_LAUNCH(sqdist_kernel<decltype(v)::value>, grid, dim3(256), 0, s, x, nx, y, ny, pivot, out, desc->N, desc->M, desc->D, (int)col_tiles,
+              desc->same_bank);
+  });
   return check_launch("feat_sqdist");
 }
 
@@ -897,10 +809,9 @@ int mf_knn_partial_f32(const float* x, const float* nx, const float* pivot, void
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(MF_FAM_MISC, s, 2.0 * desc->N * desc->N * desc->D, 4.0 * desc->N * desc->D);
   const dim3 grid(cdiv(desc->N, TM), desc->splits);
-  if (by16(desc->D, {x, pivot}))
-    MF_LAUNCH(knn_partial_kernel<4>, grid, dim3(256), 0, s, x, nx, pivot, (float*)workspace, desc->N, desc->D, desc->splits);
-  else
-    MF_LAUNCH(knn_partial_kernel<1>, grid, dim3(256), 0, s, x, nx, pivot, (float*)workspace, desc->N, desc->D, desc->splits);
+  with_load_width(desc->D, {x, pivot}, [&](auto v) {
+    MF_LAUNCH(knn_partial_kernel<decltype(v)::value>, grid, dim3(256), 0, s, x, nx, pivot, (float*)workspace, desc->N, desc->D, desc->splits);
+  });
   return check_launch("knn_partial");
 }
 
@@ -924,12 +835,10 @@ int mf_manifold_partial_f32(const float* ref, const float* nref, const float* ra
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(MF_FAM_MISC, s, 2.0 * desc->N * desc->M * desc->D, 4.0 * ((double)desc->N + desc->M) * desc->D);
   const dim3 grid(cdiv(desc->M, TM), desc->splits);
-  if (by16(desc->D, {ref, query, pivot}))
-    MF_LAUNCH(manifold_partial_kernel<4>, grid, dim3(256), 0, s, ref, nref, radii_sq, query, nquery, pivot, (uint8_t*)workspace, desc->N, desc->M, desc->D,
-              desc->splits);
-  else
-    MF_LAUNCH(manifold_partial_kernel<1>, grid, dim3(256), 0, s, ref, nref, radii_sq, query, nquery, pivot, (uint8_t*)workspace, desc->N, desc->M, desc->D,
-              desc->splits);
+  with_load_width(desc->D, {ref, query, pivot}, [&](auto v) {
+    MF_LAUNCH(manifold_partial_kernel<decltype(v)::value>, grid, dim3(256), 0, s, ref, nref, radii_sq, query, nquery, pivot, (uint8_t*)workspace, desc->N,
+              desc->M, desc->D, desc->splits);
+  });
   return check_launch("manifold_partial");
 }
 
@@ -961,12 +870,10 @@ int mf_nn_partial_f32(const float* query, const float* nquery, const float* ref,
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(MF_FAM_MISC, s, 2.0 * desc->N * desc->M * desc->D, 4.0 * ((double)desc->N + desc->M) * desc->D);
   const dim3 grid(cdiv(desc->M, TM), desc->splits);
-  if (by16(desc->D, {query, ref, pivot}))
-    MF_LAUNCH(nn_partial_kernel<4>, grid, dim3(256), 0, s, query, nquery, ref, nref, pivot, (nnkey*)workspace, desc->N, desc->M, desc->D, desc->splits,
-              desc->same_bank);
-  else
-    MF_LAUNCH(nn_partial_kernel<1>, grid, dim3(256), 0, s, query, nquery, ref, nref, pivot, (nnkey*)workspace, desc->N, desc->M, desc->D, desc->splits,
-              desc->same_bank);
+  with_load_width(desc->D, {query, ref, pivot}, [&](auto v) {
+    MF_LAUNCH(nn_partial_kernel<decltype(v)::value>, grid, dim3(256), 0, s, query, nquery, ref, nref, pivot, (nnkey*)workspace, desc->N, desc->M, desc->D,
+              desc->splits, desc->same_bank);
+  });
   return check_launch("nn_partial");
 }
 
@@ -1003,12 +910,10 @@ int mf_manifold_count_partial_f32(const float* ref, const float* nref, const flo
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(MF_FAM_MISC, s, 2.0 * desc->N * desc->M * desc->D, 4.0 * ((double)desc->N + desc->M) * desc->D);
   const dim3 grid(cdiv(desc->M, TM), desc->splits);
-  if (by16(desc->D, {ref, query, pivot}))
-    MF_LAUNCH(manifold_count_partial_kernel<4>, grid, dim3(256), 0, s, ref, nref, radii_sq, query, nquery, pivot, (int*)workspace, desc->N, desc->M,
-              desc->D, desc->splits);
-  else
-    MF_LAUNCH(manifold_count_partial_kernel<1>, grid, dim3(256), 0, s, ref, nref, radii_sq, query, nquery, pivot, (int*)workspace, desc->N, desc->M,
-              desc->D, desc->splits);
+  with_load_width(desc->D, {ref, query, pivot}, [&](auto v) {
+    MF_LAUNCH(manifold_count_partial_kernel<decltype(v)::value>, grid, dim3(256), 0, s, ref, nref, radii_sq, query, nquery, pivot, (int*)workspace,
+              desc->N, desc->M, desc->D, desc->splits);
+  });
   return check_launch("manifold_count_partial");
 }
 
@@ -1049,12 +954,10 @@ int mf_ksum_partial_f32(const float* a, const float* na, const int32_t* ia, cons
   ProfScope ps(MF_FAM_MISC, s, 2.0 * pairs * desc->D, 4.0 * desc->S * ((double)desc->sa + desc->sb) * desc->D);
   const dim3 grid((unsigned)tiles, (unsigned)desc->S);
   const int col_tiles = cdiv(desc->sb, TM);
-  if (by16(desc->D, {a, b, pivot}))
-    MF_LAUNCH(ksum_partial_kernel<4>, grid, dim3(256), 0, s, a, na, ia, b, nb, ib, pivot, (double*)workspace, desc->N, desc->M, desc->D, desc->sa, desc->sb,
-              col_tiles, (int)tiles, desc->same_bank, kernel_params(desc));
-  else
-    MF_LAUNCH(ksum_partial_kernel<1>, grid, dim3(256), 0, s, a, na, ia, b, nb, ib, pivot, (double*)workspace, desc->N, desc->M, desc->D, desc->sa, desc->sb,
-              col_tiles, (int)tiles, desc->same_bank, kernel_params(desc));
+  with_load_width(desc->D, {a, b, pivot}, [&](auto v) {
+    MF_LAUNCH(ksum_partial_kernel<decltype(v)::value>, grid, dim3(256), 0, s, a, na, ia, b, nb, ib, pivot, (double*)workspace, desc->N, desc->M, desc->D,
+              desc->sa, desc->sb, col_tiles, (int)tiles, desc->same_bank, kernel_params(desc));
+  });
   return check_launch("ksum_partial");
 }
 
@@ -1082,10 +985,10 @@ int mf_feat_kernel_f32(const float* x, const float* nx, const float* y, const fl
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(MF_FAM_MISC, s, 2.0 * desc->N * desc->M * desc->D, 4.0 * ((double)desc->N * desc->M + ((double)desc->N + desc->M) * desc->D));
   const dim3 grid((unsigned)(row_tiles * col_tiles));
-  if (by16(desc->D, {x, y, pivot}))
-    MF_LAUNCH(kernel_matrix_kernel<4>, grid, dim3(256), 0, s, x, nx, y, ny, pivot, out, desc->N, desc->M, desc->D, (int)col_tiles, kernel_params(desc));
-  else
-    MF_LAUNCH(kernel_matrix_kernel<1>, grid, dim3(256), 0, s, x, nx, y, ny, pivot, out, desc->N, desc->M, desc->D, (int)col_tiles, kernel_params(desc));
+  with_load_width(desc->D, {x, y, pivot}, [&](auto v) {
+    MF_LAUNCH(kernel_matrix_kernel<decltype(v)::value>, grid, dim3(256), 0, s, x, nx, y, ny, pivot, out, desc->N, desc->M, desc->D, (int)col_tiles,
+              kernel_params(desc));
+  });
   return check_launch("feat_kernel");
 }
 

@@ -48,8 +48,10 @@ def kernel_resources():
     out = []
     for r in rows:
         name = re.sub(r"^_ZN\d+_GLOBAL__N_1\d+", "", r.get("name", "?"))
-        tmpl = re.search(r"ILi(\d+)E", name)
-        short = re.match(r"[a-z0-9_]+", name).group(0) + (f"<V={tmpl.group(1)}>" if tmpl else "")
+        # every template argument of the instantiation, integers and bools (I Li4E Lb1E E): the first is the load width V of every kernel template here
+        tmpl = re.match(r"[a-z0-9_]+I((?:L[ib]\d+E)+)E", name)
+        args = [a[1:] if a[0] == "i" else ("false", "true")[int(a[1:])] for a in re.findall(r"L([ib]\d+)E", tmpl.group(1))] if tmpl else []
+        short = re.match(r"[a-z0-9_]+", name).group(0) + (f"<V={', '.join(args)}>" if args else "")
         out.append(f"{short:32s} vgpr {r.get('vgpr_count'):>3s} (agpr {r.get('agpr_count', '0'):>2s})  sgpr {r.get('sgpr_count'):>3s}  "
                    f"lds {r.get('group_segment_fixed_size'):>6s} B  scratch {r.get('private_segment_fixed_size')} B")
     return out

@@ -126,6 +126,27 @@ def test_radii_are_the_order_statistic_of_the_kernels_own_rows(dev, knn, splits)
     assert torch.equal(M.knn_radii(x, knn, squared=True), got)               # the planner's own S, the pivot of x
 
 
+@pytest.fixture(scope="module")
+def one_bank(dev):
+    """[257, 36]: two full tiles and one row; D = 36 takes the sixteen-byte path with a partial chunk.  -> (x, the same values one float off)"""
+    x = _random_banks(257, 1, 36, seed=23)[0].to(dev)
+    return x, _misaligned(x)
+
+
+@pytest.mark.parametrize("splits", [1, 2, 16])
+@pytest.mark.parametrize("knn", [1, 3, 15])
+def test_radii_are_the_neighbour_search_without_the_row_itself(one_bank, knn, splits):
+    """the value list and the key list run one skeleton on one tile: the row itself is the value list's exact 0 and every other d2 >= 0, so the
+    (knn + 1)-th smallest with the row equals the knn-th nearest neighbour without it, bit for bit, on either load path"""
+    for x in one_bank:
+        pivot = K.feat_colmean(x)
+        nx = K.feat_norms(x, pivot)
+        got = K.knn_radii_sq(x, nx, pivot, knn, splits)
+        want = K.nn_search(x, nx, x, nx, pivot, k=knn, splits=splits, exclude_self=True)[0][:, knn - 1]
+        assert torch.equal(got, want), (knn, splits, x.data_ptr() % 16)
+    assert torch.equal(got, K.knn_radii_sq(one_bank[0], nx, pivot, knn, splits))                    # (and the two paths agree)
+
+
 def test_radii_of_a_bank_with_two_identical_rows(dev):
     x = FC.case("c2")[0].clone()
     x[77] = x[5]

@@ -273,6 +273,20 @@ def test_counts_and_coverage_are_the_comparison_on_the_kernels_own_matrix(dev, n
     assert torch.equal(nearest < r2, covered)
 
 
+@pytest.mark.parametrize("splits", [1, 2, 16])
+def test_a_hit_is_a_nonzero_count(dev, splits):
+    """the flag and the count are one kernel body over one tile: query j is inside some ball exactly when it is inside at least one"""
+    like, wide = _random_banks(257 + 65, 65, 36, seed=29)
+    ref, query = like[:257].to(dev), torch.cat([like[257:], wide]).to(dev)    # [257, 36]: 3 reference tiles, the last of one row; [130, 36]: 2 query
+    p = K.feat_colmean(ref)                                                    # tiles, half of them drawn like the bank, half wider: in fp64 52 inside
+    nr, nq = K.feat_norms(ref, p), K.feat_norms(query, p)
+    r2 = M.knn_radii(ref, NC.KNN_DC, pivot=p, squared=True)
+    hit, hits = K.manifold_hits(ref, nr, r2, query, nq, p, splits)
+    count, _ = K.manifold_counts(ref, nr, r2, query, nq, p, splits)
+    assert torch.equal(hit.bool(), count > 0) and int(hits) == int((count != 0).sum())
+    assert 0 < int(hits) < 130                                                 # (both answers occur)
+
+
 @pytest.mark.parametrize("name", NC.ALL + ("m4-", "m5-"))
 def test_density_coverage_against_fp64_within_the_ambiguous_pairs(dev, name):
     fake, real, p = _banks(name)
