@@ -576,7 +576,8 @@ int mf_counter_add_i32(int32_t* counter, int32_t inc, void* stream);
 /* Per-row scaled combination: out[b][:] = clamp?((a[b]*x[b][:] + c[b]*y[b][:]) / d[b]); y, a, c, d optional (NULL).
  * The scheduler's tensor-level API with a timestep PER ROW (gaussian_scheduler.py:61-77 estimate_x_t, :104-107, :119-131)
  * and the lerp of DiffusionPipeline.interpolate (diffusion_pipeline.py:329); coefficient rows are gathered on the host like
- * `extract()` (scheduler_base.py:43-46).  Bit-exact vs ATen's elementwise chain. */
+ * `extract()` (scheduler_base.py:43-46).  Bit-exact vs ATen's elementwise chain.  Every clamp of the library that restates a torch.clamp (this one,
+ * clip_x0 of the scheduler / solver steps, the logvar of mf_diag_gaussian_*) keeps a NaN like torch.clamp does; +-Inf go to the nearer limit. */
 int mf_rows_axpby_f32(const float* x, const float* y, const float* a, const float* c, const float* d, float* out, int B,
                       int64_t per_row, int do_clamp, float lo, float hi, void* stream);
 

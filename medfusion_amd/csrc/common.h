@@ -92,6 +92,10 @@ static inline bool first_use_on_device(DeviceOnce& o) {
   return true;
 }
 
+// torch.clamp(v, lo, hi): a NaN stays a NaN (fminf / fmaxf return the OTHER operand for a NaN, so the bare pair would hand back `lo` -- the defect
+// csrc/split_f16.h describes for the pair split); +-Inf and every finite value keep the bits of fminf(fmaxf(v, lo), hi)
+__device__ __forceinline__ float clamp_keep_nan(float v, float lo, float hi) { return v != v ? v : fminf(fmaxf(v, lo), hi); }
+
 // MONAI Swish: x * sigmoid(1.0 * x)  (conv_blocks.py act)
 __device__ __forceinline__ float swish(float x) { return x / (1.0f + __expf(-x)); }
 // accurate variant used where parity margins are tight (embedding MLPs): expf, IEEE divide

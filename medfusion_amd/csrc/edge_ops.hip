@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void rows_axpby_kernel(const float* __restrict
       v = v + w;
     }
     if (d) v = v / d[b];
-    if (do_clamp) v = fminf(fmaxf(v, lo), hi);
+    if (do_clamp) v = clamp_keep_nan(v, lo, hi);
     out[i] = v;
   }
 }

@@ -27,10 +27,10 @@ __device__ __forceinline__ Estimate estimate_elem(bool cfg, float g, int objecti
     const float p1 = sqrt_recip_ac * xt;
     const float p2 = sqrt_recipm1_ac * pred;
     x0 = p1 - p2;
-    if (clip_x0) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    if (clip_x0) x0 = clamp_keep_nan(x0, -1.0f, 1.0f);
     xT = pred;
   } else {  // 'x_0': diffusion_pipeline.py:264-267, gaussian_scheduler.py:127-131
-    x0 = clip_x0 ? fminf(fmaxf(pred, -1.0f), 1.0f) : pred;
+    x0 = clip_x0 ? clamp_keep_nan(pred, -1.0f, 1.0f) : pred;
     const float p1 = sqrt_recip_ac * xt;
     const float df = p1 - x0;
     xT = df / sqrt_recipm1_ac;

@@ -149,7 +149,7 @@ __global__ void diag_gaussian_kernel(const float* __restrict__ mom, const float*
   const long n = i / per, r = i - n * per;
   const float mean = mom[n * 2 * per + r];
   float logvar = mom[n * 2 * per + per + r];
-  logvar = fminf(fmaxf(logvar, -30.0f), 20.0f);
+  logvar = clamp_keep_nan(logvar, -30.0f, 20.0f);
   const float hl = 0.5f * logvar;
   const float sd = expf(hl);
   const float sn = sd * noise[i];
@@ -165,7 +165,7 @@ __global__ __launch_bounds__(1024) void diag_gaussian_kl_kernel(const float* __r
   for (long i = threadIdx.x; i < total; i += 1024) {
     const long n = i / per, r = i - n * per;
     const float mean = mom[n * 2 * per + r];
-    const float logvar = fminf(fmaxf(mom[n * 2 * per + per + r], -30.0f), 20.0f);
+    const float logvar = clamp_keep_nan(mom[n * 2 * per + per + r], -30.0f, 20.0f);
     acc += (double)(mean * mean) + (double)expf(logvar) - 1.0 - (double)logvar;
   }
 #pragma unroll

@@ -266,6 +266,27 @@ def _f32(what: str, *ts):
             raise RuntimeError(f"medfusion_amd: {what}: fp32 tensors only, got {t.dtype}")
 
 
+_DTYPE_NAMES = {torch.float32: "fp32", torch.int64: "int64", torch.int32: "int32"}
+
+
+def _dense(what: str, name: str, t, dtype=torch.float32, shape=None, dim: Optional[int] = None, contiguous: bool = True, written: bool = False) -> None:
+    """`t` is read or written by raw pointer as `dtype`: refuse another dtype, a tensor that exists only as fp16 pairs, a strided view
+    (contiguous=False: the wrapper copies) and -- where given -- another rank or shape.  Pure host logic: the check_* functions below are built
+    from it and take CPU tensors as well (tests/test_edge_cpu.py); every wrapper calls its check before _gpu and before any launch."""
+    if not isinstance(t, torch.Tensor):
+        raise RuntimeError(f"medfusion_amd: {what}: {name} must be a tensor, got {type(t).__name__}")
+    if t.dtype != dtype:
+        raise RuntimeError(f"medfusion_amd: {what}: {name} must be {_DTYPE_NAMES[dtype]}, got {t.dtype}")
+    if dtype == torch.float32 and not written:      # (written: an output that is only written may be pairs-only storage; drop_split hands it to the writer)
+        _need_f32(t)
+    if contiguous and not t.is_contiguous():
+        raise RuntimeError(f"medfusion_amd: {what}: {name} must be contiguous (shape {tuple(t.shape)}, strides {t.stride()})")
+    if dim is not None and t.dim() != dim:
+        raise RuntimeError(f"medfusion_amd: {what}: {name} must have {dim} dimensions, got shape {tuple(t.shape)}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"medfusion_amd: {what}: {name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+
+
 # every mirror attribute a producer may attach (_attach) and a writer must drop (drop_split).  Not mirrors, and left alone by drop_split: `_mf_ver` (the
 # stamp; _fresh clears it), `_mf_wino_site` / `_mf_wino_site_f32` (where to report a wanted transform: they describe the producer, not the values);
 # `_mf_pairs_only` is a flag of the storage that drop_split clears by its own rule.  A new mirror kind goes HERE (tests/test_host_logic_cpu.py checks)
@@ -539,9 +560,19 @@ def _conv_call(ops, c, ws, sync, dev, partial=None, G: int = 0, measured: bool =
     return call, y
 
 
+def check_pack_nchw_pairs(x_nchw, cp: int) -> None:
+    _dense("pack_nchw_pairs", "x", x_nchw, dim=4, contiguous=False)
+    n, c, h, w = x_nchw.shape
+    if cp % 32 or not 0 < c <= cp or n < 1 or h * w < 1:
+        raise RuntimeError(f"medfusion_amd: pack_nchw_pairs: x {tuple(x_nchw.shape)} needs 1 <= C <= cp = {cp}, cp a multiple of 32")
+    if c * h * w > 1 << 18:
+        raise RuntimeError(f"medfusion_amd: pack_nchw_pairs: one workgroup per sample -- at most 2^18 values per sample, got {c * h * w}")
+
+
 def pack_nchw_pairs(x_nchw: torch.Tensor, cp: int = 32) -> torch.Tensor:
     """NCHW fp32 [N, C, H, W] (C <= cp) -> an NHWC [N, H, W, cp] tensor that exists ONLY as fp16 pairs (channels C.. zero), scaled per sample by
     the max |x| the same launch measures (mf_pack_nchw_pairs_f32): the operand form of the network input"""
+    check_pack_nchw_pairs(x_nchw, cp)
     _gpu(x_nchw)
     x = x_nchw.contiguous()
     n, c, h, w = x.shape
@@ -1032,8 +1063,18 @@ def sinusoidal(t: torch.Tensor, dim: int, max_period: float = 10000.0, shift: fl
     return out
 
 
+def check_learned_sinusoidal(t, weights, emb_dim: int) -> None:
+    """t [B] of any real dtype (the wrapper converts it); weights: the emb_dim // 2 learned frequencies, fp32"""
+    if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.shape[0] < 1 or t.is_complex() or t.dtype == torch.bool:
+        raise RuntimeError("medfusion_amd: learned_sinusoidal: t must be a non-empty [B] tensor of timesteps")
+    if int(emb_dim) < 2:
+        raise RuntimeError(f"medfusion_amd: learned_sinusoidal: emb_dim = {emb_dim} must be >= 2")
+    _dense("learned_sinusoidal", "weights", weights, shape=(int(emb_dim) // 2,), contiguous=False)
+
+
 def learned_sinusoidal(t: torch.Tensor, weights: torch.Tensor, emb_dim: int) -> torch.Tensor:
     """LearnedSinusoidalPosEmb.forward (time_embedder.py:42-49): [B] -> [B, 1 + 2 (emb_dim // 2) + (emb_dim & 1)]"""
+    check_learned_sinusoidal(t, weights, emb_dim)
     _gpu(t, weights)
     t = t.to(torch.float32).contiguous()
     w = weights.detach().contiguous()
@@ -1042,7 +1083,20 @@ def learned_sinusoidal(t: torch.Tensor, weights: torch.Tensor, emb_dim: int) -> 
     return out
 
 
+def check_embedding_add(table, idx, io) -> None:
+    """io [B, D] += table[idx]: table [rows, D] and io fp32, contiguous; idx [B] int64 or int32 (the wrapper converts and copies it)"""
+    _dense("embedding_add", "table", table, dim=2)
+    _dense("embedding_add", "io", io, dim=2)
+    if io.shape[1] != table.shape[1] or io.shape[0] < 1 or table.shape[0] < 1 or table.shape[1] < 1:
+        raise RuntimeError(f"medfusion_amd: embedding_add: io {tuple(io.shape)} must be [B, D] for the table {tuple(table.shape)} = [rows, D]")
+    if not isinstance(idx, torch.Tensor) or idx.dtype not in (torch.int64, torch.int32):
+        raise RuntimeError(f"medfusion_amd: embedding_add: idx must be int64 (or int32), got {getattr(idx, 'dtype', type(idx).__name__)}")
+    if idx.numel() != io.shape[0]:
+        raise RuntimeError(f"medfusion_amd: embedding_add: idx must hold one index per row of io = {io.shape[0]}, got shape {tuple(idx.shape)}")
+
+
 def embedding_add(table: torch.Tensor, idx: torch.Tensor, io: torch.Tensor) -> torch.Tensor:
+    check_embedding_add(table, idx, io)
     _gpu(table, idx, io)
     idx = idx.to(torch.int64).contiguous()
     drop_split(io)
@@ -1084,6 +1138,7 @@ def rows_axpby(x: torch.Tensor, a: Optional[torch.Tensor] = None, y: Optional[to
 
 def image_to_uint8(x_nchw: torch.Tensor, normalize_each: bool = False) -> torch.Tensor:
     """[N,C,H,W] float in ~[-1,1] -> [N,H,W,C] uint8 on the device (mode 0: sample_dataset.py; mode 1: sample.py + save_image)."""
+    _dense("image_to_uint8", "x", x_nchw, dim=4, contiguous=False)
     _gpu(x_nchw)
     x = x_nchw.contiguous()
     n, c, h, w = x.shape
@@ -1623,11 +1678,33 @@ def absdiff_mean_c(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def check_gather_step_rows(tables, step, cols) -> None:
+    """tables: one to three contiguous fp32 [S, NCOL, L_i] that share S and NCOL; cols [B] int64, contiguous; step: a host int in [0, S) or a
+    device int32 counter (read on the device: its value cannot be checked here)"""
+    what = "gather_step_rows"
+    if not 1 <= len(tables) <= 3:
+        raise RuntimeError(f"medfusion_amd: {what}: one to three tables, got {len(tables)}")
+    for i, t in enumerate(tables):
+        _dense(what, f"table {i}", t, dim=3)
+        if t.numel() == 0 or tuple(t.shape[:2]) != tuple(tables[0].shape[:2]):
+            raise RuntimeError(f"medfusion_amd: {what}: table {i} {tuple(t.shape)} must be a non-empty [S, NCOL, L] with the [S, NCOL] of table 0 {tuple(tables[0].shape)}")
+    _dense(what, "cols", cols, dtype=torch.int64, dim=1)
+    if cols.shape[0] < 1:
+        raise RuntimeError(f"medfusion_amd: {what}: cols must have shape [B], B >= 1")
+    if isinstance(step, torch.Tensor):
+        _dense(what, "the device step", step, dtype=torch.int32)
+        if step.numel() < 1:
+            raise RuntimeError(f"medfusion_amd: {what}: the device step is empty")
+    elif isinstance(step, bool) or not hasattr(step, "__index__") or not 0 <= int(step) < tables[0].shape[0]:
+        raise RuntimeError(f"medfusion_amd: {what}: host step {step!r} is outside [0, {tables[0].shape[0]}): the table has that many steps")
+
+
 def gather_step_rows_multi(tables, step, cols: torch.Tensor):
     """gather_step_rows for up to three [S, NCOL, L_i] tables that share `cols` and the step, in ONE launch -> list of [B, L_i]"""
+    tables = list(tables)
+    check_gather_step_rows(tables, step, cols)
     _gpu(cols, *tables)
     n = len(tables)
-    assert 1 <= n <= 3 and all(t.is_contiguous() and t.shape[:2] == tables[0].shape[:2] for t in tables) and cols.dtype == torch.int64 and cols.is_contiguous()
     B, ncol = cols.shape[0], tables[0].shape[1]
     outs = [torch.empty((B, t.shape[2]), dtype=torch.float32, device=t.device) for t in tables]
     tp = (L.c_fp * n)(*[t.data_ptr() for t in tables])
@@ -1641,9 +1718,9 @@ def gather_step_rows_multi(tables, step, cols: torch.Tensor):
 
 def gather_step_rows(table: torch.Tensor, step, cols: torch.Tensor) -> torch.Tensor:
     """table [S, NCOL, L] fp32, cols [B] int64 -> [B, L] = table[step, cols[b]]; `step`: a host int or a device int32 counter (graph replay)"""
+    check_gather_step_rows([table], step, cols)
     _gpu(table, cols)
     s_, ncol, ln = table.shape
-    assert table.is_contiguous() and cols.dtype == torch.int64 and cols.is_contiguous()
     out = torch.empty((cols.shape[0], ln), dtype=torch.float32, device=table.device)
     dev_step = isinstance(step, torch.Tensor)
     rc = L.load().mf_gather_step_rows_f32(table.data_ptr(), cols.data_ptr(), step.data_ptr() if dev_step else None, 0 if dev_step else int(step), ncol, ln,
@@ -1652,7 +1729,18 @@ def gather_step_rows(table: torch.Tensor, step, cols: torch.Tensor) -> torch.Ten
     return out
 
 
+def check_broadcast_from_table(table, step_dev, out) -> None:
+    """out [B] fp32 <- table[*step_dev]: table [S] fp32, step_dev a device int32 counter"""
+    what = "broadcast_from_table"
+    _dense(what, "table", table, dim=1)
+    _dense(what, "the device step", step_dev, dtype=torch.int32)
+    _dense(what, "out", out, dim=1, written=True)
+    if table.numel() < 1 or step_dev.numel() < 1 or out.numel() < 1:
+        raise RuntimeError(f"medfusion_amd: {what}: table {tuple(table.shape)}, step {tuple(step_dev.shape)} and out {tuple(out.shape)} must be non-empty")
+
+
 def broadcast_from_table(table: torch.Tensor, step_dev: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    check_broadcast_from_table(table, step_dev, out)
     _gpu(table, step_dev, out)
     drop_split(out)
     L.check(L.load().mf_broadcast_from_table_f32(table.data_ptr(), step_dev.data_ptr(), 0, out.data_ptr(), out.numel(), stream()), "mf_broadcast_from_table_f32")
@@ -1702,9 +1790,68 @@ def geglu(h: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def check_add(a, b, out=None) -> None:
+    """out = a + b elementwise: three contiguous fp32 tensors of one shape (out may be a or b)"""
+    _dense("add", "a", a)
+    _dense("add", "b", b, shape=a.shape)
+    if out is not None:
+        _dense("add", "out", out, shape=a.shape, written=out is not a and out is not b)
+    if a.numel() < 1:
+        raise RuntimeError("medfusion_amd: add: empty tensors")
+
+
+def check_layout(what: str, x, copies: bool) -> None:
+    """a 4-D fp32 tensor with at most 65535 samples (the sample index is blockIdx.z); copies=False: the wrapper reads it in place"""
+    _dense(what, "x", x, dim=4, contiguous=not copies)
+    if x.numel() < 1 or x.shape[0] > 65535:
+        raise RuntimeError(f"medfusion_amd: {what}: x {tuple(x.shape)} must be non-empty with N <= 65535 (one grid plane per sample)")
+
+
+def check_avgpool2d(x, k: int, stride: int, pad: int):
+    """x [N, H, W, C] fp32, C % 4 == 0; nn.AvgPool2d's own rule 2 pad <= k -> (Ho, Wo), both >= 1"""
+    _dense("avgpool2d", "x", x, dim=4, contiguous=False)
+    n, h, w, c = x.shape
+    if min(n, h, w, c) < 1 or c % 4:
+        raise RuntimeError(f"medfusion_amd: avgpool2d: x {tuple(x.shape)} must be a non-empty [N, H, W, C] with C % 4 == 0")
+    if k < 1 or stride < 1 or pad < 0 or 2 * pad > k:
+        raise RuntimeError(f"medfusion_amd: avgpool2d: kernel {k}, stride {stride}, pad {pad}: needs k >= 1, stride >= 1, 0 <= 2 pad <= k")
+    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    if ho < 1 or wo < 1:
+        raise RuntimeError(f"medfusion_amd: avgpool2d: x {tuple(x.shape)} with kernel {k}, stride {stride}, pad {pad} has an empty output")
+    return ho, wo
+
+
+def check_upsample_nearest2x(x) -> None:
+    _dense("upsample_nearest2x", "x", x, dim=4, contiguous=False)
+    if x.numel() < 1 or x.shape[3] % 4:
+        raise RuntimeError(f"medfusion_amd: upsample_nearest2x: x {tuple(x.shape)} must be a non-empty [N, H, W, C] with C % 4 == 0")
+
+
+def check_pixel_shuffle_pair(what: str, x, y, unshuffle: bool) -> None:
+    """x fp32 [N, H, W, C] (the wrapper copies a strided one); y fp32, contiguous (written in place), of the shuffled shape"""
+    _dense(what, "x", x, dim=4, contiguous=False)
+    n, h, w, c = x.shape
+    ok = x.numel() > 0 and ((h % 2 == 0 and w % 2 == 0) if unshuffle else c % 4 == 0)
+    want = (n, h // 2, w // 2, 4 * c) if unshuffle else (n, 2 * h, 2 * w, c // 4)
+    if not ok or not isinstance(y, torch.Tensor) or tuple(y.shape) != want:
+        raise RuntimeError(f"medfusion_amd: {what}: x {tuple(x.shape)} does not {'unshuffle' if unshuffle else 'shuffle'} onto y {tuple(getattr(y, 'shape', ()))}")
+    _dense(what, "y", y)
+
+
+def check_diag_gaussian(what: str, moments, noise=None):
+    """moments [N, 2C, H, W] fp32 (mean | logvar); noise, where the op takes one: [N, C, H, W] fp32; both contiguous -> (N, C, H W)"""
+    _dense(what, "moments", moments, dim=4, contiguous=noise is not None)
+    n, c2, h, w = moments.shape
+    if moments.numel() < 1 or c2 % 2:
+        raise RuntimeError(f"medfusion_amd: {what}: moments {tuple(moments.shape)} must be a non-empty [N, 2 C, H, W]")
+    if noise is not None:
+        _dense(what, "noise", noise, shape=(n, c2 // 2, h, w))
+    return n, c2 // 2, h * w
+
+
 def add(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    _gpu(a, b)
-    _need_f32(a, b)
+    check_add(a, b, out)
+    _gpu(a, b, out)
     if out is None:
         out = torch.empty_like(a)
     else:
@@ -1714,6 +1861,7 @@ def add(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) ->
 
 
 def nchw_to_nhwc(x: torch.Tensor) -> torch.Tensor:
+    check_layout("nchw_to_nhwc", x, copies=True)
     _gpu(x)
     n, c, h, w = x.shape
     x = x.contiguous()
@@ -1723,8 +1871,8 @@ def nchw_to_nhwc(x: torch.Tensor) -> torch.Tensor:
 
 
 def nhwc_to_nchw(x: torch.Tensor) -> torch.Tensor:
+    check_layout("nhwc_to_nchw", x, copies=False)
     _gpu(x)
-    _need_f32(x)
     n, h, w, c = x.shape
     out = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
     L.check(L.load().mf_nhwc_to_nchw_f32(x.data_ptr(), out.data_ptr(), n, c, h, w, stream()), "mf_nhwc_to_nchw_f32")
@@ -1733,10 +1881,9 @@ def nhwc_to_nchw(x: torch.Tensor) -> torch.Tensor:
 
 def avgpool2d(x: torch.Tensor, k: int, stride: int, pad: int) -> torch.Tensor:
     """nn.AvgPool2d(k, stride, pad) on NHWC (count_include_pad like torch's default)"""
+    ho, wo = check_avgpool2d(x, k, stride, pad)
     _gpu(x)
-    _need_f32(x)
     n, h, w, c = x.shape
-    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
     out = torch.empty((n, ho, wo, c), dtype=torch.float32, device=x.device)
     L.check(L.load().mf_avgpool2d_nhwc_f32(x.contiguous().data_ptr(), out.data_ptr(), n, h, w, c, k, stride, pad, stream()), "mf_avgpool2d_nhwc_f32")
     return out
@@ -1744,8 +1891,8 @@ def avgpool2d(x: torch.Tensor, k: int, stride: int, pad: int) -> torch.Tensor:
 
 def upsample_nearest2x(x: torch.Tensor) -> torch.Tensor:
     """F.interpolate(scale 2, nearest-exact) on NHWC"""
+    check_upsample_nearest2x(x)
     _gpu(x)
-    _need_f32(x)
     n, h, w, c = x.shape
     out = torch.empty((n, 2 * h, 2 * w, c), dtype=torch.float32, device=x.device)
     L.check(L.load().mf_upsample_nearest2x_nhwc_f32(x.contiguous().data_ptr(), out.data_ptr(), n, h, w, c, stream()), "mf_upsample_nearest2x_nhwc_f32")
@@ -1754,11 +1901,9 @@ def upsample_nearest2x(x: torch.Tensor) -> torch.Tensor:
 
 def pixel_unshuffle2_add(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     """y [N, H/2, W/2, 4C] += nn.PixelUnshuffle(2)(x [N, H, W, C]) on NHWC, in place (BasicDown(use_res=True))"""
+    check_pixel_shuffle_pair("pixel_unshuffle2_add", x, y, unshuffle=True)
     _gpu(x, y)
-    _need_f32(x, y)
     n, h, w, c = x.shape
-    if y.shape != (n, h // 2, w // 2, 4 * c) or h % 2 or w % 2:
-        raise RuntimeError(f"pixel_unshuffle2_add: x {tuple(x.shape)} does not unshuffle onto y {tuple(y.shape)}")
     drop_split(y)
     L.check(L.load().mf_pixel_unshuffle2_add_nhwc_f32(x.contiguous().data_ptr(), y.data_ptr(), n, h, w, c, stream()), "mf_pixel_unshuffle2_add_nhwc_f32")
     return y
@@ -1766,31 +1911,32 @@ def pixel_unshuffle2_add(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
 
 def pixel_shuffle2_add(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     """y [N, 2H, 2W, C/4] += nn.PixelShuffle(2)(x [N, H, W, C]) on NHWC, in place (BasicUp(use_res=True))"""
+    check_pixel_shuffle_pair("pixel_shuffle2_add", x, y, unshuffle=False)
     _gpu(x, y)
-    _need_f32(x, y)
     n, h, w, c = x.shape
-    if c % 4 or y.shape != (n, 2 * h, 2 * w, c // 4):
-        raise RuntimeError(f"pixel_shuffle2_add: x {tuple(x.shape)} does not shuffle onto y {tuple(y.shape)}")
     drop_split(y)
     L.check(L.load().mf_pixel_shuffle2_add_nhwc_f32(x.contiguous().data_ptr(), y.data_ptr(), n, h, w, c, stream()), "mf_pixel_shuffle2_add_nhwc_f32")
     return y
 
 
 def diag_gaussian_sample(moments_nchw: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
+    """z = mean + exp(0.5 clamp(logvar, -30, 20)) noise of DiagonalGaussianDistribution (latent_embedders.py:18-27): moments [N, 2C, H, W] = mean | logvar,
+    noise [N, C, H, W], both contiguous fp32 (read in place: no copy is made)"""
+    n, c, hw = check_diag_gaussian("diag_gaussian_sample", moments_nchw, noise)
     _gpu(moments_nchw, noise)
-    n, c2, h, w = moments_nchw.shape
-    z = torch.empty((n, c2 // 2, h, w), dtype=torch.float32, device=moments_nchw.device)
-    L.check(L.load().mf_diag_gaussian_sample_f32(moments_nchw.data_ptr(), noise.data_ptr(), z.data_ptr(), n, c2 // 2, h * w, stream()),
+    h, w = moments_nchw.shape[2:]
+    z = torch.empty((n, c, h, w), dtype=torch.float32, device=moments_nchw.device)
+    L.check(L.load().mf_diag_gaussian_sample_f32(moments_nchw.data_ptr(), noise.data_ptr(), z.data_ptr(), n, c, hw, stream()),
             "mf_diag_gaussian_sample_f32")
     return z
 
 
 def diag_gaussian_kl(moments_nchw: torch.Tensor) -> torch.Tensor:
     """the KL term of DiagonalGaussianDistribution (latent_embedders.py:29-31) as a 0-dim device tensor"""
+    n, c, hw = check_diag_gaussian("diag_gaussian_kl", moments_nchw)
     _gpu(moments_nchw)
-    n, c2, h, w = moments_nchw.shape
     kl = torch.empty((1,), dtype=torch.float32, device=moments_nchw.device)
-    L.check(L.load().mf_diag_gaussian_kl_f32(moments_nchw.contiguous().data_ptr(), kl.data_ptr(), n, c2 // 2, h * w, stream()), "mf_diag_gaussian_kl_f32")
+    L.check(L.load().mf_diag_gaussian_kl_f32(moments_nchw.contiguous().data_ptr(), kl.data_ptr(), n, c, hw, stream()), "mf_diag_gaussian_kl_f32")
     return kl.reshape(())
 
 

@@ -22,7 +22,7 @@ class DiagonalGaussianDistribution(nn.Module):
     def forward(self, moments_nchw: torch.Tensor, noise: torch.Tensor):
         if moments_nchw.dim() == 5:   # NCDHW: the per-voxel op on the [N, 2C, D*H, W] view
             n, c2, d, h, w = moments_nchw.shape
-            return K.diag_gaussian_sample(moments_nchw.view(n, c2, d * h, w), noise).view(n, c2 // 2, d, h, w), None
+            return K.diag_gaussian_sample(moments_nchw.view(n, c2, d * h, w), noise.view(n, c2 // 2, d * h, w)).view(n, c2 // 2, d, h, w), None
         return K.diag_gaussian_sample(moments_nchw, noise), None
 
 

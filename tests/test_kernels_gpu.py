@@ -455,6 +455,32 @@ def test_sched_step_bit_exact(dev, objective, clip):
         assert torch.equal(x0o.cpu(), x0), (i, "x0")
         assert torch.equal(xTo.cpu(), xT), (i, "xT")
         assert torch.equal(out.cpu(), want), (i, "x_t")
+        if not clip:
+            continue
+        # second pass (clip_x0 only): a NaN, a +Inf and a -Inf prediction.  x_0.clamp(-1, 1) of the reference keeps the NaN and the oracle's chain
+        # hands it on to x_t; a clamp spelled fminf(fmaxf()) would turn it into x_0 = -1 and a finite next latent
+        pcn = pc.clone()
+        for pos, v in ((5, float("nan")), (6, float("inf")), (pc.numel() - 2, float("-inf"))):      # (5, 6: inside the second group of four; the last group)
+            pcn.view(-1)[pos] = v
+        pred = pu + g * (pcn - pu)
+        assert int(torch.isnan(pred).sum()) == 1 and int(torch.isinf(pred).sum()) == 2
+        if objective == "x_T":
+            prior, x0 = osch.estimate_x_t_prior_from_x_T(x_t, t, pred, clip_x0=clip)
+            xT = pred
+        else:
+            prior, x0 = osch.estimate_x_t_prior_from_x_0(x_t, t, pred, clip_x0=clip)
+            xT = osch.estimate_x_T(x_t, x_0=pred, t=t, clip_x0=clip)
+        want = prior if i == 6 else x0 * alpha_next.sqrt() + c * xT + sigma * nddim
+        assert int(torch.isnan(x0).sum()) == 1 and bool(torch.isnan(want.view(-1)[5]))      # the reference hands the NaN back
+        d[1] = pcn.to(dev)
+        a = L.MfSchedArgs(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), None, d[3].data_ptr(), d[4].data_ptr(), 0, out.data_ptr(),
+                          x0o.data_ptr(), xTo.data_ptr(), table.data_ptr(), None, i, 0 if objective == "x_T" else 1, int(clip), g, out.numel())
+        K.sched_step(a)
+        for name, got_t, want_t in (("x0", x0o, x0), ("xT", xTo, xT), ("x_t", out, want)):
+            got_c = got_t.cpu()
+            assert torch.equal(torch.isnan(got_c), torch.isnan(want_t)), (i, name, "NaN mask")
+            keep = ~torch.isnan(want_t)
+            assert torch.equal(got_c.view(torch.int32)[keep], want_t.contiguous().view(torch.int32)[keep]), (i, name, "non-finite pass")
 
 
 @pytest.mark.parametrize("objective,use_ddim,cfg", [("x_T", True, False), ("x_T", True, True), ("x_0", True, False), ("x_T", False, False)])

@@ -89,6 +89,52 @@ def test_front_half_is_the_scheduler_steps_bit_for_bit(dev, sampler, objective, 
         assert torch.equal(got[1], want[1]) and torch.equal(got[2], want[2]), (sampler, step)
         assert torch.equal(hist[step & 1], want[1])          # the history slot of this step holds the same x_0
         assert bool(got[0].isfinite().all())
+        if clip:
+            _nonfinite_pass(dev, sch, ts, table, old, x_t, pred, pu if cfg else None, step, objective, sampler)
+
+
+def _nan_equal(got, want, what):
+    """isnan masks equal, bits equal wherever the expected value is not NaN"""
+    got, want = got.cpu(), want.cpu()
+    assert torch.equal(torch.isnan(got), torch.isnan(want)), (what, "NaN mask", (torch.isnan(got) != torch.isnan(want)).nonzero()[:8].tolist())
+    keep = ~torch.isnan(want)
+    assert torch.equal(got.contiguous().view(torch.int32)[keep], want.contiguous().view(torch.int32)[keep]), what
+
+
+def _nonfinite_pass(dev, sch, ts, table, old, x_t, pred, pu, step, objective, sampler):
+    """second pass of the front half, clip_x0 only: `pred` holds a NaN and a +Inf inside a group of four and a -Inf in the last element -- at m = 1023 the
+    scalar tail of the kernel.  The oracle's fp32 chain on the CPU (x_0.clamp(-1, 1) keeps a NaN) decides x_0 and x_T; mf_sched_step_f32 must agree too."""
+    osch = R.GaussianNoiseScheduler(**R.published_scheduler_kwargs())
+    g, t_now = 3.5, list(reversed(ts))[step]
+    for m in (x_t.numel(), x_t.numel() - 1):
+        xs, ps = x_t[:m].clone(), pred[:m].clone()
+        us = None if pu is None else pu[:m].clone()
+        for pos, v in ((5, float("nan")), (6, float("inf")), (m - 1, float("-inf"))):
+            ps[pos] = v
+        xc, pc_ = xs.cpu(), ps.cpu()
+        pc = pc_ if us is None else us.cpu() + g * (pc_ - us.cpu())
+        t = torch.full((1,), t_now, dtype=torch.long)
+        if objective == 0:
+            x0 = osch.estimate_x_0(xc[None], pc[None], t, clip_x0=True)[0]
+            xT = pc
+        else:
+            x0 = pc.clamp(-1, 1)
+            xT = osch.estimate_x_T(xc[None], x_0=pc[None], t=t, clip_x0=True)[0]
+        assert int(torch.isnan(x0).sum()) == 1 and bool(torch.isnan(x0[5])) and bool(torch.isfinite(x0[6])) and bool(torch.isfinite(x0[m - 1]))
+        want = [torch.empty_like(xs) for _ in range(3)]
+        a = L.MfSchedArgs(xs.data_ptr(), ps.data_ptr(), None if us is None else us.data_ptr(), None, None, None, 0, want[0].data_ptr(), want[1].data_ptr(),
+                          want[2].data_ptr(), old.data_ptr(), None, step, objective, 1, g, m)
+        K.sched_step(a)
+        got = [torch.empty_like(xs) for _ in range(3)]
+        hist = torch.full((2, m), float("nan"), device=dev)
+        if step > 0:
+            hist[(step + 1) & 1] = _rand("f.prev", (x_t.numel(),)).to(dev)[:m]
+        K.solver_step(_args(xs, ps, us, got[0], got[1], got[2], hist, table, objective, 1, g, step=step))
+        for who, res in (("solver_step", got), ("sched_step", want)):
+            _nan_equal(res[1], x0, (who, sampler, step, m, "x0"))
+            _nan_equal(res[2], xT, (who, sampler, step, m, "xT"))
+        _nan_equal(hist[step & 1], x0, (sampler, step, m, "history slot"))
+        assert bool(torch.isnan(got[0][5])), (sampler, step, m)          # the NaN reaches the next latent, as in the reference
 
 
 # ------------------------------------------------------------------------------------------------ 2. the kernel's back half
