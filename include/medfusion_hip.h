@@ -337,7 +337,8 @@ int mf_gn_apply_from_partials_pairs_f32(const float* x, const double* gn_partial
                                         const float* residual, const void* residual_pairs, const float* emb, int64_t emb_stride, float* out,
                                         void* out_split, const float* res_bound, const float* res_bound_slots, int res_nslots,
                                         const float* emb_bound, float bconst, float* out_bound, int N, int HW, int C, int G, int act, void* stream);
-/* bound[n] = max |x[n][:]| over per_row elements: the measured operand bound of tensors no producer bounded analytically (network
+/* bound[n] = max |x[n][:]| over the FINITE values of per_row elements (NaN and +-Inf do not count: an Inf bound would store every finite
+ * value of the row as zero): the measured operand bound of tensors no producer bounded analytically (network
  * input convolutions, embedding rows).  Two launches, no atomics: every wave stores the max of its share into its own slot of
  * `partial` (N * mf_maxabs_rows_slots(per_row) floats of caller scratch), then one wave per row reduces the slots.
  * mf_bound_finalize_f32 is that second pass on its own: it turns the slot array a convolution filled (y_bound of mf_conv2d_f16x2)

@@ -134,8 +134,8 @@ __global__ __launch_bounds__(256) void conv3d_f16x2_kernel(const Conv3dP p) {
   for (int i = 0; i < TM; ++i) {
     const int pm = min(m0 + wm * FM + i * 32 + (lane & 31), p.M - 1);
     const int pn = pm / p.DHWo;
-    e1[i] = p.bound1 ? scale_exp_of(p.bound1[pn]) : 0;
-    e2[i] = (p.bound2 && p.C2 > 0) ? scale_exp_of(p.bound2[pn]) : 0;
+    const bool has2 = p.bound2 && p.C2 > 0;
+    source_exps(p.bound1 ? p.bound1[pn] : 0.f, p.bound1 != nullptr, has2 ? p.bound2[pn] : 0.f, has2, e1[i], e2[i]);   // (a zero bound: split_f16.h)
   }
   const int it_sw = p.C2 > 0 ? (p.C1 / 32) * p.taps : p.nit;   // first iteration that reads the second source
 
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void conv3d_f16x2_kernel(const Conv3dP p) {
       if (it == it_sw && it != it0) {
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
-          const float f = exp2i(e1[i]) * exp2i(-e2[i]);
+          const float f = exp2i(e1[i]) * exp2i(-e2[i]);   // (in range for e1 - e2 <= 97 - log2(C1 taps); 1 for an all-zero source: source_exps)
 #pragma unroll
           for (int j = 0; j < TN; ++j)
 #pragma unroll

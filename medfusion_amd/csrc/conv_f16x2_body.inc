@@ -79,8 +79,7 @@ __device__ __forceinline__ void conv_f16x2_body(const ConvP2& p_arg, const int b
 // cannot re-derive from the bounds later
 #define MFC2_PIXEL_EXPS_CONVERT()                                                                                       \
   _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                                                      \
-    pe1[i] = p.bound1 ? scale_exp_of(pb1[i]) : 0;                                                                       \
-    pe2[i] = (p.bound2 && p.C2 > 0) ? scale_exp_of(pb2[i]) : 0;                                                         \
+    source_exps(pb1[i], p.bound1 != nullptr, pb2[i], p.bound2 && p.C2 > 0, pe1[i], pe2[i]);   /* (a zero bound: split_f16.h) */  \
     asm volatile("" : "+v"(pe1[i]), "+v"(pe2[i]));                                                                      \
   }                                                                                                                     \
   if (!((p.splitk == 1 || p.tree) && p.bias)) { eb0 = f32x4{0.f, 0.f, 0.f, 0.f}; eb1 = eb0; }                           \
@@ -106,7 +105,7 @@ __device__ __forceinline__ void conv_f16x2_body(const ConvP2& p_arg, const int b
     eb0 = *reinterpret_cast<const f32x4*>(p.bias + bc0_);                                                               \
     eb1 = *reinterpret_cast<const f32x4*>(p.bias + bc0_ + 4);                                                           \
   }
-#define MFC2_PIXEL_EXPS(I) const int e1_ = p.bound1 ? scale_exp_of(pb1[I]) : 0, e2_ = (p.bound2 && p.C2 > 0) ? scale_exp_of(pb2[I]) : 0;
+#define MFC2_PIXEL_EXPS(I) int e1_, e2_; source_exps(pb1[I], p.bound1 != nullptr, pb2[I], p.bound2 && p.C2 > 0, e1_, e2_);
 #else
 #define MFC2_PIXEL_EXPS_DECL()
 #define MFC2_PIXEL_EXPS_ISSUE()
@@ -115,8 +114,8 @@ __device__ __forceinline__ void conv_f16x2_body(const ConvP2& p_arg, const int b
 #define MFC2_PIXEL_EXPS(I)                                                                                              \
     const int pm_ = min(m0 + wm * FM + (I) * 32 + (lane & 31), p.M - 1);                                                \
     const int pn_ = pm_ / p.HWout;                                                                                      \
-    const int e1_ = p.bound1 ? scale_exp_of(p.bound1[pn_]) : 0;                                                         \
-    const int e2_ = (p.bound2 && p.C2 > 0) ? scale_exp_of(p.bound2[pn_]) : 0;
+    int e1_, e2_;                                                                                                       \
+    source_exps(p.bound1 ? p.bound1[pn_] : 0.f, p.bound1 != nullptr, (p.bound2 && p.C2 > 0) ? p.bound2[pn_] : 0.f, p.bound2 && p.C2 > 0, e1_, e2_);
 #endif
   MFC2_PIXEL_EXPS_DECL()
   const int total = p.tiles_m * p.tiles_n * p.splitk;

@@ -472,10 +472,14 @@ __global__ __launch_bounds__(256) void gn_apply_part_kernel(const float* __restr
 __global__ __launch_bounds__(256) void maxabs_kernel(const float* __restrict__ x, float* __restrict__ partial, long per_sample4) {
   const int n = blockIdx.y;
   const float4* p = reinterpret_cast<const float4*>(x) + (long)n * per_sample4;
+  // the largest FINITE magnitude: fmaxf drops a NaN by itself, and an Inf must not become the bound either -- its exponent is the clamp +100, under
+  // which every finite value of the sample is stored as zero: one Inf voxel turned all outputs of its sample that never read it into the bare bias
+  // (tests/test_conv3d_gpu.py).  The Inf itself goes through the split as Inf whatever the scale (split_f16.h).
+  auto fin = [](float a) { a = fabsf(a); return a <= 3.4028234663852886e38f ? a : 0.f; };
   float m = 0.f;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < per_sample4; i += (long)gridDim.x * blockDim.x) {
     const float4 v = p[i];
-    m = fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+    m = fmaxf(fmaxf(m, fmaxf(fin(v.x), fin(v.y))), fmaxf(fin(v.z), fin(v.w)));
   }
   m = wave_max(m);
   if ((threadIdx.x & 63) == 0) partial[((long)n * gridDim.x + blockIdx.x) * 4 + (threadIdx.x >> 6)] = m;

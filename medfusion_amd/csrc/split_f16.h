@@ -51,6 +51,18 @@ __device__ __forceinline__ int scale_exp_of(float bound) {
   return s < -100 ? -100 : (s > 100 ? 100 : s);
 }
 __device__ __forceinline__ float exp2i(int s) { return __uint_as_float((unsigned)(127 + s) << 23); }  // 2^s, -126 <= s <= 127
+// The two exponents of a fused concat's sources (0: that source is unscaled).  Where the K loop meets the second source the accumulators are
+// multiplied by 2^(e1 - e2): they hold up to C1 taps products of two values below 2^15 each, so the product stays inside fp32 while
+// e1 - e2 <= 97 - log2(C1 taps) (81 for the 2^16 products of the widest layer); in the other direction the factor only shrinks them.
+// Measured bounds of real activations are nowhere near 2^81 apart -- except an all-zero sample, whose bound 0 has the clamp exponent -100:
+// next to a sample of 1e6 the factor was 2^107.  A zero bound carries no information (zeros are stored as zeros under any scale), so such a
+// source takes the other source's exponent and the factor is 1; every other pair of bounds keeps its exponents, and its bits.
+__device__ __forceinline__ void source_exps(float bound1, bool has1, float bound2, bool has2, int& e1, int& e2) {
+  const int a = has1 ? scale_exp_of(bound1) : 0, b = has2 ? scale_exp_of(bound2) : 0;
+  const bool both = has1 && has2;   // (selects, not branches: this sits in front of every convolution's first load)
+  e1 = (both && bound1 == 0.f) ? b : a;
+  e2 = (both && bound2 == 0.f) ? a : b;   // (both zero: a == b)
+}
 
 // A finite value that exceeds its bound (it never does when the bound is one) saturates at the fp16 range; NaN and +-Inf are NOT clamped:
 // they go through the conversions as NaN / Inf (hi = NaN or Inf, lo' = NaN), the matrix cores carry them on, and the convolution's output

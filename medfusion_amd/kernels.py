@@ -853,11 +853,36 @@ def pack_conv3d_weight(w_oidhw: torch.Tensor, cin_pad: int = 0) -> torch.Tensor:
     return out
 
 
+def check_conv3d(x1, x2, w_split, bias, out, d: L.MfConv3dDesc) -> None:
+    """The sizes mf_conv3d_f16x2 takes on trust, against the descriptor: x1 / x2 hold N D H W voxels of C1 / C2 channels (x2 present iff C2 > 0), the
+    bias Cout values, the split weights Cout k^3 (C1 + C2), and `out` -- None: the wrapper allocates it -- is contiguous fp32 of N Do Ho Wo Cout values"""
+    def bad(msg):
+        raise RuntimeError(f"medfusion_amd: conv3d_f16x2: {msg}")
+    vox = d.N * d.D * d.H * d.W
+    if x1 is None or x1.numel() != vox * d.C1:
+        bad(f"x1 holds {None if x1 is None else x1.numel()} values, the descriptor's N D H W C1 = {d.N} {d.D} {d.H} {d.W} {d.C1} needs {vox * d.C1}")
+    if (x2 is not None) != (d.C2 > 0):
+        bad(f"the second source is {'given' if x2 is not None else 'missing'} but the descriptor has C2 = {d.C2}")
+    if x2 is not None and x2.numel() != vox * d.C2:
+        bad(f"x2 holds {x2.numel()} values, the descriptor's N D H W C2 = {d.N} {d.D} {d.H} {d.W} {d.C2} needs {vox * d.C2}")
+    if bias is not None and (bias.numel() != d.Cout or bias.dtype != torch.float32 or not bias.is_contiguous()):
+        bad(f"bias {tuple(bias.shape)} {bias.dtype} must be contiguous fp32 of Cout = {d.Cout} values")
+    wh = w_split[0]
+    if wh.numel() != d.Cout * d.k ** 3 * (d.C1 + d.C2) or not wh.is_contiguous():
+        bad(f"the split weights hold {wh.numel()} values, Cout k^3 (C1 + C2) = {d.Cout} {d.k}^3 ({d.C1} + {d.C2}) needs {d.Cout * d.k ** 3 * (d.C1 + d.C2)}")
+    if out is not None:
+        od = [((e << u) + 2 * p - d.k) // s + 1 if s > 0 else 0 for e, s, p, u in zip((d.D, d.H, d.W), d.stride, d.pad, d.upsample)]
+        want = d.N * od[0] * od[1] * od[2] * d.Cout
+        if out.numel() != want or out.dtype != torch.float32 or not out.is_contiguous():
+            bad(f"out {tuple(out.shape)} {out.dtype} must be contiguous fp32 of N Do Ho Wo Cout = {d.N} {od[0]} {od[1]} {od[2]} {d.Cout} = {want} values")
+
+
 def conv3d_f16x2(x1: torch.Tensor, w_split, bias: Optional[torch.Tensor], d: L.MfConv3dDesc, x2: Optional[torch.Tensor] = None,
                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """MF_CONV_FP32_F16X2 3-D convolution of NDHWC fp32 tensors (any shape with N leading and d.C1 / d.C2 innermost, e.g. the [N, D*H, W, C]
     view) whose fp16-pair mirrors are made on demand (or that exist as pairs only: pack_nchw_pairs).  w_split = split_weight_f16x2(
     pack_conv3d_weight(...)).  Returns y fp32 [N, Do, Ho, Wo, Cout] (or fills `out`, any shape of that size)."""
+    check_conv3d(x1, x2, w_split, bias, out, d)
     wh, wmax = w_split
     _gpu(x1, x2, wh, bias)
     lib = L.load()
