@@ -493,6 +493,7 @@ def conv2d_f16x2(x1: torch.Tensor, w_split, bias: Optional[torch.Tensor], d: L.M
     measure_out: also measure the per-sample max |y| (-> y._mf_bound: the output feeds a convolution or a residual add un-normalised).
     pinned: pin_conv_plan(d), computed once by callers that launch the same descriptor every iteration.
     Returns y, or (y, partial [N, parts, G, 2]) when gn_groups > 0 (statistics of the GroupNorm that follows)."""
+    check_conv2d("conv2d_f16x2", x1, x2, w_split[0], bias, out, d)
     wh, wmax = w_split
     _gpu(x1, x2, wh, bias)
     lib = L.load()
@@ -590,6 +591,7 @@ def conv2d_f16x2_pairs_out(x1: torch.Tensor, w_split, bias: Optional[torch.Tenso
     """the fp16-pair convolution writing its output as fp32 AND as fp16 pairs under a bound derived from the operands
     (mf_conv2d_f16x2_pairs_out): l1 = (largest filter L1 norm over the channels of x1, ... of x2), bias_max = max |bias|.  The result carries
     its mirror and bound like the output of gn_apply(split=True): no measuring pass, no split launch in front of its consumers."""
+    check_conv2d("conv2d_f16x2_pairs_out", x1, x2, w_split[0], bias, None, d)
     wh, wmax = w_split
     _gpu(x1, x2, wh, bias)
     lib = L.load()
@@ -924,9 +926,46 @@ def conv_out_hw(d: L.MfConvDesc):
     return (he + 2 * d.pad - d.KH) // d.stride + 1, (we + 2 * d.pad - d.KW) // d.stride + 1
 
 
+def check_conv2d(what: str, x1, x2, w, bias, out, d: L.MfConvDesc) -> None:
+    """The sizes mf_conv2d_f32 / mf_conv2d_f16x2 / mf_conv2d_f16x2_pairs_out take on trust, against the descriptor: x1 / x2 hold N Hin Win pixels of
+    C1 / C2 channels in either layout (x2 present iff C2 > 0), the bias Cout contiguous fp32 values, the weights Cout KH KW (C1 + C2) values -- the
+    sub-pixel packing (upsample = 2) 4 phases of Cout 2 2 (C1 + C2), the component GEMMs of a Winograd convolution (upsample = 3) 16 slabs of Cout
+    (C1 + C2), the bf16-triplet form (precision 3) three times as many -- and `out` -- None: the wrapper allocates it -- is contiguous fp32 of
+    N Ho Wo Cout values.  Host arithmetic on shapes only: no device call, no sync."""
+    def bad(msg):
+        raise RuntimeError(f"medfusion_amd: {what}: {msg}")
+    lay = "NCHW" if d.in_layout == L.LAYOUT_NCHW else "NHWC"
+    pix = d.N * d.Hin * d.Win
+    if x1 is None or x1.numel() != pix * d.C1:
+        bad(f"x1 holds {None if x1 is None else x1.numel()} values, the descriptor's N Hin Win C1 = {d.N} {d.Hin} {d.Win} {d.C1} ({lay}) needs {pix * d.C1}")
+    if (x2 is not None) != (d.C2 > 0):
+        bad(f"the second source is {'given' if x2 is not None else 'missing'} but the descriptor has C2 = {d.C2}")
+    if x2 is not None and x2.numel() != pix * d.C2:
+        bad(f"x2 holds {x2.numel()} values, the descriptor's N Hin Win C2 = {d.N} {d.Hin} {d.Win} {d.C2} ({lay}) needs {pix * d.C2}")
+    if bias is not None and (bias.numel() != d.Cout or bias.dtype != torch.float32 or not bias.is_contiguous()):
+        bad(f"bias {tuple(bias.shape)} {bias.dtype} must be contiguous fp32 of Cout = {d.Cout} values")
+    cin = d.C1 + d.C2
+    if d.upsample == 2:
+        want, form = 4 * d.Cout * 4 * cin, f"the sub-pixel packing 4 Cout 2 2 (C1 + C2) = 4 {d.Cout} 2 2 ({d.C1} + {d.C2})"
+    elif d.upsample == 3:
+        want, form = 16 * d.Cout * cin, f"16 Cout (C1 + C2) = 16 {d.Cout} ({d.C1} + {d.C2})"
+    else:
+        want, form = d.Cout * d.KH * d.KW * cin, f"Cout KH KW (C1 + C2) = {d.Cout} {d.KH} {d.KW} ({d.C1} + {d.C2})"
+    if d.precision == 3:
+        want, form = 3 * want, "three bf16 terms of " + form
+    if w is None or w.numel() != want or not w.is_contiguous():
+        bad(f"the weights hold {None if w is None else w.numel()} values{'' if w is None or w.is_contiguous() else ' (not contiguous)'}, {form} needs {want}")
+    if out is not None:
+        ho, wo = conv_out_hw(d) if d.stride > 0 else (0, 0)
+        n_out = d.N * ho * wo * d.Cout
+        if out.numel() != n_out or out.dtype != torch.float32 or not out.is_contiguous():
+            bad(f"out {tuple(out.shape)} {out.dtype} must be contiguous fp32 of N Ho Wo Cout = {d.N} {ho} {wo} {d.Cout} = {n_out} values")
+
+
 def conv2d(x1: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor], d: L.MfConvDesc, x2: Optional[torch.Tensor] = None,
            out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y = conv(x1 ++ x2) + bias per descriptor `d`.  Output NHWC [N,Ho,Wo,Cout] or NCHW [N,Cout,Ho,Wo]."""
+    check_conv2d("conv2d", x1, x2, w_packed, bias, out, d)
     _gpu(x1, x2, w_packed, bias)
     _need_f32(x1, x2)
     lib = L.load()

@@ -340,7 +340,7 @@ def _product_unit(x, w):
 def bias_add_rounds_once(y_nobias, b):
     """True where adding the bias to the exact fp32 value y rounds at most once to float32(y + b in fp64): either the fp64 sum is exact, or |y| lies
     below a quarter ulp of the bias (every correctly rounded path then returns the bias)"""
-    bb = b.double().view(1, -1, 1, 1, 1).expand_as(y_nobias)
+    bb = b.double().view(1, -1, *([1] * (y_nobias.dim() - 2))).expand_as(y_nobias)
     s = y_nobias + bb
     exact = (s - bb) == y_nobias
     tiny = y_nobias.abs() < bb.abs() * 2.0 ** -26
@@ -350,15 +350,18 @@ def bias_add_rounds_once(y_nobias, b):
 # ---------------------------------------------------------------------------------------------------------------- real-valued operands
 def real_operands(c, seed=0, cancelling=False):
     """random fp32-valued operands (fp64 tensors): N(0, 1) activations and 1/sqrt(K) weights, or -- cancelling -- activations 1 + 1e-3 noise and
-    filters with zero mean, the construction of tests/test_kernels_gpu.py::test_conv_f16x2_cancelling_sums"""
+    filters with zero mean, the construction of tests/test_kernels_gpu.py::test_conv_f16x2_cancelling_sums.  Any rank: a case with `dhw` is a
+    volume, one with `H` and `W` (tests/conv2d_cases.py) an image"""
     g = torch.Generator().manual_seed(_seed_of(c.name, "real", seed, cancelling))
     cin = c.C1 + c.C2
-    x = torch.randn((c.N, cin, *c.dhw), generator=g, dtype=torch.float64)
-    w = torch.randn((c.Cout, cin, c.k, c.k, c.k), generator=g, dtype=torch.float64) / math.sqrt(cin * c.k ** 3)
+    extents = tuple(c.dhw) if hasattr(c, "dhw") else (c.H, c.W)
+    rank = len(extents)
+    x = torch.randn((c.N, cin, *extents), generator=g, dtype=torch.float64)
+    w = torch.randn((c.Cout, cin, *((c.k,) * rank)), generator=g, dtype=torch.float64) / math.sqrt(cin * c.k ** rank)
     b = torch.randn((c.Cout,), generator=g, dtype=torch.float64) * 0.1
     if cancelling:
         x = 1.0 + 1e-3 * x
-        w = w - w.mean(dim=(1, 2, 3, 4), keepdim=True)
+        w = w - w.mean(dim=tuple(range(1, rank + 2)), keepdim=True)
     x, w, b = x.float().double(), w.float().double(), b.float().double()
     return x[:, :c.C1].contiguous(), (x[:, c.C1:].contiguous() if c.C2 else None), w, b
 

@@ -14,6 +14,7 @@ ROOT = Path(__file__).resolve().parents[1]
 
 from oracle import restate as R
 from oracle import synth as S
+from tests.conv2d_cases import F16X2_TILES, HALO_HG, IGEMM_BN, _halo_fits  # noqa: F401  (the one restatement of the planners' tables and rules)
 from tests.util import relerr
 
 
@@ -46,9 +47,6 @@ CONV_CASES = [
     (2, 8, 8, 512, 512, 512, 3, 1, 0),  # out-block two-source, long K -> split-K
     (1, 7, 9, 96, 0, 96, 3, 1, 0),      # Cout = 96 (BN=32 path), ragged
 ]
-
-
-IGEMM_BN = {1: 128, 2: 64, 3: 128, 4: 64, 5: 32, 6: 32, 7: 128, 8: 128, 9: 256, 10: 128, 23: 128, 24: 64, 27: 128, 28: 128}
 
 
 def _igemm_tiles(case, tiles):
@@ -689,29 +687,6 @@ F16X2_CASES = [
     (5, 8, 8, 96, 32, 256, 3, 1, 0),     # four 8 x 8 images per 256-row tile (the last tile holds one), two per 128-row tile
     (1, 64, 64, 32, 0, 128, 3, 1, 0),    # 64-wide image: 4 / 2 rows per tile
 ]
-F16X2_TILES = {31: (128, 256), 32: (256, 128), 33: (128, 128), 34: (128, 128), 35: (256, 64), 36: (128, 64), 37: (64, 256),
-               51: (128, 128), 52: (128, 128), 53: (64, 128), 54: (128, 64),   # 51-54: 4-wave workgroups, two per CU
-               61: (256, 128), 62: (256, 128), 63: (128, 128), 64: (128, 128)}   # 61-64: halo tiles (3x3 stride 1 only; HG = 6, 7, 4, 5)
-HALO_HG = {61: (6, 8), 62: (7, 8), 63: (4, 8), 64: (5, 8)}   # tile -> (halo pieces per wave, waves)
-
-
-def _halo_fits(case, tile):
-    n, h, w, c1, c2, co, k, stride, ups = case
-    if tile not in HALO_HG:
-        return True
-    bm, _ = F16X2_TILES[tile]
-    if k != 3 or stride != 1 or ups:
-        return False
-    if h * w >= bm:
-        if (h * w) % bm or bm % w:
-            return False
-        r, segs = bm // w, 1
-    else:
-        if bm % (h * w):
-            return False
-        r, segs = h, bm // (h * w)
-    hg, nw = HALO_HG[tile]
-    return segs * (r + 2) * (w + 2) <= 8 * nw * hg
 
 
 def _f16x2_tiles(case):
