@@ -880,6 +880,93 @@ int mf_ksum_finish_f64(const void* workspace, double* out, const MfKernelSumDesc
 int mf_feat_kernel_f32(const float* x, const float* nx, const float* y, const float* ny, const float* pivot, float* out, const MfKernelSumDesc* desc,
                        void* stream);
 
+/* Held-out denoising loss (the validation step of diffusion_pipeline.py:78-201 on the device; additive to ABI 250).  All tensors fp32, NCHW / NCDHW
+ * contiguous, B rows of per_row elements; t is a device int32 [B]; the scheduler tables are device fp32 [T].  No host synchronisation, no allocation,
+ * no atomics, capture-safe.
+ *
+ * mf_diffuse_rows_f32: the forward process with t PER ROW, GaussianNoiseScheduler.estimate_x_t (gaussian_scheduler.py:61-77):
+ *   x_t[b] = sqrt_ac[t_b] x_0[b] + sqrt_1m_ac[t_b] eps[b], the two products rounded separately, then the sum (mf_rows_axpby_f32's chain on the
+ *   gathered coefficients, bit for bit); a row with t_b < 0 returns x_0[b], one with t_b >= T returns eps[b], as the reference's clipper does.
+ *   eps != NULL  the caller's draw; any per_row, 16-byte vectors when every tensor is 16-byte aligned and per_row % 4 == 0, else element by element;
+ *   eps == NULL  generated in registers: the values mf_philox_normal_f32 writes for (seed, draw, rows sample_offset .. + B); eps_out (optional)
+ *                receives them.  Refused (MF_EUNSUPPORTED) where mf_solver_step_noise_f32 refuses: per_row not a multiple of 4, an unaligned tensor. */
+typedef struct MfDiffuseArgs {
+  const float* x_0;
+  const float* eps;          /* the caller's draw, or NULL: Philox inside the launch */
+  float* x_t;
+  float* eps_out;            /* Philox form only, optional: the draw */
+  const int32_t* t;          /* [B], device */
+  const float* sqrt_ac;      /* [T] sqrt_alphas_cumprod */
+  const float* sqrt_1m_ac;   /* [T] sqrt_one_minus_alphas_cumprod */
+  int64_t per_row;
+  uint64_t seed;             /* Philox form: the key of mf_philox_normal_f32 */
+  int64_t sample_offset;     /* Philox form: global index of row 0 */
+  int32_t draw;
+  int32_t T, B;
+  int32_t reserved;          /* 0 */
+} MfDiffuseArgs;
+int mf_diffuse_rows_f32(const MfDiffuseArgs* a, void* stream);
+/* mf_denoise_loss_f32 / mf_denoise_loss_finish_f32: per-row error sums of one prediction against its target.
+ *   pred [B][C][D][H][W] (D = 1 and dims = 2 for images).  The target has extents (D f, H f, W f) -- (H f, W f) in 2-D -- for an integer pooling
+ *   factor f >= 1 and is average-pooled on the fly: the pooled value is the fp32 sum of the f^dims block, added in (depth, row, column) order, divided
+ *   by f^dims -- F.interpolate(mode='area') for a side that is a multiple of f (anything else cannot be described here).
+ *   target != NULL  read from the tensor;
+ *   target == NULL  regenerated in registers: the values mf_philox_normal_f32 writes for (seed, draw, rows sample_offset .. + B) of target shape
+ *                   (MF_EUNSUPPORTED unless the target's elements per row are a multiple of 4): the draw is never stored.
+ *   Per element d = fl32(pred - target); every lane adds |d| and d d in fp64 over its elements in ascending order, the 256 lanes of a workgroup meet
+ *   in LDS by a fixed tree, and each workgroup writes two doubles: workspace [B][parts][2], parts = mf_loss_parts(per_row), 16 bytes per partial --
+ *   mf_loss_workspace_bytes(B, per_row, 2) in all (parts <= 256; one partial covers at least 8192 elements).  The finish launch adds a row's partials
+ *   in ascending order: out [B][2] fp64 = (sum |d|, sum d d).  A workgroup takes whole quads of 4 consecutive elements of a row; 16-byte loads of pred
+ *   (and of an un-pooled target) when they are 16-byte aligned and per_row % 4 == 0, element by element otherwise -- the same elements in the same
+ *   lanes in the same order.  The bits of a row's sums depend on that row's data only: not on B, the row's place, the load path, or whether the
+ *   target was stored or regenerated. */
+typedef struct MfLossDesc {
+  int32_t B, C;
+  int32_t dims;        /* 2 or 3 */
+  int32_t size[3];     /* pred's D, H, W (D = 1 in 2-D) */
+  int32_t f;           /* pooling factor of the target per axis, >= 1 */
+  int32_t draw;        /* Philox target */
+  uint64_t seed;
+  int64_t sample_offset;
+} MfLossDesc;
+int mf_loss_parts(int64_t per_row);
+size_t mf_loss_workspace_bytes(int B, int64_t per_row, int values);
+int mf_denoise_loss_f32(const float* pred, const float* target_or_null, const MfLossDesc* d, void* workspace, size_t workspace_bytes, void* stream);
+int mf_denoise_loss_finish_f32(const void* workspace, double* out, int B, int64_t per_row, void* stream);
+/* mf_variance_loss_f32 / mf_variance_loss_finish_f32: the learned-variance terms of the validation step (diffusion_pipeline.py:152-173) per row, with
+ * the same partial / finish scheme (three doubles per partial: mf_loss_workspace_bytes(B, per_row, 3)).  Per element, evaluated in fp64 on the fp32
+ * data (inputs, tables, and the two clamp constants as an fp32 run holds them, 1e-20f and 1e-6f): at t = 0 exp(-pred_logvar) reaches e^46 and the
+ * two terms of nll cancel, so one fp32 evaluation of an element is only good to ~2e-6 of it:
+ *   vs = (pred_var + 1) / 2;  lmax = log(max(betas[t], 1e-20)), lmin = log(max(posterior_variance[t], 1e-20));
+ *   pred_logvar = vs lmax + (1 - vs) lmin;  true_logvar = lmin;
+ *   pred_x_0 = objective 0 ('x_T'): clip?(sqrt_recip_ac[t] x_t - sqrt_recipm1_ac[t] x_T) with the TRUE x_T (the reference's line 159, mirrored);
+ *              objective 1 ('x_0'): pred;
+ *   pred_mean = coef1[t] pred_x_0 + coef2[t] x_t,  true_mean = coef1[t] x_0 + coef2[t] x_t;
+ *   kl  = 0.5 (pred_logvar - true_logvar + exp(true_logvar - pred_logvar) + (true_mean - pred_mean)^2 exp(-pred_logvar) - 1)   (math_utils.py);
+ *   nll = 0.5 (log(v) + (pred_x_0 - x_0)^2 / v), v = max(exp(pred_logvar), 1e-6)                                           (F.gaussian_nll_loss).
+ * out [B][3] fp64 = (sum kl, sum nll, sum vs).  The select t == 0 ? nll : kl belongs to the caller.  A row whose t is outside [0, T) reads no
+ * table and gives NaN. */
+typedef struct MfVarianceLossArgs {
+  const float* x_0;
+  const float* x_t;
+  const float* x_T;
+  const float* pred;
+  const float* pred_var;
+  const int32_t* t;                 /* [B], device */
+  const float* betas;               /* the [T] tables of the scheduler */
+  const float* posterior_variance;
+  const float* coef1;               /* posterior_mean_coef1 */
+  const float* coef2;               /* posterior_mean_coef2 */
+  const float* sqrt_recip_ac;
+  const float* sqrt_recipm1_ac;
+  int64_t per_row;
+  int32_t T, B;
+  int32_t objective;                /* 0: 'x_T', 1: 'x_0' */
+  int32_t clip_x0;
+} MfVarianceLossArgs;
+int mf_variance_loss_f32(const MfVarianceLossArgs* a, void* workspace, size_t workspace_bytes, void* stream);
+int mf_variance_loss_finish_f32(const void* workspace, double* out, int B, int64_t per_row, void* stream);
+
 /* ------------------------------------------------------------------ built-in launch timing (bench / roofline)
  * When enabled every launch is bracketed by hipEvents on its own stream and attributed to a kernel family.
  * NOT capture-safe; off by default. */

@@ -16,6 +16,7 @@ from .pipeline import DiffusionPipeline, EMAModel  # noqa: F401
 from .scheduler import BasicNoiseScheduler, GaussianNoiseScheduler  # noqa: F401
 from .unet import LabelEmbedder, LearnedSinusoidalPosEmb, SinusoidalPosEmb, TimeEmbbeding, UNet  # noqa: F401
 from .vae import VAE, DiagonalGaussianDistribution  # noqa: F401
+from .validation import ValidationMeter  # noqa: F401
 from .vq import VAEGAN, VQGAN, VQVAE, VectorQuantizer  # noqa: F401
 
 __version__ = "0.1.0"

@@ -1730,6 +1730,113 @@ def solver_step_noise(args: L.MfSolverArgs, nz: L.MfSolverNoise, blend: Optional
     L.check(L.load().mf_solver_step_noise_f32(C.byref(args), C.byref(nz), None if blend is None else C.byref(blend), stream()), "mf_solver_step_noise_f32")
 
 
+def check_rows_t(what: str, t, B: int) -> None:
+    """t: the timestep of every row as the loss kernels read it -- contiguous int32 [B]"""
+    _dense(what, "t", t, dtype=torch.int32, shape=(B,))
+
+
+def philox_in_launch_ok(*ts) -> bool:
+    """may a launch over these [B, ...] tensors generate its draw in registers?  mf_solver_step_noise_f32's rule: elements per sample a multiple
+    of 4 and every tensor 16-byte aligned (None: absent)"""
+    ts = [t for t in ts if t is not None]
+    return all(t.data_ptr() % 16 == 0 for t in ts) and (ts[0].numel() // max(1, ts[0].shape[0])) % 4 == 0
+
+
+def diffuse_rows(x_0: torch.Tensor, t: torch.Tensor, sqrt_ac: torch.Tensor, sqrt_1m_ac: torch.Tensor, eps: Optional[torch.Tensor] = None, philox=None,
+                 eps_out: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, outputs=()) -> torch.Tensor:
+    """x_t[b] = sqrt_ac[t_b] x_0[b] + sqrt_1m_ac[t_b] eps[b] in one launch (mf_diffuse_rows_f32; rows with t < 0 return x_0, t >= T eps).  eps: the
+    caller's draw, or philox = (seed, draw, sample_offset): the draw is generated in registers (eps_out, optional, receives it).  t: int32 [B] on
+    the device; the two tables fp32 [T].  `outputs` as in sched_step."""
+    what = "diffuse_rows"
+    _dense(what, "x_0", x_0)
+    B = x_0.shape[0]
+    check_rows_t(what, t, B)
+    _dense(what, "sqrt_ac", sqrt_ac, dim=1)
+    _dense(what, "sqrt_1m_ac", sqrt_1m_ac, shape=sqrt_ac.shape)
+    if (eps is None) == (philox is None):
+        raise RuntimeError("medfusion_amd: diffuse_rows: either eps or philox=(seed, draw, sample_offset)")
+    for name, v in (("eps", eps), ("eps_out", eps_out), ("out", out)):
+        if v is not None:
+            _dense(what, name, v, shape=x_0.shape, written=name != "eps")
+    _gpu(x_0, t, sqrt_ac, sqrt_1m_ac, eps, eps_out, out)
+    if out is None:
+        out = torch.empty_like(x_0)
+    _drop_outputs((out, eps_out, *outputs))
+    seed, draw, offset = philox if philox is not None else (0, 0, 0)
+    a = L.MfDiffuseArgs(x_0.data_ptr(), _ptr(eps), out.data_ptr(), _ptr(eps_out), t.data_ptr(), sqrt_ac.data_ptr(), sqrt_1m_ac.data_ptr(), x_0.numel() // B,
+                        seed & 0xFFFFFFFFFFFFFFFF, offset, draw, sqrt_ac.shape[0], B, 0)
+    L.check(L.load().mf_diffuse_rows_f32(C.byref(a), stream()), "mf_diffuse_rows_f32")
+    return out
+
+
+def loss_pool_factor(pred_shape, target_shape) -> int:
+    """the integer factor f by which a [B, C, spatial...] target is average-pooled onto pred: every spatial side of the target f times pred's
+    (ValueError otherwise: F.interpolate(mode='area') between sides that do not divide is not this pooling)"""
+    ps, ts = tuple(pred_shape), tuple(target_shape)
+    if len(ps) != len(ts) or len(ps) not in (4, 5) or ps[:2] != ts[:2]:
+        raise ValueError(f"denoise_loss: pred {ps} against target {ts}: [B, C, spatial...] tensors of one rank, batch and channel count")
+    if any(p < 1 for p in ps[2:]) or ts[2] % ps[2] or ts[2] < ps[2]:
+        raise ValueError(f"denoise_loss: pred {ps} against target {ts}: the target's side must be a multiple of pred's")
+    f = ts[2] // ps[2]
+    if any(tt != f * pp for pp, tt in zip(ps[2:], ts[2:])):
+        raise ValueError(f"denoise_loss: pred {ps} against target {ts}: every side of the target must be {f} times pred's")
+    return f
+
+
+def _loss_sums(entry: str, finish: str, launch, B: int, per: int, values: int, device) -> torch.Tensor:
+    lib = L.load()
+    need = lib.mf_loss_workspace_bytes(B, per, values)
+    ws = Workspace.get(need, device)
+    out = torch.empty((B, values), dtype=torch.float64, device=device)
+    L.check(launch(lib, ws.data_ptr(), need), entry)
+    L.check(getattr(lib, finish)(ws.data_ptr(), out.data_ptr(), B, per, stream()), finish)
+    return out
+
+
+def denoise_loss(pred: torch.Tensor, target: Optional[torch.Tensor] = None, philox=None, target_shape=None) -> torch.Tensor:
+    """[B, 2] fp64 = per row (sum |pred - target|, sum (pred - target)^2), the target average-pooled on the fly onto pred's extents
+    (mf_denoise_loss_f32 + mf_denoise_loss_finish_f32; partials in the per-stream workspace).  target: a [B, C, spatial...] tensor, or
+    philox = (seed, draw, sample_offset) with target_shape: the draw mf_philox_normal_f32 would write there, regenerated in registers."""
+    what = "denoise_loss"
+    _dense(what, "pred", pred)
+    if (target is None) == (philox is None):
+        raise RuntimeError("medfusion_amd: denoise_loss: either target or philox=(seed, draw, sample_offset) with target_shape")
+    if target is not None:
+        _dense(what, "target", target)
+        target_shape = target.shape
+    f = loss_pool_factor(pred.shape, target_shape)
+    _gpu(pred, target)
+    B, Cc = pred.shape[0], pred.shape[1]
+    sp = tuple(pred.shape[2:])
+    seed, draw, offset = philox if philox is not None else (0, 0, 0)
+    d = L.MfLossDesc(B, Cc, len(sp), (C.c_int32 * 3)(*((1,) * (3 - len(sp)) + sp)), f, draw, seed & 0xFFFFFFFFFFFFFFFF, offset)
+    return _loss_sums("mf_denoise_loss_f32", "mf_denoise_loss_finish_f32",
+                      lambda lib, ws, n: lib.mf_denoise_loss_f32(pred.data_ptr(), _ptr(target), C.byref(d), ws, n, stream()), B, pred.numel() // B, 2, pred.device)
+
+
+VARIANCE_TABLES = ("betas", "posterior_variance", "posterior_mean_coef1", "posterior_mean_coef2", "sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod")
+
+
+def variance_loss(x_0: torch.Tensor, x_t: torch.Tensor, x_T: torch.Tensor, pred: torch.Tensor, pred_var: torch.Tensor, t: torch.Tensor, tables: dict,
+                  objective: int, clip_x0: bool) -> torch.Tensor:
+    """[B, 3] fp64 = per row (sum kl, sum nll, sum var_scale) of the learned-variance terms of the validation step (mf_variance_loss_f32 +
+    mf_variance_loss_finish_f32).  tables: the scheduler's device tables by buffer name (VARIANCE_TABLES); t int32 [B] on the device."""
+    what = "variance_loss"
+    _dense(what, "x_0", x_0)
+    for name, v in (("x_t", x_t), ("x_T", x_T), ("pred", pred), ("pred_var", pred_var)):
+        _dense(what, name, v, shape=x_0.shape)
+    B = x_0.shape[0]
+    check_rows_t(what, t, B)
+    tabs = [tables[n] for n in VARIANCE_TABLES]
+    for n, v in zip(VARIANCE_TABLES, tabs):
+        _dense(what, n, v, shape=tabs[0].shape, dim=1)
+    _gpu(x_0, x_t, x_T, pred, pred_var, t, *tabs)
+    a = L.MfVarianceLossArgs(x_0.data_ptr(), x_t.data_ptr(), x_T.data_ptr(), pred.data_ptr(), pred_var.data_ptr(), t.data_ptr(), *(v.data_ptr() for v in tabs),
+                             x_0.numel() // B, tabs[0].shape[0], B, int(objective), int(bool(clip_x0)))
+    return _loss_sums("mf_variance_loss_f32", "mf_variance_loss_finish_f32", lambda lib, ws, n: lib.mf_variance_loss_f32(C.byref(a), ws, n, stream()), B,
+                      x_0.numel() // B, 3, x_0.device)
+
+
 def absdiff_mean_c(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """[N,C,...] fp32 x 2 -> [N,1,...]: the mean over the channels of |a - b| (mf_absdiff_mean_c_f32)"""
     _gpu(a, b)

@@ -62,6 +62,22 @@ class MfSolverNoise(C.Structure):
                 ("draw_base", C.c_int32), ("draw_stride", C.c_int32), ("B", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MfDiffuseArgs(C.Structure):
+    _fields_ = [("x_0", c_fp), ("eps", c_fp), ("x_t", c_fp), ("eps_out", c_fp), ("t", c_fp), ("sqrt_ac", c_fp), ("sqrt_1m_ac", c_fp), ("per_row", C.c_int64),
+                ("seed", C.c_uint64), ("sample_offset", C.c_int64), ("draw", C.c_int32), ("T", C.c_int32), ("B", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MfLossDesc(C.Structure):
+    _fields_ = [("B", C.c_int32), ("C", C.c_int32), ("dims", C.c_int32), ("size", C.c_int32 * 3), ("f", C.c_int32), ("draw", C.c_int32), ("seed", C.c_uint64),
+                ("sample_offset", C.c_int64)]
+
+
+class MfVarianceLossArgs(C.Structure):
+    _fields_ = ([(n, c_fp) for n in ("x_0", "x_t", "x_T", "pred", "pred_var", "t", "betas", "posterior_variance", "coef1", "coef2", "sqrt_recip_ac",
+                                     "sqrt_recipm1_ac")]
+                + [("per_row", C.c_int64), ("T", C.c_int32), ("B", C.c_int32), ("objective", C.c_int32), ("clip_x0", C.c_int32)])
+
+
 TRAJ_RECORD, TRAJ_KEEP = 0, 1
 
 
@@ -205,6 +221,13 @@ _SIGS = {
     "mf_solver_step_blend_f32": (_I, [C.POINTER(MfSolverArgs), C.POINTER(MfSchedBlend), c_fp]),
     "mf_solver_step_traj_f32": (_I, [C.POINTER(MfSolverArgs), C.POINTER(MfSolverTraj), c_fp]),
     "mf_solver_step_noise_f32": (_I, [C.POINTER(MfSolverArgs), C.POINTER(MfSolverNoise), C.POINTER(MfSchedBlend), c_fp]),
+    "mf_diffuse_rows_f32": (_I, [C.POINTER(MfDiffuseArgs), c_fp]),
+    "mf_loss_parts": (_I, [_I64]),
+    "mf_loss_workspace_bytes": (_SZ, [_I, _I64, _I]),
+    "mf_denoise_loss_f32": (_I, [c_fp, c_fp, C.POINTER(MfLossDesc), c_fp, _SZ, c_fp]),
+    "mf_denoise_loss_finish_f32": (_I, [c_fp, c_fp, _I, _I64, c_fp]),
+    "mf_variance_loss_f32": (_I, [C.POINTER(MfVarianceLossArgs), c_fp, _SZ, c_fp]),
+    "mf_variance_loss_finish_f32": (_I, [c_fp, c_fp, _I, _I64, c_fp]),
     "mf_absdiff_mean_c_f32": (_I, [c_fp, c_fp, c_fp, _I, _I, _I64, c_fp]),
     "mf_select_cells_f32": (_I, [c_fp, c_fp, c_fp, c_fp, _I, _I, _I64, c_fp]),
     "mf_window_gather_f32": (_I, [c_fp, c_fp, C.POINTER(MfWindowDesc), c_fp]),

@@ -6,7 +6,7 @@ prefixes (`noise_estimator.`, `noise_scheduler.`, `latent_embedder.`, `ema_model
 Differences, all outside the arithmetic: no streamlit/tqdm (Q16); noise comes from a NoiseSource
 (`noise=` keyword; default = device Philox keyed from torch's default CPU generator, which it advances: consecutive
 `sample()` calls differ and `torch.manual_seed(0)` before `sample()` is reproducible, like the reference harness); `shard=(rank, world)` keyword partitions the batch
-rows across GPUs with shard-invariant noise.  Training (`_step`) is out of scope.
+rows across GPUs with shard-invariant noise.  Of `_step` (:78-201) the evaluation half is mirrored (`validation_step`); training is out of scope.
 """
 from __future__ import annotations
 
@@ -995,6 +995,189 @@ class DiffusionPipeline(nn.Module):
                 pix = (mask > 0.5) if mask.is_floating_point() else (mask != 0)
                 out = K.select_cells(pix.to(torch.uint8).contiguous(), out, x)
             return (out, K.absdiff_mean_c(out, x)) if return_map else out
+
+    # ------------------------------------------------------------------ held-out denoising loss (the reference's validation step)
+    LOSSES = ("l1", "l2")
+
+    @staticmethod
+    def deep_supervision_weights(heads: int):
+        """diffusion_pipeline.py:144-146: w_i = 2^-i / sum over the horizontal prediction (i = 0) and the `heads` vertical ones"""
+        w = [1 / 2 ** i for i in range(1 + heads)]
+        tot = sum(w)
+        return [v / tot for v in w]
+
+    def _latent_extents(self, x, is_latent):
+        """the spatial extents of the latent of `x`, known before the encoder runs"""
+        sp, emb = tuple(x.shape[2:]), self.latent_embedder
+        if is_latent or emb is None:
+            return sp
+        return tuple(a // b for a, b in zip(sp, getattr(emb, "scale3", None) or (emb.scale,) * len(sp)))
+
+    def _check_validation(self, x, t, loss, is_latent):
+        """the argument rules of validation_step / denoising_profile, before anything touches the device -> the head pooling factors.  t: None, or
+        the timesteps as a tensor (checked for shape and dtype; for its range where it lives on the host)"""
+        if loss not in self.LOSSES:
+            raise ValueError(f"loss={loss!r}: one of {self.LOSSES}")
+        if not torch.is_tensor(x) or x.dtype != torch.float32 or not x.is_cuda or x.dim() not in (4, 5):
+            raise ValueError("x: an fp32 [B, C, spatial...] tensor on the GPU (no CPU fallback)" +
+                             (f", got {x.dtype} on {x.device} with shape {tuple(x.shape)}" if torch.is_tensor(x) else f", got {type(x).__name__}"))
+        if self.estimator_objective not in ("x_T", "x_0"):
+            raise ValueError("Unknown Objective")
+        if t is not None:
+            T = self.noise_scheduler.T
+            if t.dtype not in (torch.int32, torch.int64):
+                raise ValueError(f"t: an int32 or int64 tensor, got {t.dtype}")
+            if tuple(t.shape) != (x.shape[0],):
+                raise ValueError(f"t: one timestep per row, shape ({x.shape[0]},), got {tuple(t.shape)}")
+            if not t.is_cuda and t.numel() and (int(t.min()) < 0 or int(t.max()) >= T):
+                raise ValueError(f"t: timesteps in [0, {T}), got {int(t.min())} .. {int(t.max())}")
+        sp = self._latent_extents(x, is_latent)
+        factors = []
+        for i, f in enumerate(getattr(self._estimator(), "head_factors", [])):
+            if len(set(f)) != 1 or any(s % f[0] for s in sp):
+                raise ValueError(f"x: deep-supervision head {i} is smaller than the latent {sp} by {f} per axis: the area-pooled target needs one integer factor that "
+                                 "divides every side")
+            factors.append(f[0])
+        return factors
+
+    def _validation_rows(self, z0, condition, t32, noise, loss, factors):
+        """one estimator pass on z0 diffused to t32 with the next draw of `noise` (begun) -> per-row fp64 [B] tensors: loss, l1, l2 and, with
+        estimate_variance, variance and variance_scale.  Nothing waits for the device."""
+        sch, est = self.noise_scheduler, self._estimator()
+        B, per = z0.shape[0], z0.numel() // z0.shape[0]
+        obj_xT = self.estimator_objective == "x_T"
+        draw_no = getattr(noise, "draw_index", 0)
+        x_t, eps = sch.diffuse_rows(z0, t32, noise, want_eps=self.estimate_variance)
+        philox = None if eps is not None else (noise._seed, draw_no, noise.sample_offset)   # (a Philox draw that was never stored)
+        tl = t32.to(torch.long)
+        self_cond = x_t if self.use_self_conditioning else None   # (Q11: the estimator only asks whether it is None)
+        if self.estimate_variance:
+            h, y_ver = est.features(x_t, tl, condition, self_cond)
+            c = est.out_ch
+            pred, pred_var = est.outc(h, rows=slice(0, c)), est.outc(h, rows=slice(c, 2 * c))
+        else:
+            (pred, y_ver), pred_var = est(x_t, tl, condition=condition, self_cond=self_cond), None
+        if len(y_ver) != len(factors):
+            raise RuntimeError(f"the estimator returned {len(y_ver)} deep-supervision heads, {len(factors)} expected")
+
+        def sums(p):   # [B, 2] = (sum |d|, sum d^2) against the target, area-pooled onto p
+            p = p.contiguous()
+            if obj_xT and philox is not None:
+                return K.denoise_loss(p, philox=philox, target_shape=z0.shape)
+            return K.denoise_loss(p, target=eps if obj_xT else z0)
+
+        k = self.LOSSES.index(loss)
+        w = self.deep_supervision_weights(len(y_ver))
+        hor = sums(pred) / per
+        rows = {"l1": hor[:, 0], "l2": hor[:, 1]}
+        total = w[0] * hor[:, k]
+        if self.estimate_variance:
+            tb = sch.device_tables(z0.device)
+            v = K.variance_loss(z0, x_t, eps, pred.contiguous(), pred_var.contiguous(), t32, tb, 0 if obj_xT else 1, self.clip_x0) / per
+            rows["variance"] = torch.where(t32 == 0, v[:, 1], v[:, 0])      # t == 0 ? nll : kl (diffusion_pipeline.py:172)
+            rows["variance_scale"] = v[:, 2]
+            total = total + rows["variance"]
+        for i, p in enumerate(y_ver):
+            if tuple(p.shape[2:]) != tuple(s // factors[i] for s in z0.shape[2:]):
+                raise RuntimeError(f"deep-supervision head {i} has extents {tuple(p.shape[2:])}, the latent {tuple(z0.shape[2:])} over {factors[i]} expected")
+            total = total + w[i + 1] * (sums(p)[:, k] / (p.numel() // B))
+        rows["loss"] = total
+        return rows
+
+    @torch.no_grad()
+    def validation_step(self, x, condition=None, *, t=None, noise: Optional[NoiseSource] = None, loss="l1", is_latent=False,
+                        encode_noise: Optional[NoiseSource] = None, per_sample=False):
+        """The held-out denoising loss: `_step` of the reference at state != 'train' (diffusion_pipeline.py:78-201), what it logs as val/loss,
+        val/L1, val/L2 and val/variance_loss -- line by line:
+          x_0 = x (is_latent=True: the model's own latent, taken as it is), else latent_embedder.encode(x) -- a VAE's sample, drawn from
+          `encode_noise` as in sample_from -- and 2 x_0 - 1 with do_input_centering (:84-90);
+          t: one timestep per row (:99), x_T = draw #0 of `noise`, x_t = estimate_x_t(x_0, t, x_T);
+          the EMA estimator with use_ema (:102-105); ONE estimator pass (:126).  With use_self_conditioning the reference runs a first pass whose
+          result only decides that self_cond is not None (Q11: the estimator then concatenates x_t itself); that pass is skipped here;
+          loss = w_0 L(pred, target) + variance_loss + sum_i w_i L(head_i, area-pooled target), L = L1 (`loss="l1"`, the reference's default
+          L1Loss) or MSE ("l2"), w_i = 2^-i / sum (:142-183); L1 and L2 of the horizontal prediction (:189-190).
+        The reference's coin flip that drops the condition (classifier_free_guidance_dropout, :122) belongs to the caller: the method evaluates
+        with the `condition` it is given, None being the unconditional pass.
+        Draws: t=None takes torch.randint(0, T, (B,)) from torch's CPU default generator (one call, after the encoder's draw); then `noise` --
+        a fresh PhiloxDeviceNoise when None, as in sample() -- begins and gives draw #0; draw_index == 1 afterwards.  With a device source and
+        objective 'x_T' the draw is never stored: the forward process and the loss regenerate it in registers.  A HostNoise draw is uploaded.
+        Every sum is a per-row fp64 sum in a fixed order (K.denoise_loss, K.variance_loss): a row's figures do not depend on the batch it is
+        in.  A mean is the row's sum divided in fp64, a batch mean the mean of the row means.  Returns 0-dim fp64 device tensors `loss`, `L1`,
+        `L2` (+ `variance_loss`, `variance_scale` with estimate_variance); per_sample=True adds the [B] tensors `loss_rows`, `l1_rows`, `l2_rows`
+        (+ `variance_rows`) and the `t` used (int64).  The method never waits for the device.
+        ValueError, naming the argument, before anything touches the device: t of the wrong shape or dtype, or -- where t lives on the host --
+        outside [0, T); an unknown loss; x not fp32 or not on the GPU; a deep-supervision head whose side does not divide the latent's."""
+        if t is not None and not torch.is_tensor(t):
+            t = torch.as_tensor(t)
+        factors = self._check_validation(x, t, loss, is_latent)
+        dev, B = x.device, x.shape[0]
+        with torch.cuda.device(dev):
+            z0 = self._input_latent(x, is_latent, encode_noise)
+            if t is None:
+                t = torch.randint(0, self.noise_scheduler.T, (B,))
+            t32 = t.to(device=dev, dtype=torch.int32)
+            if noise is None:
+                noise = default_noise()
+            noise.begin(B, dev)
+            rows = self._validation_rows(z0, condition, t32, noise, loss, factors)
+        out = {"loss": rows["loss"].mean(), "L1": rows["l1"].mean(), "L2": rows["l2"].mean()}
+        if self.estimate_variance:
+            out["variance_loss"], out["variance_scale"] = rows["variance"].mean(), rows["variance_scale"].mean()
+        if per_sample:
+            out.update(loss_rows=rows["loss"], l1_rows=rows["l1"], l2_rows=rows["l2"], t=t32.to(torch.long))
+            if self.estimate_variance:
+                out["variance_rows"] = rows["variance"]
+        return out
+
+    @torch.no_grad()
+    def denoising_profile(self, x, condition=None, *, timesteps=None, draws=1, noise: Optional[NoiseSource] = None, loss="l1", is_latent=False, batch=None):
+        """The denoising loss of every image at every listed timestep: validation_step's figures per (timestep, image), averaged over `draws`
+        draws -> {"t": [K] int64, "loss": [K, N], "L1": [K, N], "L2": [K, N], "score": [N]} as CPU fp64 tensors; score is an image's loss averaged
+        over the timesteps (how well the model explains it: large = unusual).  timesteps: default the 20-point log-SNR grid
+        loop_timesteps(20, True, "logsnr").  The input is encoded ONCE; then for timestep k and draw d every image is diffused with draw number
+        k * draws + d of `noise` (rows keep their index in x, so `batch` -- rows per estimator pass, default all -- does not change a figure) and
+        evaluated as validation_step(t = timesteps[k]) evaluates it.  One host sync, at the end."""
+        sch = self.noise_scheduler
+        if timesteps is None:
+            timesteps = sch.loop_timesteps(20, True, "logsnr")[0]
+        ts = [int(v) for v in timesteps]
+        if not ts or any(v < 0 or v >= sch.T for v in ts):
+            raise ValueError(f"timesteps: a non-empty list of timesteps in [0, {sch.T}), got {ts}")
+        if not (isinstance(draws, int) and draws >= 1):
+            raise ValueError(f"draws={draws!r}: a positive integer")
+        N = x.shape[0] if torch.is_tensor(x) else 0
+        batch = N if batch is None else int(batch)
+        if batch < 1:
+            raise ValueError(f"batch={batch!r}: a positive integer")
+        factors = self._check_validation(x, None, loss, is_latent)
+        from .noise import PhiloxDeviceNoise
+
+        dev = x.device
+        with torch.cuda.device(dev):
+            z0 = self._input_latent(x, is_latent, None)
+            if noise is None:
+                noise = default_noise()
+            noise.begin(N, dev)
+            device_draw = isinstance(noise, PhiloxDeviceNoise)
+            acc = torch.zeros((len(ts), 3, N), dtype=torch.float64, device=dev)
+            for k, tk in enumerate(ts):
+                for d in range(draws):
+                    eps = None if device_draw else noise.draw(tuple(z0.shape))      # (a host source draws in sequence: number k * draws + d)
+                    for lo in range(0, N, batch):
+                        hi = min(N, lo + batch)
+                        if device_draw:   # the same key, the rows' own sample indices, draw number k * draws + d
+                            src = PhiloxDeviceNoise(noise._seed)
+                            src.begin(hi - lo, dev, sample_offset=noise.sample_offset + lo)
+                            src.draw_index = k * draws + d
+                        else:
+                            src = eps[lo:hi]
+                        t32 = torch.full((hi - lo,), tk, dtype=torch.int32, device=dev)
+                        r = self._validation_rows(z0[lo:hi], None if condition is None else condition[lo:hi], t32, src, loss, factors)
+                        acc[k, :, lo:hi] += torch.stack((r["loss"], r["l1"], r["l2"]))
+            if device_draw:
+                noise.draw_index = len(ts) * draws
+            host = (acc / draws).cpu()                                              # the one host sync
+        return {"t": torch.tensor(ts, dtype=torch.long), "loss": host[:, 0], "L1": host[:, 1], "L2": host[:, 2], "score": host[:, 0].mean(0)}
 
     @torch.no_grad()
     def interpolate(self, img1, img2, i=None, condition=None, lam=0.5, noise: Optional[NoiseSource] = None, **kwargs):

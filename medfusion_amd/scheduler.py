@@ -405,6 +405,39 @@ class GaussianNoiseScheduler(BasicNoiseScheduler):
             noise = self.x_final(x_t)
         return K.rows_axpby(mean, None, noise, std.to(x_t.device)), x_0
 
+    def device_tables(self, device) -> dict:
+        """the fp32 buffers on `device` by name, uploaded once per device (again when a buffer was modified): what the kernels that take a
+        timestep per row from the device index (diffuse_rows, K.variance_loss) -- no per-call gather on the host"""
+        device = torch.device(device)
+        cache = self.__dict__.setdefault("_device_tables", {})
+        key = tuple(getattr(self, n)._version for n in self.TABLES)
+        hit = cache.get(device)
+        if hit is None or hit[0] != key:
+            hit = cache[device] = (key, {n: v.to(device).contiguous() for n, v in self.host_tables().items()})
+        return hit[1]
+
+    def diffuse_rows(self, x_0, t, noise, want_eps: bool = False):
+        """estimate_x_t (gaussian_scheduler.py:61-77) with t per row in ONE launch and no host gather -> (x_t, eps | None).  t: int32 [B] on
+        x_0's device.  noise: the draw as a tensor of x_0's shape, or a NoiseSource that has begun: its next draw (draw_index advances by one).  A
+        PhiloxDeviceNoise is drawn inside the launch and stored only with want_eps; where the launch cannot draw (elements per sample not a
+        multiple of 4, an unaligned tensor) and for every other source the draw is made first and read back as a tensor."""
+        from .noise import PhiloxDeviceNoise
+
+        x_0 = x_0.contiguous()
+        tb = self.device_tables(x_0.device)
+        a, c = tb["sqrt_alphas_cumprod"], tb["sqrt_one_minus_alphas_cumprod"]
+        if torch.is_tensor(noise):
+            return K.diffuse_rows(x_0, t, a, c, eps=noise.contiguous()), noise
+        if isinstance(noise, PhiloxDeviceNoise):
+            x_t = torch.empty_like(x_0)
+            eps = torch.empty_like(x_0) if want_eps else None
+            if K.philox_in_launch_ok(x_0, x_t, eps):
+                K.diffuse_rows(x_0, t, a, c, philox=(noise._seed, noise.draw_index, noise.sample_offset), eps_out=eps, out=x_t)
+                noise.draw_index += 1
+                return x_t, eps
+        eps = noise.draw(tuple(x_0.shape))
+        return K.diffuse_rows(x_0, t, a, c, eps=eps), eps
+
     def sample(self, x_0):
         """scheduler_base.py:20-24 (the training-side entry of the forward process; kept for API completeness): one random t in [0, T) per
         row (torch's generator of x_0's device, like the reference), x_T = x_final(x_0), returns (x_t, x_T, t)."""

@@ -179,6 +179,10 @@ class UNet(nn.Module):
         self.outc_ver = nn.ModuleList([
             zero_module(UnetOutBlock_(spatial_dims, hid_chs[i] + hid_chs[i - 1], out_ch, dropout=None)) for i in range(2, deep_supervision + 2)])
 
+        # per head of y_ver, the factor per axis between the input's extents and the head's (the strides above it multiplied up)
+        axes = lambda s: tuple(s) if isinstance(s, (list, tuple)) else (s,) * spatial_dims
+        self.head_factors = [tuple(math.prod(axes(s)[a] for s in strides[:i]) for a in range(spatial_dims)) for i in range(2, deep_supervision + 2)]
+
         # all local embedders (Swish -> Linear(E, Cout)) batched into ONE GEMM per forward
         self._emb_blocks = [m for m in self.modules() if isinstance(m, (_EmbBlock, B3._EmbBlock)) and hasattr(m, "local_embedder")]
         self._emb_cache_key = None
