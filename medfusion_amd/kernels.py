@@ -665,11 +665,47 @@ def pin_wino_plan(d: L.MfConvDesc):
     return lib.mf_wino_workspace_bytes(C.byref(d)), lib.mf_wino_sync_words(C.byref(d))
 
 
+def check_wino(what: str, x1, x2, u, bias, d: L.MfConvDesc, G: int = 0, gamma=None, beta=None, residual=None, emb=None, emb_stride: int = 0) -> None:
+    """The sizes mf_conv2d_wino_f16x2 / mf_conv2d_wino_gn_apply_f16x2 / mf_wino_tail_f32 take on trust, against the descriptor, in the style of
+    check_conv2d: x1 / x2 are contiguous fp32 NHWC [N, Hin, Win, C1 / C2] (x2 present iff C2 > 0; a tensor that exists as pairs only still has
+    that shape), `u` holds the 16 slabs of Cout (C1 + C2) transformed weights (fp16 pairs: int32 storage; fp32; the bf16 triplets of precision 3
+    three times as many), bias / gamma / beta Cout contiguous fp32 values (gamma and beta together), the residual N Hin Win Cout values, the
+    embedding rows [N, Cout] with unit channel stride and the row stride the caller states.  G > 0: the group count of the tail divides Cout.
+    Host arithmetic on shapes only: no device call, no sync."""
+    def bad(msg):
+        raise RuntimeError(f"medfusion_amd: {what}: {msg}")
+    for name, x, ch in (("x1", x1, d.C1), ("x2", x2, d.C2)):
+        if (x is not None) != (ch > 0):
+            bad(f"{name} is {'given' if x is not None else 'missing'} but the descriptor has {ch} channels for it")
+        if x is not None and (tuple(x.shape) != (d.N, d.Hin, d.Win, ch) or x.dtype != torch.float32 or not x.is_contiguous()):
+            bad(f"{name} {tuple(x.shape)} {x.dtype} must be contiguous fp32 NHWC of the descriptor's N Hin Win C = {(d.N, d.Hin, d.Win, ch)}")
+    want = 16 * d.Cout * (d.C1 + d.C2) * (3 if d.precision == 3 else 1)
+    udt = {5: torch.int32, 3: torch.int16}.get(d.precision, torch.float32)   # fp16 pairs / bf16 triplets are opaque integer storage
+    if u is None or u.numel() != want or not u.is_contiguous() or u.dtype != udt:
+        bad(f"the transformed weights hold {None if u is None else (u.numel(), u.dtype)}, 16 Cout (C1 + C2) = 16 {d.Cout} ({d.C1} + {d.C2})"
+            f"{' in three bf16 terms' if d.precision == 3 else ''} needs {want} contiguous {udt} values")
+    for name, t in (("bias", bias), ("gamma", gamma), ("beta", beta)):
+        if t is not None and (t.numel() != d.Cout or t.dtype != torch.float32 or not t.is_contiguous()):
+            bad(f"{name} {tuple(t.shape)} {t.dtype} must be contiguous fp32 of Cout = {d.Cout} values")
+    if (gamma is None) != (beta is None):
+        bad("gamma and beta go together")
+    if G and (G < 0 or d.Cout % G):
+        bad(f"{G} groups do not divide Cout = {d.Cout}")
+    if residual is not None and (tuple(residual.shape) != (d.N, d.Hin, d.Win, d.Cout) or residual.dtype != torch.float32 or not residual.is_contiguous()):
+        bad(f"the residual {tuple(residual.shape)} {residual.dtype} must be contiguous fp32 NHWC {(d.N, d.Hin, d.Win, d.Cout)}")
+    if emb is not None:
+        if emb.dim() != 2 or tuple(emb.shape) != (d.N, d.Cout) or emb.dtype != torch.float32 or emb.stride(1) != 1:
+            bad(f"the embedding {tuple(emb.shape)} {emb.dtype} (strides {emb.stride()}) must be fp32 rows [N, Cout] = {(d.N, d.Cout)} with unit channel stride")
+        if emb_stride % 4 or emb_stride < d.Cout or (d.N > 1 and emb_stride != emb.stride(0)):
+            bad(f"emb_stride {emb_stride} must be the embedding's row stride {emb.stride(0)}, a multiple of 4 and >= Cout = {d.Cout}")
+
+
 def conv2d_wino_f16x2(x1: torch.Tensor, u_split, bias: Optional[torch.Tensor], d: L.MfConvDesc, x2: Optional[torch.Tensor] = None,
                       gn_groups: int = 0, gn_parts: int = 0, pinned=None):
     """The 3x3 stride-1 convolution `d` in its Winograd form (mf_conv2d_wino_f16x2): u_split = split_weight_f16x2(wino_pack_weight(w)).
     Returns y fp32 NHWC, or (y, partial [N, parts, G, 2]) when gn_groups > 0 (gn_parts = wino_gn_parts(d, G) > 0)."""
     uh, umax = u_split
+    check_wino("conv2d_wino_f16x2", x1, x2, uh, bias, d, gn_groups)
     _gpu(x1, x2, uh, bias)
     lib = L.load()
     v1, b1, v2, b2 = _wino_operands(x1, x2)
@@ -703,6 +739,7 @@ def conv2d_wino_gn_apply(x1: torch.Tensor, u_split, bias: Optional[torch.Tensor]
     guest = dict(w_split, bias, d, pinned): conv_res of the same ResBlock (a 1x1 on the same x1 | x2) in the GEMM's grid; its measured output IS the
     residual of the tail (`residual` must be None then)."""
     uh, umax = u_split
+    check_wino("conv2d_wino_gn_apply", x1, x2, uh, bias, d, G, gamma, beta, residual, emb, emb_stride)
     _gpu(x1, x2, uh, bias, gamma, beta, residual, emb)
     lib = L.load()
     v1, b1, v2, b2 = _wino_operands(x1, x2)
@@ -765,6 +802,7 @@ def conv2d_wino_gn_apply_f32(x1: torch.Tensor, u_packed: torch.Tensor, bias: Opt
     """conv3x3 -> GroupNorm -> Swish -> + residual -> + emb on the Winograd form of an EXACT arithmetic (d.precision 0 or 3): the 16 component GEMMs run on
     that arithmetic's own implicit-GEMM kernel (mf_conv2d_f32 on the upsample = 3 descriptor; u_packed = U = G g G^T [16, Cout, 1, 1, Cin], pre-split for
     precision 3), the transforms and the tail are fp32.  Returns y fp32 NHWC; want_wino: it also carries V of y for the next Winograd convolution."""
+    check_wino("conv2d_wino_gn_apply_f32", x1, x2, u_packed, bias, d, G, gamma, beta, residual, emb, emb_stride)
     _gpu(x1, x2, u_packed, bias, gamma, beta, residual, emb)
     lib = L.load()
     n, h, w, c1 = x1.shape

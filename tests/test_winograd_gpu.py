@@ -43,8 +43,7 @@ WINO_CASES = [
     (16, 8, 8, 1024, 1024, 1024), # published out-block, K = 2048: split-K inside the launch
     (16, 16, 16, 512, 0, 512),    # published 16 x 16 level
 ]
-TILES = {31: (128, 256), 32: (256, 128), 33: (128, 128), 34: (128, 128), 35: (256, 64), 36: (128, 64), 37: (64, 256), 51: (128, 128), 52: (128, 128),
-         53: (64, 128), 54: (128, 64)}
+from tests.wino_cases import TILES   # noqa: E402  tile -> (BM, BN) of the tiles a component GEMM can run on (restated from kTiles2 there)
 
 
 def test_wino_weight_and_input_transforms(dev):
