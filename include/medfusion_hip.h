@@ -967,6 +967,63 @@ typedef struct MfVarianceLossArgs {
 int mf_variance_loss_f32(const MfVarianceLossArgs* a, void* workspace, size_t workspace_bytes, void* stream);
 int mf_variance_loss_finish_f32(const void* workspace, double* out, int B, int64_t per_row, void* stream);
 
+/* Guidance stage (additive to ABI 250): what stands between the estimator and the scheduler / solver step of a denoise iteration when the guidance
+ * scale follows a schedule, the guided prediction is rescaled (Lin et al. 2024, section 3.4) or the x_0 estimate is thresholded dynamically (Saharia
+ * et al. 2022).  All tensors fp32, B rows of n contiguous elements.  No host synchronisation, no allocation, capture-safe; the launch sequence is
+ * fixed by (B, n, stages).  Per row b, with the table row S = table[step_dev ? *step_dev : step]:
+ *   1. p = fl(pu + fl(S.g fl(pc - pu))) -- the chain of the step launches; pred_uncond == NULL: p = pred.
+ *   2. MF_GUIDE_RESCALE: sigma_pos, sigma_cfg = the unbiased standard deviations of pc and p over the row, from fp64 sums of the fp32 values about a
+ *      pivot (an element of the row), added in a fixed order; k = fl32(S.phi sigma_pos / sigma_cfg + (1 - S.phi)) evaluated in fp64 and rounded once,
+ *      k = 1 when sigma_cfg == 0 or n < 2; p <- fl(k p).
+ *   3. MF_GUIDE_THRESHOLD: x0 = fl(fl(a x_t) - fl(b p)) for objective 0 ('x_T'; a = S.sqrt_recip_ac, b = S.sqrt_recipm1_ac), x0 = p for objective 1.
+ *      v = the row's |x0| in ascending order of their bit patterns (torch.sort's order on finite values; a NaN sorts above +inf and is one more large
+ *      magnitude, it does not poison the row as it does torch.quantile); pos = S.q (n - 1) in fp64 (S.q as the table's fp32 holds it), lo = floor(pos),
+ *      hi = ceil(pos); s = fl32(v[lo] + (v[hi] - v[lo]) (pos - lo)) in fp64 (v[lo] itself when hi == lo); s <- max(s, 1) (a NaN s gives 1), and
+ *      min(s, S.s_max) when S.s_max > 0.  x0' = clamp_keep_nan(x0, -s, s) / s; p <- x0' for objective 1, fl(fl(fl(a x_t) - x0') / b) for objective 0:
+ *      the prediction that the step turns back into x0'.  v[lo] and v[hi] are EXACT: a most-significant-digit-first radix select (8-bit digits, four
+ *      passes, integer counts through LDS atomics) on the non-negative bit patterns, both ranks at once.
+ *   pred_out = p (it may be `pred` itself, nothing else); scale_out[b] = k (1 without the stage), limit_out[b] = s (0 without the stage), optional.
+ * A caller then runs its step launch on pred_out with pred_uncond = NULL.
+ * n <= MF_GUIDE_ROW_ONE_WG: ONE launch of B workgroups, the row held in registers.  Longer rows: workgroups of mf_guide_workspace_bytes' geometry
+ * (at most 64 per row) in a fixed sequence -- combine (+ partial sums), then with the threshold four counting passes, then the apply pass: 1 launch
+ * without a stage, 2 with the rescale alone, 6 with the threshold -- through a caller-owned workspace that no launch expects zeroed.  16-byte vectors
+ * when every tensor is 16-byte aligned and n % 4 == 0, element by element otherwise: the same elements in the same lanes.  A row's bits depend on
+ * its data and its table row only: not on B, the row's place, the load path or the launch.  No floating-point atomics, no global atomics. */
+#define MF_GUIDE_ROW_ONE_WG 8192
+#define MF_GUIDE_RESCALE 1
+#define MF_GUIDE_THRESHOLD 2
+typedef struct MfGuideStep {
+  float g;                   /* guidance scale of this executed iteration */
+  float phi;                 /* rescale weight in [0, 1] (read with MF_GUIDE_RESCALE) */
+  float q;                   /* quantile in (0, 1] (read with MF_GUIDE_THRESHOLD) */
+  float s_max;               /* cap of the limit, > 1; <= 0: none */
+  float sqrt_recip_ac;       /* of the iteration's timestep, as in its MfSchedStep / MfSolverStep row */
+  float sqrt_recipm1_ac;
+  int32_t t;
+  int32_t reserved;          /* 0 */
+} MfGuideStep;
+typedef struct MfGuideArgs {
+  const float* x_t;          /* read with MF_GUIDE_THRESHOLD and objective 0; else may be NULL */
+  const float* pred;         /* the conditional prediction (the only one without a pair) */
+  const float* pred_uncond;  /* or NULL: no pair */
+  float* pred_out;           /* may be `pred` */
+  float* scale_out;          /* [B] or NULL */
+  float* limit_out;          /* [B] or NULL */
+  const MfGuideStep* table;  /* device, one row per executed iteration */
+  const int32_t* step_dev;   /* device step counter, or NULL: `step` */
+  void* workspace;           /* mf_guide_workspace_bytes(B, n) bytes, 8-byte aligned; may be NULL when that is 0 or stages == 0 */
+  uint64_t workspace_bytes;
+  int64_t n;                 /* elements per row, <= 2^31 - 1 */
+  int32_t step;
+  int32_t objective;         /* 0: 'x_T', 1: 'x_0' */
+  int32_t B;                 /* <= 65535 */
+  int32_t stages;            /* MF_GUIDE_RESCALE | MF_GUIDE_THRESHOLD */
+  int32_t reserved;          /* 0 */
+  int32_t reserved2;         /* 0 */
+} MfGuideArgs;
+size_t mf_guide_workspace_bytes(int B, int64_t n);
+int mf_guide_f32(const MfGuideArgs* a, void* stream);
+
 /* ------------------------------------------------------------------ built-in launch timing (bench / roofline)
  * When enabled every launch is bracketed by hipEvents on its own stream and attributed to a kernel family.
  * NOT capture-safe; off by default. */

@@ -1875,6 +1875,53 @@ def variance_loss(x_0: torch.Tensor, x_t: torch.Tensor, x_T: torch.Tensor, pred:
                       x_0.numel() // B, 3, x_0.device)
 
 
+def guide_table(rows, device) -> torch.Tensor:
+    """the device table of the guidance stage: a list of L.MfGuideStep, one per executed iteration -> uint8 tensor"""
+    arr = (L.MfGuideStep * len(rows))(*rows)
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).clone().to(device)
+
+
+def guide_workspace(B: int, n: int, device) -> Optional[torch.Tensor]:
+    """the caller-owned workspace of mf_guide_f32 for B rows of n elements (None: a row fits one workgroup, none is needed).  A tensor of its own,
+    not the per-stream scratch: it is made before a recorded iteration and must not move under it."""
+    need = L.load().mf_guide_workspace_bytes(B, n)
+    return torch.empty(need, dtype=torch.uint8, device=device) if need else None
+
+
+def guide(pred: torch.Tensor, table: torch.Tensor, *, pred_uncond: Optional[torch.Tensor] = None, x_t: Optional[torch.Tensor] = None, step=0,
+          objective: int = 0, stages: int = 0, out: Optional[torch.Tensor] = None, scale_out: Optional[torch.Tensor] = None,
+          limit_out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The guidance stage on B rows (mf_guide_f32; include/medfusion_hip.h): the classifier-free combine with the scale of table row `step`, then
+    -- stages & L.GUIDE_RESCALE -- the guidance rescale and -- stages & L.GUIDE_THRESHOLD -- dynamic thresholding of the x_0 estimate.  pred /
+    pred_uncond / x_t: fp32 [B, ...] tensors of one shape (they may start at any 4-byte offset); step: a host int, or an int32 device tensor
+    (the loop's counter); out: None = in place on `pred`.  scale_out / limit_out: fp32 [B], the k and s used.  workspace: guide_workspace(B, n),
+    made here when None and needed (not inside a recorded iteration).  Returns `out`."""
+    what = "guide"
+    _dense(what, "pred", pred)
+    B = pred.shape[0]
+    n = pred.numel() // max(1, B)
+    for name, v in (("pred_uncond", pred_uncond), ("x_t", x_t), ("out", out)):
+        if v is not None:
+            _dense(what, name, v, shape=pred.shape, written=name == "out")
+    for name, v in (("scale_out", scale_out), ("limit_out", limit_out)):
+        if v is not None:
+            _dense(what, name, v, shape=(B,), written=True)
+    step_dev = step if torch.is_tensor(step) else None
+    if step_dev is not None:
+        _dense(what, "step", step_dev, dtype=torch.int32)
+    _gpu(pred, table, pred_uncond, x_t, out, scale_out, limit_out, step_dev, workspace)
+    if out is None:
+        out = pred
+    if workspace is None and stages:
+        workspace = guide_workspace(B, n, pred.device)
+    _drop_outputs((out,))
+    a = L.MfGuideArgs(_ptr(x_t), pred.data_ptr(), _ptr(pred_uncond), out.data_ptr(), _ptr(scale_out), _ptr(limit_out), table.data_ptr(), _ptr(step_dev),
+                      _ptr(workspace), 0 if workspace is None else workspace.numel() * workspace.element_size(), n, 0 if step_dev is not None else int(step),
+                      int(objective), B, int(stages), 0, 0)
+    L.check(L.load().mf_guide_f32(C.byref(a), stream()), "mf_guide_f32")
+    return out
+
+
 def absdiff_mean_c(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """[N,C,...] fp32 x 2 -> [N,1,...]: the mean over the channels of |a - b| (mf_absdiff_mean_c_f32)"""
     _gpu(a, b)

@@ -78,6 +78,21 @@ class MfVarianceLossArgs(C.Structure):
                 + [("per_row", C.c_int64), ("T", C.c_int32), ("B", C.c_int32), ("objective", C.c_int32), ("clip_x0", C.c_int32)])
 
 
+GUIDE_ROW_ONE_WG = 8192
+GUIDE_RESCALE, GUIDE_THRESHOLD = 1, 2
+
+
+class MfGuideStep(C.Structure):
+    _fields_ = [("g", C.c_float), ("phi", C.c_float), ("q", C.c_float), ("s_max", C.c_float), ("sqrt_recip_ac", C.c_float), ("sqrt_recipm1_ac", C.c_float),
+                ("t", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MfGuideArgs(C.Structure):
+    _fields_ = [("x_t", c_fp), ("pred", c_fp), ("pred_uncond", c_fp), ("pred_out", c_fp), ("scale_out", c_fp), ("limit_out", c_fp), ("table", c_fp),
+                ("step_dev", c_fp), ("workspace", c_fp), ("workspace_bytes", C.c_uint64), ("n", C.c_int64), ("step", C.c_int32), ("objective", C.c_int32),
+                ("B", C.c_int32), ("stages", C.c_int32), ("reserved", C.c_int32), ("reserved2", C.c_int32)]
+
+
 TRAJ_RECORD, TRAJ_KEEP = 0, 1
 
 
@@ -228,6 +243,8 @@ _SIGS = {
     "mf_denoise_loss_finish_f32": (_I, [c_fp, c_fp, _I, _I64, c_fp]),
     "mf_variance_loss_f32": (_I, [C.POINTER(MfVarianceLossArgs), c_fp, _SZ, c_fp]),
     "mf_variance_loss_finish_f32": (_I, [c_fp, c_fp, _I, _I64, c_fp]),
+    "mf_guide_workspace_bytes": (_SZ, [_I, _I64]),
+    "mf_guide_f32": (_I, [C.POINTER(MfGuideArgs), c_fp]),
     "mf_absdiff_mean_c_f32": (_I, [c_fp, c_fp, c_fp, _I, _I, _I64, c_fp]),
     "mf_select_cells_f32": (_I, [c_fp, c_fp, c_fp, c_fp, _I, _I, _I64, c_fp]),
     "mf_window_gather_f32": (_I, [c_fp, c_fp, C.POINTER(MfWindowDesc), c_fp]),

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import copy
 import ctypes
+import math
 import os
 from typing import Optional
 
@@ -57,6 +58,29 @@ class _PureLaunchGuard(torch.utils._python_dispatch.TorchDispatchMode):
             if touches and not (name == "aten::contiguous" and out is (args[0] if args else None)):
                 self.foreign.append(name)
         return out
+
+
+class _GuideStage:
+    """The guidance stage of one loop (mf_guide_f32): its device table -- one MfGuideStep row per EXECUTED iteration -- its workspace and the
+    [B] tensors that receive the k and s of the last iteration, all made before the loop starts.  apply() is one library call (one launch where a
+    row fits one workgroup), in place on the estimator's prediction; the step comes from the loop's device counter where there is one."""
+
+    def __init__(self, spec, g_scales, recs, x_t, objective):
+        phi, q, s_max, schedule = spec
+        dev, B = x_t.device, x_t.shape[0]
+        rows = [L.MfGuideStep(float(g), float(phi), 0.0 if q is None else float(q), 0.0 if s_max is None else float(s_max), r.sqrt_recip_ac,
+                              r.sqrt_recipm1_ac, int(r.t), 0) for g, r in zip(g_scales, recs)]
+        self.table = K.guide_table(rows, dev)
+        self.stages = (L.GUIDE_RESCALE if phi > 0 else 0) | (L.GUIDE_THRESHOLD if q is not None else 0)
+        self.pair = schedule is not None          # (a schedule always evaluates the classifier-free pair)
+        self.objective = objective
+        self.workspace = K.guide_workspace(B, x_t.numel() // B, dev) if self.stages else None
+        self.scale = torch.ones(B, dtype=torch.float32, device=dev)
+        self.limit = torch.zeros(B, dtype=torch.float32, device=dev)
+
+    def apply(self, x_t, pred, pred_uncond, step):
+        return K.guide(pred, self.table, pred_uncond=pred_uncond, x_t=x_t, step=step, objective=self.objective, stages=self.stages,
+                       scale_out=self.scale, limit_out=self.limit, workspace=self.workspace)
 
 
 class EMAModel(nn.Module):
@@ -106,6 +130,8 @@ class DiffusionPipeline(nn.Module):
         self.last_cmdlist_foreign_ops = []      # ATen operators that put device work into the recorded iteration (replay refused)
         self.time_cmdlist = False               # measurement aid: time the host side of one replayed iteration (costs a device sync)
         self.last_cmdlist_host_ms = None
+        self.last_guide_scale = None            # [B] device tensors: the rescale factor k and the threshold s of the last loop's LAST iteration
+        self.last_guide_limit = None            # (None: that loop ran without the guidance stage)
         self.use_ema = use_ema
         if use_ema:
             self.ema_model = EMAModel(self.noise_estimator, **ema_kwargs)
@@ -124,21 +150,29 @@ class DiffusionPipeline(nn.Module):
     def _estimator(self):
         return self.ema_model.averaged_model if self.use_ema else self.noise_estimator
 
-    def _predict(self, x_t, t, condition, self_cond, guidance_scale, un_cond, emb=None, win=None):
+    def _predict(self, x_t, t, condition, self_cond, guidance_scale, un_cond, emb=None, win=None, guide=None, step=0, pair=False):
         """UNet call(s) of forward :240-253.  Returns (pred, pred_uncond|None, pred_var|None).
         emb = (table, i, cols_cond, cols_uncond, cols_uncond ++ cols_cond): the loop's precomputed embeddings
         (UNet.precompute_embeddings), or None.
         win: a WindowPlan (windowed denoising, _window_plan) -- x_t is the canvas [B, ...]; it is cropped into B * M windows (one launch,
         K.window_gather), the estimator runs on those rows -- t, condition, un_cond and the embedding columns come with B * M rows, window m of
         sample b at row b * M + m -- and its output is merged back to canvas shape (one launch, K.window_merge; the guidance pair's 2 B M rows as
-        2 B canvas rows), so whatever follows sees canvas tensors.  The estimator is never told."""
+        2 B canvas rows), so whatever follows sees canvas tensors.  The estimator is never told.
+        guide: a _GuideStage (guidance_rescale= / dynamic_threshold= / guidance_schedule=) -- the pair is combined, rescaled and thresholded by
+        one more library call on the canvas prediction (row `step` of its table: a host int, or the loop's device counter) and the result comes
+        back as (pred, None, None): every step variant then runs as it does without a pair.  None: exactly the launches below.
+        pair: evaluate the classifier-free pair whatever the scalar guidance_scale is (a guidance schedule)."""
+        if guide is not None:
+            canvas = x_t
+            pred, pred_uncond, _ = self._predict(x_t, t, condition, self_cond, guidance_scale, un_cond, emb=emb, win=win, pair=guide.pair)
+            return guide.apply(canvas, pred, pred_uncond, step), None, None
         est = self._estimator()
         if win is not None:   # (never with a learned variance head or self-conditioning: _window_plan refuses them)
             canvas_rows, x_t = x_t.shape[0], K.window_gather(x_t, win)
             merge = lambda p: K.window_merge(p, win)
         else:
             canvas_rows, merge = x_t.shape[0], (lambda p: p)
-        cfg = (condition is not None) and (guidance_scale != 1.0)
+        cfg = (condition is not None) and (guidance_scale != 1.0 or pair)
         ec = (lambda cols: None) if emb is None else (lambda cols: est.step_embeddings(emb[0], emb[1], cols))
         if cfg:
             if self.estimate_variance:
@@ -182,6 +216,73 @@ class DiffusionPipeline(nn.Module):
 
     def _check_window(self, canvas, kwargs):
         self._window_plan(canvas, *(kwargs.get(k, d) for k, d in zip(self.WINDOW_KEYS, (None, None, "tent"))), kwargs.get("cold_diffusion", False))
+
+    # ------------------------------------------------------------------ guidance rescale, dynamic thresholding, guidance schedules
+    GUIDE_KEYS = ("guidance_rescale", "dynamic_threshold", "threshold_max", "guidance_schedule")
+
+    @staticmethod
+    def _guide_scales(schedule, ts, guidance_scale, name="guidance_schedule"):
+        """the guidance scale of every executed iteration (ts: their timesteps in execution order), on the host"""
+        if schedule is None:
+            return [float(guidance_scale)] * len(ts)
+        if callable(schedule):
+            g = [float(schedule(int(t))) for t in ts]
+        elif isinstance(schedule, (tuple, list)) and len(schedule) == 3 and schedule[0] == "interval":
+            lo, hi = float(schedule[1]), float(schedule[2])
+            if not lo <= hi:
+                raise ValueError(f"{name}={schedule!r}: ('interval', t_lo, t_hi) with t_lo <= t_hi")
+            g = [float(guidance_scale) if lo <= t <= hi else 1.0 for t in ts]
+        else:
+            try:
+                g = [float(v) for v in schedule]
+            except TypeError:
+                raise ValueError(f"{name}={schedule!r}: a sequence of floats, a callable t -> float or ('interval', t_lo, t_hi)") from None
+            if len(g) != len(ts):
+                raise ValueError(f"{name}: {len(g)} entries for {len(ts)} executed iterations (one per executed iteration, in execution order)")
+        if not all(math.isfinite(v) for v in g):
+            raise ValueError(f"{name}: a guidance scale that is not finite: {g}")
+        return g
+
+    def _guide_spec(self, kw, condition, ts, prefix=""):
+        """the rules of guidance_rescale= / dynamic_threshold= / threshold_max= / guidance_schedule= (kw: those keys, guidance_scale and
+        cold_diffusion, where present), checked on the host before anything touches the device.  ts: the timesteps of the executed iterations;
+        prefix: "source_" where edit() checks the twins of its inversion pass (the errors name the arguments the caller wrote).
+        -> (None, None) with every argument at its default, else ((phi, q, s_max, schedule), the scale of every executed iteration)"""
+        phi, q, s_max, schedule = (kw.get(k, d) for k, d in zip(self.GUIDE_KEYS, (0.0, None, None, None)))
+        rescale_name, schedule_name = prefix + "guidance_rescale", prefix + "guidance_schedule"
+        if phi is None:
+            phi = 0.0
+        if isinstance(phi, bool) or not isinstance(phi, (int, float)) or not math.isfinite(phi) or not 0.0 <= phi <= 1.0:
+            raise ValueError(f"{rescale_name}={phi!r}: a finite weight in [0, 1]")
+        if q is not None and (isinstance(q, bool) or not isinstance(q, (int, float)) or not (0.0 < q <= 1.0)):
+            raise ValueError(f"dynamic_threshold={q!r}: None or a quantile in (0, 1]")
+        if s_max is not None:
+            if isinstance(s_max, bool) or not isinstance(s_max, (int, float)) or not s_max > 1.0:
+                raise ValueError(f"threshold_max={s_max!r}: None or a cap > 1")
+            if q is None:
+                raise ValueError(f"threshold_max={s_max!r} needs dynamic_threshold=")
+            if math.isinf(s_max):
+                s_max = None
+        if phi == 0.0 and q is None and schedule is None:
+            return None, None
+        on = schedule_name if schedule is not None else rescale_name if phi > 0 else "dynamic_threshold"
+        if kw.get("cold_diffusion", False):
+            raise ValueError(f"{on}= with cold_diffusion=True: cold diffusion runs through the single-step API, which has no guidance stage")
+        if self.estimate_variance:
+            raise ValueError(f"{on}= with estimate_variance: the learned-variance path takes no guidance and is not thresholded (out of scope)")
+        g = kw.get("guidance_scale", 1.0)
+        if schedule is not None and condition is None:
+            raise ValueError(f"{schedule_name}= needs a guidance pair (condition is None)")
+        if phi > 0 and (condition is None or (schedule is None and g == 1.0)):
+            raise ValueError(f"{rescale_name}={phi!r} needs a guidance pair (a condition and guidance_scale != 1, or a schedule)")
+        return (float(phi), None if q is None else float(q), None if s_max is None else float(s_max), schedule), self._guide_scales(schedule, ts, g, schedule_name)
+
+    def _check_guide(self, kwargs, condition, steps, use_ddim):
+        """denoise() / sample(): the rules above on the grid the loop will execute, before the first draw"""
+        if any(k in kwargs for k in self.GUIDE_KEYS):
+            sampler = kwargs.get("sampler")
+            ts, _ = self.noise_scheduler.loop_timesteps(steps, use_ddim, kwargs.get("spacing") if sampler is not None else None)
+            self._guide_spec(kwargs, condition, list(reversed(ts)))
 
     @torch.no_grad()
     def forward(self, x_t, t, condition=None, self_cond=None, guidance_scale=1.0, cold_diffusion=False, un_cond=None, noise=None):
@@ -296,9 +397,19 @@ class DiffusionPipeline(nn.Module):
         (B * M rows; `condition` / `un_cond` repeated per window once, before the loop), the predictions are merged per cell with fixed weights and
         the scheduler / solver step, the inpainting select, the draws and the decode run once on the canvas, exactly as without a window: same
         draw order, same draw count, canvas-shaped draws.  Two more launches per iteration, both the library's (all three loop forms).  A window
-        equal to the canvas is the un-windowed path.  ValueError with use_self_conditioning, estimate_variance or cold_diffusion=True."""
+        equal to the canvas is the un-windowed path.  ValueError with use_self_conditioning, estimate_variance or cold_diffusion=True.
+        guidance_rescale=phi in [0, 1], dynamic_threshold=q in (0, 1] (threshold_max= caps its limit, > 1), guidance_schedule= a sequence with one
+        scale per EXECUTED iteration in execution order | a callable t -> float | ("interval", t_lo, t_hi) (guidance_scale inside, 1 outside): the
+        guidance stage (mf_guide_f32, include/medfusion_hip.h) between the estimator and the step -- the pair combined with the iteration's
+        scale, its per-sample spread brought back towards the conditional prediction's, the x_0 estimate clamped to its own per-sample quantile
+        of |x_0| and divided by it -- inside the recorded iteration, no host sync, the same bits in all three loop forms.  A schedule always
+        evaluates the pair.  Draws and draw order are unchanged.  With every argument at its default the loop issues exactly the launches it
+        issued before.  ValueError (naming the argument) before anything touches the device: values out of range, guidance_rescale or a schedule
+        without a guidance pair, a schedule of the wrong length, any of them with cold_diffusion=True or estimate_variance.  The k and s of
+        the last iteration stay in last_guide_scale / last_guide_limit ([B] device tensors)."""
         self._check_sampler(kwargs.get("sampler"), kwargs.get("spacing"), use_ddim, kwargs.get("cold_diffusion", False))
         self._check_window(tuple(x_t.shape[2:]), kwargs)
+        self._check_guide(kwargs, condition, steps, use_ddim)
         return self._denoise_guarded(x_t, steps, condition, use_ddim, noise, trace, decode, use_graph, loop, progress_cb, 0, None, kwargs)
 
     def _denoise_guarded(self, x_t, steps, condition, use_ddim, noise, trace, decode, use_graph, loop, progress_cb, start, blend, kwargs, traj=None, up=None):
@@ -348,6 +459,7 @@ class DiffusionPipeline(nn.Module):
         cold_diffusion = bool(kwargs.pop("cold_diffusion", False))
         sampler, spacing = kwargs.pop("sampler", None), kwargs.pop("spacing", None)
         window = [kwargs.pop(k, d) for k, d in zip(self.WINDOW_KEYS, (None, None, "tent"))]
+        guide_kw = {k: kwargs.pop(k) for k in self.GUIDE_KEYS if k in kwargs}
         if kwargs:
             raise TypeError(f"forward() got an unexpected keyword argument '{next(iter(kwargs))}'")
         self._check_sampler(sampler, spacing, use_ddim, cold_diffusion)
@@ -430,6 +542,13 @@ class DiffusionPipeline(nn.Module):
                 table = sch.upload_records(recs, dev)
         objective = 0 if self.estimator_objective == "x_T" else 1
         x_t = x_t.contiguous().clone()
+        guide = None
+        if guide_kw:   # (rev and recs: the executed iterations; the table's rows are indexed like the step table's)
+            # (g_scales: one guidance scale per executed iteration -- not `scales`, the draw scales of a stochastic sampler's rows)
+            spec, g_scales = self._guide_spec(dict(guide_kw, guidance_scale=guidance_scale, cold_diffusion=cold_diffusion), condition, rev)
+            if spec is not None:
+                guide = _GuideStage(spec, g_scales, recs, x_t, objective)
+        self.last_guide_scale, self.last_guide_limit = (None, None) if guide is None else (guide.scale, guide.limit)
         if cold_diffusion:
             # diffusion_pipeline.py:294 forwards the flag to forward() on every iteration: off the hot loop, so composed from the
             # single-step API (forward() takes no posterior draw in this mode; the DDIM update and its draw are those of :297-304)
@@ -459,7 +578,7 @@ class DiffusionPipeline(nn.Module):
         nz, n_buf = self._solver_noise(noise, scales, x_t, blend, noise.draw_index) if stochastic else (None, None)
         if mode in ("graph", "cmdlist"):
             self._denoise_graph(x_t, rev, recs, table, condition, guidance_scale, un_cond, use_ddim, noise, objective, cmdlist=(mode == "cmdlist"),
-                                progress_cb=progress_cb, blend=blend, solver=None if sampler is None else (hist, _traj, nz, n_buf), win=win)
+                                progress_cb=progress_cb, blend=blend, solver=None if sampler is None else (hist, _traj, nz, n_buf), win=win, guide=guide)
         elif sampler is not None:
             t_all = torch.tensor(rev, dtype=torch.float32, device=dev).reshape(-1, 1).expand(-1, Bw).contiguous()
             x0 = torch.empty_like(x_t) if (self.use_self_conditioning or trace is not None) else None
@@ -467,7 +586,7 @@ class DiffusionPipeline(nn.Module):
             emb_tab = self._hoisted_embeddings(self._estimator(), t_all[:, 0].contiguous(), condition, un_cond, Bw, dev)
             for i in range(len(rev)):
                 pred, pred_uncond, _ = self._predict(x_t, t_all[i], condition, self_cond, guidance_scale, un_cond,
-                                                     emb=None if emb_tab is None else (emb_tab[0], i, emb_tab[1], emb_tab[2], emb_tab[3]), win=win)
+                                                     emb=None if emb_tab is None else (emb_tab[0], i, emb_tab[1], emb_tab[2], emb_tab[3]), win=win, guide=guide, step=i)
                 if stochastic and i < len(rev) - 1:
                     if n_buf is None:
                         noise.draw_index += 1                          # (draw nz.draw_base + i, generated inside the launch)
@@ -489,7 +608,8 @@ class DiffusionPipeline(nn.Module):
             emb_tab = self._hoisted_embeddings(est, t_all[:, 0].contiguous(), condition, un_cond, Bw, dev)
             for i in range(len(rev)):
                 pred, pred_uncond, pred_var = self._predict(x_t, t_all[i], condition, self_cond, guidance_scale, un_cond,
-                                                            emb=None if emb_tab is None else (emb_tab[0], i, emb_tab[1], emb_tab[2], emb_tab[3]), win=win)
+                                                            emb=None if emb_tab is None else (emb_tab[0], i, emb_tab[1], emb_tab[2], emb_tab[3]), win=win, guide=guide,
+                                                            step=i)
                 noise.draw(tuple(x_t.shape), out=n_post)          # gaussian_scheduler.py:99 -- drawn on every iteration (Q3)
                 ddim = recs[i].mode == 1
                 if ddim:
@@ -526,7 +646,7 @@ class DiffusionPipeline(nn.Module):
         return (tab, cc, cu, torch.cat([cu, cc]))   # (the last: columns of the 2B-row classifier-free-guidance pair, un-guided rows first)
 
     def _denoise_graph(self, x_t, rev, recs, table, condition, guidance_scale, un_cond, use_ddim, noise, objective, cmdlist=False, progress_cb=None,
-                       blend=None, solver=None, win=None):
+                       blend=None, solver=None, win=None, guide=None):
         """The loop body as ONE captured hipGraph replayed `steps` times (BASELINE.json configs[3]) -- or, cmdlist=True, recorded by the
         library while it runs once and re-issued from C (mf_cmdlist_*: the native command list of the loop body).  Everything the
         reference reads on the host each iteration (t, alphas_cumprod[t], the t==0 test, the RNG state) is indexed by a
@@ -579,7 +699,8 @@ class DiffusionPipeline(nn.Module):
         def body():
             if emb is None:   # (with the embedding rows hoisted out of the loop the estimator never reads t)
                 K.broadcast_from_table(t_table, step_dev, t_cur)
-            pred, pred_uncond, pred_var = self._predict(x_t, t_cur, condition, None if not self.use_self_conditioning else x0, g, un_cond, emb=emb, win=win)
+            pred, pred_uncond, pred_var = self._predict(x_t, t_cur, condition, None if not self.use_self_conditioning else x0, g, un_cond, emb=emb, win=win,
+                                                        guide=guide, step=step_dev)
             if solver is not None:
                 solver_tail(pred, pred_uncond)
                 return pred
@@ -607,7 +728,7 @@ class DiffusionPipeline(nn.Module):
             if self.use_self_conditioning:
                 if emb is None:
                     K.broadcast_from_table(t_table, step_dev, t_cur)
-                pred, pu, pv = self._predict(x_t, t_cur, condition, None, g, un_cond, emb=emb)
+                pred, pu, pv = self._predict(x_t, t_cur, condition, None, g, un_cond, emb=emb, guide=guide, step=step_dev)
                 if solver is not None:
                     solver_tail(pred, pu)
                     return
@@ -720,6 +841,7 @@ class DiffusionPipeline(nn.Module):
         shape and the whole canvas is decoded in one latent_embedder.decode call."""
         self._check_sampler(kwargs.get("sampler"), kwargs.get("spacing"), kwargs.get("use_ddim", True), kwargs.get("cold_diffusion", False))
         self._check_window(tuple(img_size)[1:], kwargs)
+        self._check_guide(kwargs, condition, kwargs.get("steps"), kwargs.get("use_ddim", True))
         dev = self.device
         if dev.type != "cuda":
             raise RuntimeError("medfusion_amd.DiffusionPipeline.sample: move the pipeline to a ROCm device first (no CPU fallback)")
@@ -774,7 +896,7 @@ class DiffusionPipeline(nn.Module):
     def sample_from(self, x, strength, condition=None, *, mask=None, is_latent=False, steps=None, use_ddim=True, noise: Optional[NoiseSource] = None,
                     encode_noise: Optional[NoiseSource] = None, composite=False, shard=None, decode=True, trace=None, loop=None, use_graph=None,
                     progress_cb=None, guidance_scale=1.0, un_cond=None, sampler=None, spacing=None, window=None, window_stride=None, window_weight="tent",
-                    **kwargs):
+                    guidance_rescale=0.0, dynamic_threshold=None, threshold_max=None, guidance_schedule=None, **kwargs):
         """Image-conditioned sampling: img2img (variations of `x` at a chosen `strength`) and, with `mask`, inpainting.  A composition of the
         reference's own functions -- the training front end (diffusion_pipeline.py:84-90), GaussianNoiseScheduler.estimate_x_t
         (gaussian_scheduler.py:61-77) and the LAST k iterations of denoise's loop (:278-310):
@@ -796,7 +918,9 @@ class DiffusionPipeline(nn.Module):
         iterations, the first of them is first-order, the kept cells take the known latent at the next timestep of that grid; eps0 is the only
         draw of a deterministic sampler, a stochastic one ("ddim1", "dpmpp2m_sde") adds one draw per non-final iteration (k draws in all).
         window= / window_stride= / window_weight= as in denoise(): the input's latent is the canvas; eps0, the mask's select and the decode are
-        canvas-sized and unchanged, so the kept cells still end as z0 exactly."""
+        canvas-sized and unchanged, so the kept cells still end as z0 exactly.
+        guidance_rescale= / dynamic_threshold= / threshold_max= / guidance_schedule= as in denoise(): a schedule has one entry per EXECUTED
+        iteration (the k that the strength leaves); the stage changes the prediction only, so the kept cells still end as z0 exactly."""
         if "eta" in kwargs:
             raise TypeError("forward() got an unexpected keyword argument 'eta'")
         if kwargs.pop("cold_diffusion", False):
@@ -813,6 +937,9 @@ class DiffusionPipeline(nn.Module):
         timesteps, _ = sch.loop_timesteps(steps, use_ddim, spacing)
         asked, steps = steps, len(timesteps)
         s, k = self._strength_span(steps, strength)
+        guide_kw = dict(guidance_rescale=guidance_rescale, dynamic_threshold=dynamic_threshold, threshold_max=threshold_max, guidance_schedule=guidance_schedule)
+        spec, _ = self._guide_spec(dict(guide_kw, guidance_scale=guidance_scale), condition, list(reversed(timesteps))[s:])
+        guide_kw = guide_kw if spec is not None else {}   # (every argument at its default: the loop is called as it always was)
         if composite and (is_latent or mask is None):
             raise ValueError("composite=True needs an image input and an image-resolution mask")
         if not x.is_cuda:
@@ -865,7 +992,7 @@ class DiffusionPipeline(nn.Module):
             # (the loop rebuilds the grid from the step count: the log-SNR grid of `asked` steps is not the one of len(timesteps) steps)
             out = self._denoise_guarded(x_t, asked if sampler is not None else steps, condition, use_ddim, noise, trace, decode, use_graph, loop, progress_cb,
                                         s, blend, dict(guidance_scale=guidance_scale, un_cond=un_cond, sampler=sampler, spacing=spacing, window=window,
-                                                       window_stride=window_stride, window_weight=window_weight))
+                                                       window_stride=window_stride, window_weight=window_weight, **guide_kw))
             if composite:
                 pix = (mask > 0.5) if mask.is_floating_point() else (mask != 0)
                 out = K.select_cells(pix.to(torch.uint8).contiguous(), out, x)
@@ -913,7 +1040,7 @@ class DiffusionPipeline(nn.Module):
             noise.begin(B, dev)
         return noise
 
-    def _invert_latent(self, z0, k, steps, sampler, spacing, condition, guidance_scale, un_cond, noise, trace, loop, use_graph, progress_cb):
+    def _invert_latent(self, z0, k, steps, sampler, spacing, condition, guidance_scale, un_cond, noise, trace, loop, use_graph, progress_cb, guide_kw=None):
         """the k - 1 upward iterations from z0 -> (latent at ts[k-1], trajectory buffer [k + 1][...]).  The buffer's slots 0 AND 1 hold z0, slot
         j + 1 the latent at ts[j]: the upward step j records slot 2 + j, and the downward loop of edit() -- whose step i produces the latent at
         ts[k-2-i], and z0 once more on its last iteration -- keeps from slot k - 1 - i, both linear in the device step counter."""
@@ -922,13 +1049,13 @@ class DiffusionPipeline(nn.Module):
         traj[1].copy_(z0)
         tr = L.MfSolverTraj(traj.data_ptr(), None, 0, 0, L.TRAJ_RECORD, 2, 1, k + 1, 0)
         top = self._denoise_guarded(z0, steps, condition, True, noise, trace, False, use_graph, loop, progress_cb, 0, None,
-                                    dict(guidance_scale=guidance_scale, un_cond=un_cond, sampler=sampler, spacing=spacing), traj=tr, up=k)
+                                    dict(guidance_scale=guidance_scale, un_cond=un_cond, sampler=sampler, spacing=spacing, **(guide_kw or {})), traj=tr, up=k)
         return top, traj
 
     @torch.no_grad()
     def invert(self, x, condition=None, *, steps=None, sampler="ddim0", spacing=None, strength=1.0, is_latent=False, guidance_scale=1.0, un_cond=None,
                loop=None, use_graph=None, progress_cb=None, trace=None, return_trajectory=False, encode_noise: Optional[NoiseSource] = None,
-               noise: Optional[NoiseSource] = None, **kwargs):
+               noise: Optional[NoiseSource] = None, guidance_rescale=0.0, dynamic_threshold=None, threshold_max=None, guidance_schedule=None, **kwargs):
         """DDIM inversion: the probability-flow ODE of a deterministic sampler carried UPWARD from a given image (or latent) to its noise code.
         A composition of the reference's own functions: the training front end (diffusion_pipeline.py:84-90) for z0, then per iteration
         forward()'s x_0 / x_T estimates at ts[j] and, for "ddim0", GaussianNoiseScheduler.estimate_x_t(x_0_est, ts[j+1], x_T=x_T_est)
@@ -938,20 +1065,26 @@ class DiffusionPipeline(nn.Module):
           return_trajectory=True: also [k][...], the latents at ts[0] .. ts[k-1] (slot 0 is z0).
         All three loop forms (the replayed ones from 4 iterations on), hoisted embeddings of the ascending timesteps, guidance as in denoise().
         Nothing is drawn: `noise` (optional) is carried, its draw_index unchanged; without it torch's generator is not advanced either (the
-        encoder's draw comes from `encode_noise`, as in sample_from).  sampler=None and cold_diffusion=True raise ValueError, `eta` TypeError."""
+        encoder's draw comes from `encode_noise`, as in sample_from).  sampler=None and cold_diffusion=True raise ValueError, `eta` TypeError.
+        guidance_rescale= / dynamic_threshold= / threshold_max= / guidance_schedule= as in denoise(); a schedule has one entry per executed UPWARD
+        iteration (k - 1 of them, at ts[0] .. ts[k-2])."""
         timesteps, k = self._inversion_args("invert", steps, sampler, spacing, strength, kwargs)
+        guide_kw = dict(guidance_rescale=guidance_rescale, dynamic_threshold=dynamic_threshold, threshold_max=threshold_max, guidance_schedule=guidance_schedule)
+        if self._guide_spec(dict(guide_kw, guidance_scale=guidance_scale), condition, list(timesteps[:k - 1]))[0] is None:
+            guide_kw = {}
         if not x.is_cuda:
             raise RuntimeError("medfusion_amd.DiffusionPipeline runs on a ROCm device only (no CPU fallback)")
         with torch.cuda.device(x.device):
             z0 = self._input_latent(x, is_latent, encode_noise)
             noise = self._quiet_noise(noise, z0.shape[0], z0.device)
-            top, traj = self._invert_latent(z0, k, steps, sampler, spacing, condition, guidance_scale, un_cond, noise, trace, loop, use_graph, progress_cb)
+            top, traj = self._invert_latent(z0, k, steps, sampler, spacing, condition, guidance_scale, un_cond, noise, trace, loop, use_graph, progress_cb, guide_kw)
             return (top, traj[1:]) if return_trajectory else top
 
     @torch.no_grad()
     def edit(self, x, target_condition, *, source_condition=None, strength=1.0, steps=None, sampler="ddim0", spacing=None, guidance_scale=1.0,
              source_guidance_scale=1.0, un_cond=None, mask=None, composite=False, is_latent=False, decode=True, return_map=False, loop=None, use_graph=None,
-             progress_cb=None, encode_noise: Optional[NoiseSource] = None, noise: Optional[NoiseSource] = None, **kwargs):
+             progress_cb=None, encode_noise: Optional[NoiseSource] = None, noise: Optional[NoiseSource] = None, guidance_rescale=0.0,
+             source_guidance_rescale=0.0, dynamic_threshold=None, threshold_max=None, guidance_schedule=None, source_guidance_schedule=None, **kwargs):
         """Counterfactual editing: "this image, as the model would draw it under `target_condition`".  invert() under `source_condition` /
         `source_guidance_scale`, recording the trajectory; then the LAST k iterations of the deterministic sampler's loop (denoise's, from
         iteration len - k) from the inverted latent under `target_condition` / `guidance_scale`.  Nothing is drawn.
@@ -960,8 +1093,19 @@ class DiffusionPipeline(nn.Module):
           re-noised copy -- and z0 after the last one, inside the solver step's launch: the kept cells of the final latent are z0 bit for bit.
           composite=True (image input, image-resolution mask): where(mask, decoded, x).
           return_map=True (image input, decode=True): also [B, 1, ...], the mean over the channels of |result - x|.
-        progress_cb(done, total) counts both passes: total = 2 k - 1."""
+        progress_cb(done, total) counts both passes: total = 2 k - 1.
+        guidance_rescale= / guidance_schedule= (as in denoise()) belong to the downward pass under `target_condition`, one schedule entry per
+        executed iteration (k); source_guidance_rescale= / source_guidance_schedule= are their twins for the inversion under `source_condition`
+        (k - 1 entries, upward).  dynamic_threshold= / threshold_max= are ONE setting for both passes: an inversion is only the inverse of the
+        sampler it is run with, so the x_0 estimate is thresholded the same way up and down."""
         timesteps, k = self._inversion_args("edit", steps, sampler, spacing, strength, kwargs)
+        down_kw = dict(guidance_rescale=guidance_rescale, dynamic_threshold=dynamic_threshold, threshold_max=threshold_max, guidance_schedule=guidance_schedule)
+        up_kw = dict(guidance_rescale=source_guidance_rescale, dynamic_threshold=dynamic_threshold, threshold_max=threshold_max,
+                     guidance_schedule=source_guidance_schedule)
+        if self._guide_spec(dict(down_kw, guidance_scale=guidance_scale), target_condition, list(reversed(timesteps))[len(timesteps) - k:])[0] is None:
+            down_kw = {}
+        if self._guide_spec(dict(up_kw, guidance_scale=source_guidance_scale), source_condition, list(timesteps[:k - 1]), "source_")[0] is None:
+            up_kw = {}
         if composite and (is_latent or mask is None):
             raise ValueError("composite=True needs an image input and an image-resolution mask")
         if return_map and (is_latent or not decode):
@@ -983,14 +1127,15 @@ class DiffusionPipeline(nn.Module):
             total = 2 * k - 1
             up_cb = None if progress_cb is None else (lambda done, _t: progress_cb(done, total))
             down_cb = None if progress_cb is None else (lambda done, _t: progress_cb(k - 1 + done, total))
-            top, traj = self._invert_latent(z0, k, steps, sampler, spacing, source_condition, source_guidance_scale, un_cond, noise, None, loop, use_graph, up_cb)
+            top, traj = self._invert_latent(z0, k, steps, sampler, spacing, source_condition, source_guidance_scale, un_cond, noise, None, loop, use_graph, up_cb,
+                                            up_kw)
             keep = None
             if cmask is not None:
                 cells = z0.numel() // (z0.shape[0] * z0.shape[1])
                 keep = L.MfSolverTraj(traj.data_ptr(), cmask.data_ptr(), cells, z0.shape[1], L.TRAJ_KEEP, k - 1, -1, k + 1, 0)
                 keep._keep = (traj, cmask)
             out = self._denoise_guarded(top, steps, target_condition, True, noise, None, decode, use_graph, loop, down_cb, len(timesteps) - k, None,
-                                        dict(guidance_scale=guidance_scale, un_cond=un_cond, sampler=sampler, spacing=spacing), traj=keep)
+                                        dict(guidance_scale=guidance_scale, un_cond=un_cond, sampler=sampler, spacing=spacing, **down_kw), traj=keep)
             if composite:
                 pix = (mask > 0.5) if mask.is_floating_point() else (mask != 0)
                 out = K.select_cells(pix.to(torch.uint8).contiguous(), out, x)

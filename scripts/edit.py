@@ -25,6 +25,7 @@ from img2img import _ChunkNoise, load_png
 from medfusion_amd import DiffusionPipeline
 from medfusion_amd import kernels as K
 from medfusion_amd.egress import AsyncImageWriter
+from medfusion_amd.utils import add_guidance_arguments, guidance_kwargs
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
@@ -43,6 +44,7 @@ if __name__ == "__main__":
     ap.add_argument("--source-guidance", type=float, default=1.0, help="guidance scale of the inversion")
     ap.add_argument("--sampler", default="ddim0", choices=["ddim0", "dpmpp2m"])
     ap.add_argument("--spacing", default=None, choices=["uniform", "logsnr"])
+    add_guidance_arguments(ap)      # (of the target pass; the threshold holds for the inversion too)
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
@@ -80,7 +82,8 @@ if __name__ == "__main__":
                             source_condition=None if labels is None else torch.tensor(labels[lo:lo + n], device=device), strength=args.strength,
                             steps=args.steps, sampler=args.sampler, spacing=args.spacing, guidance_scale=args.guidance,
                             source_guidance_scale=args.source_guidance, un_cond=None, mask=None if mask is None else mask.expand(n, -1, -1, -1).contiguous(),
-                            composite=mask is not None, return_map=map_writer is not None, encode_noise=_ChunkNoise(args.seed, lo, len(files)))
+                            composite=mask is not None, return_map=map_writer is not None, encode_noise=_ChunkNoise(args.seed, lo, len(files)),
+                            **guidance_kwargs(args))
         if map_writer is not None:
             res, cmap = res
             map_writer.submit(cmap, [Path(args.map_out) / f.name for f in chunk])

@@ -28,6 +28,7 @@ import torch
 from medfusion_amd import DiffusionPipeline, PhiloxDeviceNoise
 from medfusion_amd import kernels as K
 from medfusion_amd.egress import AsyncImageWriter
+from medfusion_amd.utils import add_guidance_arguments, guidance_kwargs
 
 
 class _ChunkNoise(PhiloxDeviceNoise):
@@ -66,6 +67,7 @@ if __name__ == "__main__":
     ap.add_argument("--window", type=int, nargs="+", default=None, help="windowed denoising: the trained extents, in latent cells (smaller than the images' latent)")
     ap.add_argument("--window-stride", type=int, nargs="+", default=None, help="stride of the windows per axis (default: half a window)")
     ap.add_argument("--window-weight", default="tent", choices=["tent", "uniform"], help="weights of the per-cell average over the windows")
+    add_guidance_arguments(ap)
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--save-tensor", action="store_true", help="also write result.pt: the fp32 images behind the PNG files")
@@ -98,7 +100,7 @@ if __name__ == "__main__":
                                    steps=args.steps, use_ddim=not args.ddpm, guidance_scale=args.guidance, un_cond=None, composite=mask is not None,
                                    sampler=args.sampler, spacing=args.spacing, window=None if args.window is None else tuple(args.window),
                                    window_stride=None if args.window_stride is None else tuple(args.window_stride), window_weight=args.window_weight,
-                                   noise=_ChunkNoise(args.seed, lo, len(files)), encode_noise=_ChunkNoise(args.seed + 1, lo, len(files)))
+                                   noise=_ChunkNoise(args.seed, lo, len(files)), encode_noise=_ChunkNoise(args.seed + 1, lo, len(files)), **guidance_kwargs(args))
         writer.submit(res, [out / f.name for f in chunk])
         if args.save_tensor:
             kept.append(res.cpu())

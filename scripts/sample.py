@@ -20,6 +20,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 import torch
 
 from medfusion_amd import DiffusionPipeline
+from medfusion_amd.utils import add_guidance_arguments, guidance_kwargs
 
 
 def rgb2gray(img):
@@ -74,6 +75,7 @@ if __name__ == "__main__":
     ap.add_argument("--window", type=int, nargs="+", default=None, help="windowed denoising: the trained extents, in latent cells (smaller than --canvas)")
     ap.add_argument("--window-stride", type=int, nargs="+", default=None, help="stride of the windows per axis (default: half a window)")
     ap.add_argument("--window-weight", default="tent", choices=["tent", "uniform"], help="weights of the per-cell average over the windows")
+    add_guidance_arguments(ap)
     args = ap.parse_args()
     path_out = Path.cwd() / args.out
     path_out.mkdir(parents=True, exist_ok=True)
@@ -89,11 +91,14 @@ if __name__ == "__main__":
     if args.window is not None:
         window_kw = dict(window=tuple(args.window), window_stride=None if args.window_stride is None else tuple(args.window_stride), window_weight=args.window_weight)
     raw = {}
+    guide_kw = guidance_kwargs(args)
+    unguided_kw = {k: v for k, v in guide_kw.items() if k in ("dynamic_threshold", "threshold_max")}   # (the unconditional set has no guidance pair)
     for cond in [0, 1, None]:
         torch.manual_seed(0)
         condition = torch.tensor([cond] * n_samples, device=device) if cond is not None else None
         un_cond = None
-        results = pipeline.sample(n_samples, (8, *args.canvas), guidance_scale=8, condition=condition, un_cond=un_cond, steps=steps, use_ddim=use_ddim, **window_kw)
+        results = pipeline.sample(n_samples, (8, *args.canvas), guidance_scale=8, condition=condition, un_cond=un_cond, steps=steps, use_ddim=use_ddim, **window_kw,
+                                  **(guide_kw if cond is not None else unguided_kw))
         raw[str(cond)] = results.cpu()
         results = (results + 1) / 2
         results = results.clamp(0, 1)

@@ -20,6 +20,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 import torch
 
 from medfusion_amd import DiffusionPipeline
+from medfusion_amd.utils import add_guidance_arguments, guidance_kwargs
 from medfusion_amd.egress import AsyncImageWriter, save_png
 
 
@@ -44,6 +45,7 @@ if __name__ == "__main__":
     ap.add_argument("--sampler", default=None, choices=["ddim0", "dpmpp2m", "ddim1", "dpmpp2m_sde"],
                     help="a few-step sampler, deterministic (ddim0, dpmpp2m) or stochastic (ddim1, dpmpp2m_sde); default: the reference's loop")
     ap.add_argument("--spacing", default=None, choices=["uniform", "logsnr"], help="timestep grid of --sampler (logsnr: uniform in log-SNR)")
+    add_guidance_arguments(ap)
     ap.add_argument("--diversity", type=int, default=0, metavar="PAIRS",
                     help="also report the pairwise MS-SSIM (mean ± std over PAIRS random pairs, seed 0) of every generated set; 0: off.  Keeps every "
                          "set on the device until it is measured: 2 x 4 bytes per value of --n-samples images on top of the run's own memory")
@@ -80,7 +82,7 @@ if __name__ == "__main__":
                 for chunk in chunks(list(range(args.n_samples)), args.sample_batch):
                     condition = torch.tensor([label] * len(chunk), device=device)
                     un_cond = torch.tensor([1 - label] * len(chunk), device=device)
-                    results = pipeline.sample(len(chunk), (8, 32, 32), guidance_scale=cfg, condition=condition, un_cond=un_cond, steps=steps, **solver)
+                    results = pipeline.sample(len(chunk), (8, 32, 32), guidance_scale=cfg, condition=condition, un_cond=un_cond, steps=steps, **solver, **guidance_kwargs(args))
                     if writer is not None:
                         writer.submit(results, [path_out / f"fake_{counter + i}.png" for i in range(len(chunk))])
                     if args.diversity and egress:
