@@ -587,6 +587,9 @@ int mf_rows_axpby_f32(const float* x, const float* y, const float* a, const floa
  * (sample_offset + b) in draw `draw` depends only on (seed, draw, sample index, q).  Stands in for
  * torch.randn_like at diffusion_pipeline.py:315(x_final), gaussian_scheduler.py:99, diffusion_pipeline.py:303.
  * draw index = draw_base + draw_stride * step where step = *step_dev (or `step`).
+ * The sample index is one 32-bit word of the Philox counter: sample_offset + b is taken mod 2^32 (row 2^32 draws what row 0 draws), here
+ * and in every launch that regenerates these values.  A uniform whose 24 bits are all ones is exactly 1.0 in fp32: where it is the radius
+ * word, the pair of normals is (+-0, +-0), finite.
  */
 int mf_philox_normal_f32(float* out, uint64_t seed, int32_t draw_base, int32_t draw_stride, const int32_t* step_dev,
                          int32_t step, int64_t sample_offset, int B, int64_t per_sample, void* stream);

@@ -13,6 +13,7 @@ from oracle import synth as S
 from tests import edit_cases as E
 from tests.test_solver_gpu import _args, _sched, product_pipe
 from tests.util import T, gold, relerr
+from tests.util import offset_view as _view
 
 TOL = 1e-4             # as in tests/test_solver_gpu.py
 DRIFT_FACTOR = 2.0     # a case over TOL is held to max(TOL, 2 x the fp32 composition's distance from its own fp64 evaluation): that file's rule
@@ -35,18 +36,6 @@ def pipes(dev):
 
 def _rand(name, shape, scale=1.0):
     return S.synth_input("edit." + name, shape, scale)
-
-
-def _view(t, offset):
-    """a copy of t: 16-byte aligned, or (offset=True) at a 4-byte offset from a 16-byte boundary, where the launch must take its element-by-element
-    path"""
-    if not offset:
-        return t.clone()
-    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
-    v = buf[1:].view(t.shape)
-    v.copy_(t)
-    assert v.data_ptr() % 16 == 4
-    return v
 
 
 # ------------------------------------------------------------------------------------------------ 1. the kernel

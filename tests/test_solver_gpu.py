@@ -138,6 +138,19 @@ def _nonfinite_pass(dev, sch, ts, table, old, x_t, pred, pu, step, objective, sa
 
 
 # ------------------------------------------------------------------------------------------------ 2. the kernel's back half
+def back_half_bound(r, xi, e0, eT, prev):
+    """the fp64 value of a non-final row's back half from the fp64 copies of x_t, x_0, x_T and the previous x_0, and the bound the test below
+    derives for it -> (want, 4 * 2^-24 * the sum of the terms' magnitudes, that sum)"""
+    if r.mode == L.SOLVER_DDIM0:
+        terms = [r.B * e0, r.A * eT]
+    elif r.mode == L.SOLVER_ORDER1:
+        terms = [r.A * xi, r.B * e0]
+    else:
+        terms = [r.A * xi, r.B * e0, r.C * prev]
+    want, mag = sum(terms), sum(t.abs() for t in terms)
+    return want, 4 * 2.0 ** -24 * mag, mag
+
+
 @pytest.mark.parametrize("n", [4096, 1023, 4098, 3])
 @pytest.mark.parametrize("sampler", SAMPLERS)
 def test_back_half_against_fp64_history_slots_and_device_counter(dev, sampler, n):
@@ -158,15 +171,9 @@ def test_back_half_against_fp64_history_slots_and_device_counter(dev, sampler, n
         if r.mode == L.SOLVER_FINAL:
             assert torch.equal(x, x0)
         else:
-            if r.mode == L.SOLVER_DDIM0:
-                terms = [r.B * e0, r.A * eT]
-            elif r.mode == L.SOLVER_ORDER1:
-                terms = [r.A * xi, r.B * e0]
-            else:
-                terms = [r.A * xi, r.B * e0, r.C * prev]
-            want, mag = sum(terms), sum(t.abs() for t in terms)
+            want, bound, mag = back_half_bound(r, xi, e0, eT, prev)
             err = (x.double().cpu() - want).abs()
-            assert bool((err <= 4 * 2.0 ** -24 * mag).all()), (sampler, n, i, float((err / mag.clamp_min(1e-30)).max()))
+            assert bool((err <= bound).all()), (sampler, n, i, float((err / mag.clamp_min(1e-30)).max()))
         assert torch.equal(hist[i & 1], x0)                       # this step's slot; the other still holds the previous x_0 (or NaN before any)
         if prev is not None:
             assert torch.equal(hist[(i + 1) & 1].double().cpu(), prev)

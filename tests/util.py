@@ -44,6 +44,18 @@ def relerr_rms(a: torch.Tensor, b: torch.Tensor) -> float:
     return float(((a - b).pow(2).mean(1) / b.pow(2).mean(1).clamp_min(1e-60)).sqrt().max())
 
 
+def offset_view(t: torch.Tensor, offset) -> torch.Tensor:
+    """a copy of t: 16-byte aligned, or (offset=True) at a 4-byte offset from a 16-byte boundary, where the launch must take its element-by-element
+    path"""
+    if not offset:
+        return t.clone()
+    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
+    v = buf[1:].view(t.shape)
+    v.copy_(t)
+    assert v.data_ptr() % 16 == 4
+    return v
+
+
 def to_product_kwargs(kw: dict) -> dict:
     """oracle kwargs -> product kwargs (swap the embedder classes)."""
     import medfusion_amd as M
