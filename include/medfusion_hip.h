@@ -1027,6 +1027,86 @@ typedef struct MfGuideArgs {
 size_t mf_guide_workspace_bytes(int B, int64_t n);
 int mf_guide_f32(const MfGuideArgs* a, void* stream);
 
+/* ------------------------------------------------------------------ dataset transform (additive to ABI 250): resize, crop, normalise on the device
+ * Replaces the loader's transform, medical_diffusion/data/datasets/dataset_simple_2d.py:34-45: T.Resize (PIL, bilinear, antialiased when reducing) ->
+ * T.CenterCrop -> T.ToTensor -> T.Normalize(0.5, 0.5), and augmentations_2d.py:14-19 (Normalize: (v - min) / (max - min)), for a RAGGED batch: N
+ * images of any sizes back to back in one byte buffer, one pair of launches, no launch per image, no host sync, nothing allocated.
+ *
+ * The definition is PIL's ImagingResample restated (tests/ingest_cases.py; 0 mismatching pixels / bits against Pillow on the test list).
+ * Coefficient table of one axis, in -> out samples, fp64 on the host (mf_resample_table): scale = in / out, fs = max(scale, 1), support = fs,
+ * ksize = 2 ceil(support) + 1; for output xx: center = (xx + 0.5) scale, xmin = max(int(center - support + 0.5), 0), xmax = min(int(center + support
+ * + 0.5), in), n = xmax - xmin (int() truncates), w_x = max(0, 1 - |(x + xmin - center + 0.5) (1 / fs)|) for x < n -- the product with the rounded
+ * reciprocal, as PIL forms it --, summed ascending to ww, each divided by ww when ww != 0; entries n .. ksize are 0.
+ *   uint8 (1 or 3 interleaved channels): k_x = int(0.5 + w_x 2^22) (int(-0.5 + ...) for a negative one); a sample is
+ *     clamp((2^21 + sum_x pix[xmin + x] k_x) >> 22, 0, 255) in 32-bit integers.
+ *   float32 (1 channel): ss = 0; ss = ss + double(pix) w_x, x ascending, product and sum rounded separately; the sample is (float)ss.
+ *   uint16 (1 channel): the same chain; the sample is clamp(floor(ss + 0.5), 0, 65535).
+ * The horizontal pass comes first and its result is rounded to the element type; the vertical pass runs on that.  An axis whose size does not
+ * change is skipped (its elements pass through: nothing is rounded twice).  The crop box (top, left, h, w) of the resized image is applied inside the
+ * kernels: only the surviving columns, and only the source rows the surviving rows reach, are computed -- the same bits as resize-then-crop.
+ * out_mode: MF_INGEST_RAW -> out [N][C][h][w] fp32, the resampled values; MF_INGEST_CENTERED (uint8 / uint16) -> fl(fl(fl(v / full) - 0.5) / 0.5),
+ * full = 255 / 65535 (mf_image_ingress_u8's chain: an image that needs no pass gives that call's bits); MF_INGEST_BYTES (uint8) -> out [N][h][w][C]
+ * uint8.  mf_minmax_apply_f32: x [N][n] in place, v = fl(fl(v - min) / fl(max - min)), then fl(fl(v - 0.5) / 0.5) with center != 0; minmax [N][2] is
+ * mf_rows_minmax_f32's.
+ *
+ * The caller concatenates the tables of the distinct (in, out) pairs of the batch: weights_f64 / weights_i32 ([out][ksize] rows, the same entry
+ * offsets in both; uint8 reads the integers, the others the doubles -- the unused one may be NULL) and bounds ((xmin, n) pairs), on the device, with
+ * a HOST copy of the bounds and of the descriptors: every rule is checked on the host copies before any launch (the device copies must equal them).
+ * mf_resample_plan (host only) checks the descriptors and fills their derived fields: the source rows an image's surviving rows reach, its offset
+ * in the workspace, its first workgroup in the horizontal pass.  Refused before any launch, MF_EINVAL unless stated: a null pointer, C not 1 or 3,
+ * C = 3 with uint16 / float32 (MF_EUNSUPPORTED), a side < 1, a crop outside the resized image, bytes or table rows outside what was given, a ksize
+ * that is not the pair's, derived fields that are not the plan's, a workspace too small (MF_EWORKSPACE). */
+#define MF_INGEST_U8 0
+#define MF_INGEST_U16 1
+#define MF_INGEST_F32 2
+#define MF_INGEST_RAW 0
+#define MF_INGEST_CENTERED 1
+#define MF_INGEST_BYTES 2
+typedef struct MfResampleImage {
+  int64_t src_off;           /* byte offset of the image ([H][W][C] elements) in src; a multiple of the element size, else any alignment */
+  int64_t ws_off;            /* (plan) ELEMENT offset of its intermediate [rows][w][C] in the workspace */
+  int64_t tw_h, tw_v;        /* first entry of its horizontal / vertical table in weights_* (read when that axis changes size) */
+  int64_t tb_h, tb_v;        /* first (xmin, n) pair of its horizontal / vertical table in bounds */
+  int32_t H, W;              /* source size */
+  int32_t Hr, Wr;            /* resized size */
+  int32_t top, left;         /* crop box's corner in the resized image; its size is the batch's (h, w) */
+  int32_t ksize_h, ksize_v;  /* row length of the two tables */
+  int32_t row0, rows;        /* (plan) source rows [row0, row0 + rows) the surviving output rows reach */
+  int32_t wg_h;              /* (plan) its first workgroup in the horizontal pass */
+  int32_t reserved;          /* 0 */
+} MfResampleImage;
+typedef struct MfResamplePlan {
+  int64_t workspace_bytes;   /* of the horizontal pass's intermediates */
+  int32_t wg_h, wg_v;        /* workgroups of the two passes (wg_h = 0: no image changes width, one launch) */
+  int32_t launches;          /* 1 or 2 */
+  int32_t reserved;
+} MfResamplePlan;
+typedef struct MfResampleArgs {
+  const void* src;                     /* device: the images back to back */
+  const MfResampleImage* images;       /* device [N] */
+  const MfResampleImage* images_host;  /* host [N], equal */
+  const double* weights_f64;           /* device */
+  const int32_t* weights_i32;          /* device */
+  const int32_t* bounds;               /* device, (xmin, n) pairs */
+  const int32_t* bounds_host;          /* host, equal */
+  void* workspace;                     /* device, 16-byte aligned; may be NULL when no image changes width */
+  void* out;                           /* device: fp32 [N][C][h][w], or uint8 [N][h][w][C] with MF_INGEST_BYTES */
+  int64_t bounds_count;                /* pairs in bounds */
+  int64_t weights_count;               /* entries in weights_* */
+  int64_t src_bytes;
+  uint64_t workspace_bytes;
+  int32_t N, C, dtype, h, w, out_mode;
+  int32_t reserved;                    /* 0 */
+  int32_t reserved2;
+} MfResampleArgs;
+/* host only, no device needed: -> ksize (negative: MF_E*); fills weights [out][ksize] fp64, fixed [out][ksize] (the 22-bit integers) and bounds
+ * [out][2], each of which may be NULL (all NULL: only ksize) */
+int mf_resample_table(int in, int out, double* weights, int32_t* fixed, int32_t* bounds);
+int mf_resample_plan(MfResampleImage* images, int N, int C, int dtype, int h, int w, const int32_t* bounds_host, int64_t bounds_count,
+                     int64_t weights_count, int64_t src_bytes, MfResamplePlan* plan);
+int mf_image_resample(const MfResampleArgs* a, void* stream);
+int mf_minmax_apply_f32(float* x, const float* minmax, int N, int64_t n, int center, void* stream);
+
 /* ------------------------------------------------------------------ built-in launch timing (bench / roofline)
  * When enabled every launch is bracketed by hipEvents on its own stream and attributed to a kernel family.
  * NOT capture-safe; off by default. */

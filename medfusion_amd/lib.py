@@ -93,6 +93,25 @@ class MfGuideArgs(C.Structure):
                 ("B", C.c_int32), ("stages", C.c_int32), ("reserved", C.c_int32), ("reserved2", C.c_int32)]
 
 
+INGEST_U8, INGEST_U16, INGEST_F32 = 0, 1, 2
+INGEST_RAW, INGEST_CENTERED, INGEST_BYTES = 0, 1, 2
+
+
+class MfResampleImage(C.Structure):
+    _fields_ = ([(n, C.c_int64) for n in ("src_off", "ws_off", "tw_h", "tw_v", "tb_h", "tb_v")]
+                + [(n, C.c_int32) for n in ("H", "W", "Hr", "Wr", "top", "left", "ksize_h", "ksize_v", "row0", "rows", "wg_h", "reserved")])
+
+
+class MfResamplePlan(C.Structure):
+    _fields_ = [("workspace_bytes", C.c_int64), ("wg_h", C.c_int32), ("wg_v", C.c_int32), ("launches", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MfResampleArgs(C.Structure):
+    _fields_ = ([(n, c_fp) for n in ("src", "images", "images_host", "weights_f64", "weights_i32", "bounds", "bounds_host", "workspace", "out")]
+                + [("bounds_count", C.c_int64), ("weights_count", C.c_int64), ("src_bytes", C.c_int64), ("workspace_bytes", C.c_uint64)]
+                + [(n, C.c_int32) for n in ("N", "C", "dtype", "h", "w", "out_mode", "reserved", "reserved2")])
+
+
 TRAJ_RECORD, TRAJ_KEEP = 0, 1
 
 
@@ -245,6 +264,10 @@ _SIGS = {
     "mf_variance_loss_finish_f32": (_I, [c_fp, c_fp, _I, _I64, c_fp]),
     "mf_guide_workspace_bytes": (_SZ, [_I, _I64]),
     "mf_guide_f32": (_I, [C.POINTER(MfGuideArgs), c_fp]),
+    "mf_resample_table": (_I, [_I, _I, c_fp, c_fp, c_fp]),
+    "mf_resample_plan": (_I, [C.POINTER(MfResampleImage), _I, _I, _I, _I, _I, c_fp, _I64, _I64, _I64, C.POINTER(MfResamplePlan)]),
+    "mf_image_resample": (_I, [C.POINTER(MfResampleArgs), c_fp]),
+    "mf_minmax_apply_f32": (_I, [c_fp, c_fp, _I, _I64, _I, c_fp]),
     "mf_absdiff_mean_c_f32": (_I, [c_fp, c_fp, c_fp, _I, _I, _I64, c_fp]),
     "mf_select_cells_f32": (_I, [c_fp, c_fp, c_fp, c_fp, _I, _I, _I64, c_fp]),
     "mf_window_gather_f32": (_I, [c_fp, c_fp, C.POINTER(MfWindowDesc), c_fp]),

@@ -22,6 +22,8 @@ def parse_args(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--max-samples", type=int, default=None, help="only the first N files (default: all)")
     ap.add_argument("--batch", type=int, default=256, help="files per host-to-device copy")
+    from medfusion_amd.ingest import add_ingest_arguments
+    add_ingest_arguments(ap)
     args = ap.parse_args(argv)
     if args.pairs < 1:
         ap.error("--pairs: at least 1")
@@ -54,10 +56,10 @@ def main(argv=None):
 
     from evaluate_latent_embedder import list_images, load_batch
     device = torch.device("cuda")
-    files = list_images(args.images, args.max_samples)
+    files = list_images(args.images, args.max_samples, args.ext)
     if len(files) < 2:
         raise SystemExit(f"{args.images}: at least two images make a pair")
-    bank = torch.cat([(load_batch(files[lo:lo + args.batch], 3, device) + 1) / 2 for lo in range(0, len(files), args.batch)])
+    bank = torch.cat([(load_batch(files[lo:lo + args.batch], 3, device, args) + 1) / 2 for lo in range(0, len(files), args.batch)])
     res = diversity(bank, args.pairs, args.seed)
     print(f"MS-SSIM (pairwise, {res['pairs']} pairs of {res['images']} images): {res['ms_ssim_pairwise_mean']} ± {res['ms_ssim_pairwise_std']}")
     print(json.dumps(dict(res, images_folder=str(args.images), seed=args.seed)))

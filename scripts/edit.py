@@ -18,12 +18,10 @@ import sys
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
-import numpy as np
 import torch
 
-from img2img import _ChunkNoise, load_png
-from medfusion_amd import DiffusionPipeline
-from medfusion_amd import kernels as K
+from img2img import _ChunkNoise, load_images, load_png
+from medfusion_amd import DiffusionPipeline, ingest
 from medfusion_amd.egress import AsyncImageWriter
 from medfusion_amd.utils import add_guidance_arguments, guidance_kwargs
 
@@ -45,6 +43,7 @@ if __name__ == "__main__":
     ap.add_argument("--sampler", default="ddim0", choices=["ddim0", "dpmpp2m"])
     ap.add_argument("--spacing", default=None, choices=["uniform", "logsnr"])
     add_guidance_arguments(ap)      # (of the target pass; the threshold holds for the inversion too)
+    ingest.add_ingest_arguments(ap)
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
@@ -54,9 +53,9 @@ if __name__ == "__main__":
     pipeline = DiffusionPipeline.load_from_checkpoint(args.checkpoint, **ckpt_kw).to(device).eval()
     emb = pipeline.latent_embedder
     channels = 3 if emb is None else getattr(emb, "out_channels", 3)
-    files = sorted(Path(args.images).glob("*.png"))
+    files = ingest.list_images(args.images, args.ext)
     if not files:
-        raise SystemExit(f"no PNG files in {args.images}")
+        raise SystemExit(f"no {'PNG' if args.ext is None else '/'.join(args.ext)} files in {args.images}")
     labels = None
     if args.labels:
         labels = [int(v) for v in Path(args.labels).read_text().split()]
@@ -68,7 +67,7 @@ if __name__ == "__main__":
     out.mkdir(parents=True, exist_ok=True)
     mask = None
     if args.mask:
-        mask = torch.from_numpy(load_png(args.mask, 1)[..., 0].copy())[None, None].to(device)     # uint8 [1, 1, H, W]
+        mask = ingest.load_mask(args.mask, device, args, loader=load_png)                         # uint8 [1, 1, H, W]
     writer = AsyncImageWriter(device, normalize_each=False)
     map_writer = None
     if args.map_out:
@@ -76,7 +75,7 @@ if __name__ == "__main__":
         map_writer = AsyncImageWriter(device, normalize_each=True)
     for lo in range(0, len(files), args.batch):
         chunk = files[lo:lo + args.batch]
-        x = K.image_ingress(torch.from_numpy(np.stack([load_png(f, channels) for f in chunk])).to(device))
+        x = load_images(chunk, channels, device, args)
         n = x.shape[0]
         res = pipeline.edit(x, torch.full((n,), args.target, device=device),
                             source_condition=None if labels is None else torch.tensor(labels[lo:lo + n], device=device), strength=args.strength,

@@ -65,6 +65,8 @@ def parse_args(argv=None):
                     help="also the authenticity and the copy ratios of the generated set against --real as the training set (10 neighbours when given without a value)")
     ap.add_argument("--kid", type=int, nargs="?", const=100, default=None, metavar="SUBSETS",
                     help="also the Kernel Inception Distance over SUBSETS pairs of subsets (100 when given without a value)")
+    from medfusion_amd.ingest import add_ingest_arguments
+    add_ingest_arguments(ap)
     ap.add_argument("--kid-subset-size", type=int, default=1000, metavar="ROWS", help="rows of a subset of --kid (at most the rows of the smaller set)")
     args = ap.parse_args(argv)
     if args.kid is not None and not 1 <= args.kid <= 65535:
@@ -107,12 +109,12 @@ def load_features(path, max_samples, expect_2d=None):
     return t[slice(max_samples)].to(torch.float32).contiguous()
 
 
-def folder_features(folder, extractor, channels, batch, max_samples, device):
+def folder_features(folder, extractor, channels, batch, max_samples, device, args=None):
     import torch
 
     from evaluate_latent_embedder import list_images, load_batch
-    files = list_images(folder, max_samples)
-    return torch.cat([extractor(load_batch(files[lo:lo + batch], channels, device)) for lo in range(0, len(files), batch)])
+    files = list_images(folder, max_samples, getattr(args, "ext", None))
+    return torch.cat([extractor(load_batch(files[lo:lo + batch], channels, device, args)) for lo in range(0, len(files), batch)])
 
 
 def main(argv=None):
@@ -143,7 +145,7 @@ def main(argv=None):
         if is_feature_file(src):
             sets[name] = load_features(src, args.max_samples).to(device)
         else:
-            sets[name] = folder_features(src, extractor, channels, args.batch, args.max_samples, device)
+            sets[name] = folder_features(src, extractor, channels, args.batch, args.max_samples, device, args)
     real, fake = sets["real"], sets["fake"]
     logger.info(f"Samples Real: {real.shape[0]}")
     logger.info(f"Samples Fake: {fake.shape[0]}")

@@ -32,6 +32,8 @@ def parse_args(argv=None):
     ap.add_argument("--max-samples", type=int, default=None, help="only the first N files (default: all)")
     ap.add_argument("--out", default="results/metrics", help="folder of the log and the JSON")
     ap.add_argument("--seed", type=int, default=0, help="Philox key of the draws a VAE / VAEGAN makes")
+    from medfusion_amd.ingest import add_ingest_arguments
+    add_ingest_arguments(ap)
     args = ap.parse_args(argv)
     if (args.checkpoint is None) == (not args.synthetic):
         ap.error("exactly one of --checkpoint and --synthetic")
@@ -42,10 +44,12 @@ def parse_args(argv=None):
     return args
 
 
-def list_images(folder, max_samples=None):
-    files = sorted(Path(folder).glob("*.png"))[slice(max_samples)]
+def list_images(folder, max_samples=None, exts=None):
+    """the files of a folder by name: *.png, or the extensions of --ext"""
+    from medfusion_amd.ingest import list_images as ls
+    files = ls(folder, exts)[slice(max_samples)]
     if not files:
-        raise SystemExit(f"no PNG files in {folder}")
+        raise SystemExit(f"no {'PNG' if exts is None else '/'.join(exts)} files in {folder}")
     return files
 
 
@@ -56,8 +60,12 @@ def load_png(path, channels):
     return arr[..., None] if arr.ndim == 2 else arr
 
 
-def load_batch(files, channels, device):
-    """PNG files -> fp32 [n, C, H, W] in [-1, 1] on the device"""
+def load_batch(files, channels, device, args=None):
+    """PNG files -> fp32 [n, C, H, W] in [-1, 1] on the device; with --resize / --crop (args): files of any sizes through the data set's transform
+    (medfusion_amd.ingest)"""
+    from medfusion_amd import ingest
+    if args is not None and ingest.ingest_requested(args):
+        return ingest.load_batch(files, channels, device, args)
     import numpy as np
     import torch
 
@@ -106,7 +114,7 @@ def main(argv=None):
     logger.addHandler(logging.StreamHandler(sys.stdout))
     logger.addHandler(logging.FileHandler(out / f"metrics_{stamp}.log", "w"))
 
-    files = list_images(args.images, args.max_samples)
+    files = list_images(args.images, args.max_samples, args.ext)
     logger.info(f"Samples Real: {len(files)}")
     model = build_embedder(args).to(device).eval()
     channels = getattr(model, "in_channels", None) or 3
@@ -114,7 +122,7 @@ def main(argv=None):
     meter = ReconstructionMeter(model, noise=noise)
     for lo in range(0, len(files), args.batch):
         noise.offset = lo
-        meter.update(load_batch(files[lo:lo + args.batch], channels, device))
+        meter.update(load_batch(files[lo:lo + args.batch], channels, device, args))
     res = meter.compute()
     logger.info("LPIPS: not built (needs VGG weights)")
     logger.info(f"MS-SSIM: {res['ms_ssim_mean']} ± {res['ms_ssim_std']}")

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from medfusion_amd import DiffusionPipeline, PhiloxDeviceNoise
-from medfusion_amd import kernels as K
+from medfusion_amd import ingest
 from medfusion_amd.egress import AsyncImageWriter
 from medfusion_amd.utils import add_guidance_arguments, guidance_kwargs
 
@@ -49,6 +49,12 @@ def load_png(path, channels):
     return arr[..., None] if arr.ndim == 2 else arr
 
 
+def load_images(files, channels, device, args=None):
+    """files -> [n, C, h, w] fp32 in [-1, 1] on the device: the bytes of equal-sized PNG files through mf_image_ingress_u8, or, with --resize /
+    --crop, files of any sizes through the data set's transform (medfusion_amd.ingest: PIL-exact resize, centre crop, the same value map)"""
+    return ingest.load_batch(files, channels, device, args, loader=load_png)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--checkpoint", required=True)
@@ -68,6 +74,7 @@ if __name__ == "__main__":
     ap.add_argument("--window-stride", type=int, nargs="+", default=None, help="stride of the windows per axis (default: half a window)")
     ap.add_argument("--window-weight", default="tent", choices=["tent", "uniform"], help="weights of the per-cell average over the windows")
     add_guidance_arguments(ap)
+    ingest.add_ingest_arguments(ap)
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--save-tensor", action="store_true", help="also write result.pt: the fp32 images behind the PNG files")
@@ -78,21 +85,20 @@ if __name__ == "__main__":
     pipeline = DiffusionPipeline.load_from_checkpoint(args.checkpoint, **ckpt_kw).to(device).eval()
     emb = pipeline.latent_embedder
     channels = 3 if emb is None else getattr(emb, "out_channels", 3)      # (the autoencoders of the reference reconstruct their input: same channels)
-    files = sorted(Path(args.images).glob("*.png"))
+    files = ingest.list_images(args.images, args.ext)
     if not files:
-        raise SystemExit(f"no PNG files in {args.images}")
+        raise SystemExit(f"no {'PNG' if args.ext is None else '/'.join(args.ext)} files in {args.images}")
     out = Path(args.out)
     out.mkdir(parents=True, exist_ok=True)
     mask = None
     if args.mask:
-        mask = torch.from_numpy(load_png(args.mask, 1)[..., 0].copy())[None, None].to(device)     # uint8 [1, 1, H, W]
+        mask = ingest.load_mask(args.mask, device, args, loader=load_png)                         # uint8 [1, 1, H, W]
 
     writer = AsyncImageWriter(device, normalize_each=False)
     kept = []
     for lo in range(0, len(files), args.batch):
         chunk = files[lo:lo + args.batch]
-        u8 = torch.from_numpy(np.stack([load_png(f, channels) for f in chunk])).to(device)           # [n, H, W, C] bytes
-        x = K.image_ingress(u8)
+        x = load_images(chunk, channels, device, args)
         n = x.shape[0]
         cond = None if args.condition is None else torch.full((n,), args.condition, device=device)
         # (one Philox key for the whole folder, the chunk's rows at their global offset: the result does not depend on --batch)

@@ -37,6 +37,8 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=100)
     ap.add_argument("--max-samples", type=int, default=None)
     ap.add_argument("--out", default="results/audit", help="folder of the JSON and the contact sheet")
+    from medfusion_amd.ingest import add_ingest_arguments
+    add_ingest_arguments(ap)
     ap.add_argument("--plan", action="store_true", help="print launches, splits and workspace, touch no device")
     ap.add_argument("--n-train", type=int, default=50000, help="--plan: training rows")
     ap.add_argument("--n-fake", type=int, default=10000, help="--plan: generated rows")
@@ -87,8 +89,8 @@ def load_set(src, args, extractor, channels, device):
     import torch
     if ev.is_feature_file(src):
         return ev.load_features(src, args.max_samples).to(device), None
-    files = list_images(src, args.max_samples)
-    feats = torch.cat([extractor(load_batch(files[lo:lo + args.batch], channels, device)) for lo in range(0, len(files), args.batch)])
+    files = list_images(src, args.max_samples, getattr(args, "ext", None))
+    feats = torch.cat([extractor(load_batch(files[lo:lo + args.batch], channels, device, args)) for lo in range(0, len(files), args.batch)])
     return feats, files
 
 

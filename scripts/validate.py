@@ -44,6 +44,8 @@ def parse_args(argv=None):
     ap.add_argument("--bins", type=int, default=10)
     ap.add_argument("--profile", type=int, nargs="?", const=20, default=None, metavar="K", help="per-scan loss at K log-SNR-spaced timesteps (default 20)")
     ap.add_argument("--out", default=None, help="the JSON (default: validate.json in --images)")
+    from medfusion_amd.ingest import add_ingest_arguments
+    add_ingest_arguments(ap)
     ap.add_argument("--plan", action="store_true", help="print what would run; touches no device and needs no checkpoint")
     a = ap.parse_args(argv)
     if a.batch < 1 or a.passes < 1 or a.bins < 1 or (a.profile is not None and a.profile < 1):
@@ -62,14 +64,17 @@ def plan_lines(a, files=None):
     return lines
 
 
-def load_inputs(folder, channels, device):
+def load_inputs(folder, channels, device, args=None):
     """-> (list of files, loader(chunk) -> fp32 device tensor [n, C, spatial...])"""
     import numpy as np
     import torch
 
     from medfusion_amd import kernels as K
     folder = Path(folder)
-    files = sorted(folder.glob("*.png"))
+    from medfusion_amd import ingest
+    files = ingest.list_images(folder, getattr(args, "ext", None))
+    if files and args is not None and ingest.ingest_requested(args):      # files of any sizes through the data set's transform
+        return files, lambda chunk: ingest.load_batch(chunk, channels, device, args)
     if files:
         from img2img import load_png
         return files, lambda chunk: K.image_ingress(torch.from_numpy(np.stack([load_png(f, channels) for f in chunk])).to(device))
@@ -103,7 +108,7 @@ def main(argv=None):
             raise SystemExit("--ema: the checkpoint holds no EMA weights")
         pipe.use_ema = a.ema
     emb = pipe.latent_embedder
-    files, load = load_inputs(a.images, 3 if emb is None else getattr(emb, "in_channels", 3), device)
+    files, load = load_inputs(a.images, 3 if emb is None else getattr(emb, "in_channels", 3), device, a)
     labels = None
     if a.labels and not a.uncond:
         labels = [int(v) for v in Path(a.labels).read_text().split()]
