@@ -1107,6 +1107,60 @@ int mf_resample_plan(MfResampleImage* images, int N, int C, int dtype, int h, in
 int mf_image_resample(const MfResampleArgs* a, void* stream);
 int mf_minmax_apply_f32(float* x, const float* minmax, int N, int64_t n, int center, void* stream);
 
+/* ------------------------------------------------------------------ LPIPS (additive to ABI 250): a pretrained-CNN trunk's plain layers and the distance
+ * Replaces lpips.LPIPS(net='vgg').forward at medical_diffusion/loss/perceivers.py (the embedders' perception_loss: per slice, the mean over depth for
+ * volumes) and torchmetrics' LearnedPerceptualImagePatchSimilarity (AlexNet trunk) at scripts/evaluate_latent_embedder.py ("LPIPS Score: 1 - mean").
+ * Nothing pretrained is shipped or fetched: the caller loads the torchvision trunk state dict and the lpips package's linear-layer file.
+ *
+ * Definition (lpips v0.1).  Inputs x, y: fp32 NCHW, C in {1, 3}, in [-1, 1]; with normalize they are in [0, 1] and fl(2 x - 1) is taken first.
+ *   Scaling layer: h_c = fl(fl(x_c' - shift_c) / scale_c), c = 0, 1, 2, c' = c for 3 channels and 0 for one; shift = (-.030, -.088, -.188),
+ *     scale = (.458, .448, .450).
+ *   Trunks: every convolution has a bias and is followed by ReLU.
+ *     vgg: thirteen 3x3 pad 1 convolutions of widths 64, 64 | 128, 128 | 256, 256, 256 | 512, 512, 512 | 512, 512, 512; a 2x2 stride-2 max-pool
+ *       (floor mode) at each |; taps after relu1_2, 2_2, 3_3, 4_3, 5_3; keys features.{0,2,5,7,10,12,14,17,19,21,24,26,28}.{weight,bias}.
+ *     alex: conv1 3 -> 64, 11x11, stride 4, pad 2; conv2 64 -> 192, 5x5, pad 2; conv3-5 3x3 pad 1, 192 -> 384 -> 256 -> 256; a 3x3 stride-2 max-pool
+ *       (no padding, floor mode) after relu1 and after relu2; taps after each of the five ReLUs; keys features.{0,3,6,8,10}.{weight,bias}.
+ *   Distance: per tap l, pixel p, feature vectors a, b: a^ = a / (sqrt(sum_c a_c^2) + 1e-10), b^ likewise; d_p = sum_c w_{l,c} (a^_c - b^_c)^2;
+ *     term_l = mean_p d_p; lpips = sum_l term_l.  w_l: key lin{l}.model.1.weight, [1, C_l, 1, 1].
+ *   Volumes [B, C, D, H, W]: the mean over d of the 2-D value of slice d.  Minimum side (host-checked): 16 for vgg, 31 for alex.
+ *
+ * mf_lpips_prepare_f32: x, y NCHW [B][C][H][W] -> out NHWC [2B][H][W][3], the scaled operand: rows [0, B) from x, rows [B, 2B) from y, so that the
+ *   trunk runs once over both.
+ * mf_conv2d_direct_f32: y = conv(x, w) + bias (bias may be NULL), ReLU with desc.relu, NHWC in and out; a deliberately simple kernel for the layers
+ *   the implicit-GEMM path does not take (Cin = 3, 11x11 stride 4, 5x5): any Cin and Cout, KH, KW <= 11, stride 1 .. 4, any pad >= 0; one fp32 fma chain
+ *   per output value in (kh, kw, cin) order, padding taps skipped, then + bias.  Weights [KH][KW][Cin][Cout] (OIHW permuted once at load time).
+ * mf_relu_f32: in place, x < 0 -> 0 (a NaN stays).  mf_maxpool_nhwc_f32: (k, stride) = (2, 2) or (3, 2), floor mode, no padding; a NaN wins.
+ * mf_lpips_layer_f32: fx, fy [B][P][C] (the two halves of a tap's feature map), w [C] -> per-workgroup partial sums of d_p in `workspace`
+ *   (mf_lpips_workspace_bytes(B, P)); evaluated in fp64 on the fp32 features, channel and pixel sums in a fixed order, no atomics.  A pair's bits depend
+ *   on its own feature values only: not on B, its place in the batch, or the load path (16-byte loads when both operands are 16-byte aligned and
+ *   C % 4 == 0, else element-wise).  An all-zero vector gives a^ = 0; identical maps give exactly 0.
+ * mf_lpips_finish_f32: terms[b][layer] (fp64, [B][layers]) = the pair's partials added in ascending order / P; with total != NULL also
+ *   total[b] = (float)(terms[b][0] + ... + terms[b][layers - 1]) in ascending order (pass it with the last layer).
+ * Refused before any launch, MF_EINVAL unless stated: a null pointer, a side below the minimum, C not 1 or 3, a (k, stride) pair other than the two, sizes
+ * outside the ranges above, a workspace too small (MF_EWORKSPACE). */
+#define MF_LPIPS_VGG 0
+#define MF_LPIPS_ALEX 1
+typedef struct MfDirectConvDesc {
+  int32_t N, Hin, Win;
+  int32_t Cin, Cout;
+  int32_t KH, KW;          /* 1 .. 11 */
+  int32_t stride;          /* 1 .. 4 */
+  int32_t pad;             /* >= 0 */
+  int32_t relu;            /* != 0: y = max(y, 0) after the bias */
+  int32_t reserved;        /* 0 */
+  int32_t reserved2;
+} MfDirectConvDesc;
+int mf_lpips_min_side(int net);
+int mf_lpips_prepare_f32(const float* x, const float* y, float* out, int B, int C, int H, int W, int normalize, int net, void* stream);
+int mf_conv2d_direct_out_dims(const MfDirectConvDesc* d, int32_t* out2);
+int mf_conv2d_direct_f32(const float* x, const float* w_hwio, const float* bias, float* y, const MfDirectConvDesc* d, void* stream);
+int mf_relu_f32(float* x, int64_t n, void* stream);
+int mf_maxpool_nhwc_f32(const float* x, float* y, int N, int H, int W, int C, int k, int stride, void* stream);
+int mf_lpips_layer_parts(int64_t P);
+size_t mf_lpips_workspace_bytes(int B, int64_t P);
+int mf_lpips_layer_f32(const float* fx, const float* fy, const float* w, void* workspace, size_t workspace_bytes, int B, int64_t P, int C, void* stream);
+int mf_lpips_finish_f32(const void* workspace, double* terms, float* total, int B, int64_t P, int layer, int layers, void* stream);
+
 /* ------------------------------------------------------------------ built-in launch timing (bench / roofline)
  * When enabled every launch is bracketed by hipEvents on its own stream and attributed to a kernel family.
  * NOT capture-safe; off by default. */

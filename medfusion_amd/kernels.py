@@ -266,7 +266,7 @@ def _f32(what: str, *ts):
             raise RuntimeError(f"medfusion_amd: {what}: fp32 tensors only, got {t.dtype}")
 
 
-_DTYPE_NAMES = {torch.float32: "fp32", torch.int64: "int64", torch.int32: "int32"}
+_DTYPE_NAMES = {torch.float32: "fp32", torch.float64: "fp64", torch.int64: "int64", torch.int32: "int32"}
 
 
 def _dense(what: str, name: str, t, dtype=torch.float32, shape=None, dim: Optional[int] = None, contiguous: bool = True, written: bool = False) -> None:
@@ -1920,6 +1920,96 @@ def guide(pred: torch.Tensor, table: torch.Tensor, *, pred_uncond: Optional[torc
                       int(objective), B, int(stages), 0, 0)
     L.check(L.load().mf_guide_f32(C.byref(a), stream()), "mf_guide_f32")
     return out
+
+
+def lpips_prepare(x: torch.Tensor, y: torch.Tensor, normalize: bool, net: int) -> torch.Tensor:
+    """x, y NCHW [B, 1|3, H, W] -> the scaling layer's output of both as one NHWC batch [2B, H, W, 3] (mf_lpips_prepare_f32)"""
+    _dense("lpips_prepare", "x", x, dim=4)
+    _dense("lpips_prepare", "y", y, shape=x.shape)
+    _gpu(x, y)
+    B, Cc, H, W = x.shape
+    out = torch.empty((2 * B, H, W, 3), dtype=torch.float32, device=x.device)
+    L.check(L.load().mf_lpips_prepare_f32(x.data_ptr(), y.data_ptr(), out.data_ptr(), B, Cc, H, W, int(bool(normalize)), net, stream()), "mf_lpips_prepare_f32")
+    return out
+
+
+def make_direct_conv_desc(N, Hin, Win, Cin, Cout, kh, kw, stride, pad, relu=False) -> L.MfDirectConvDesc:
+    return L.MfDirectConvDesc(N, Hin, Win, Cin, Cout, kh, kw, stride, pad, int(bool(relu)), 0, 0)
+
+
+def direct_conv_out_hw(d: L.MfDirectConvDesc):
+    out = (C.c_int32 * 2)()
+    L.check(L.load().mf_conv2d_direct_out_dims(C.byref(d), out), "mf_conv2d_direct_out_dims")
+    return int(out[0]), int(out[1])
+
+
+def pack_direct_conv_weight(w_oihw: torch.Tensor) -> torch.Tensor:
+    """OIHW -> [KH][KW][Cin][Cout], the layout mf_conv2d_direct_f32 reads (a copy at load time)"""
+    return w_oihw.detach().permute(2, 3, 1, 0).contiguous()
+
+
+def conv2d_direct(x: torch.Tensor, w_hwio: torch.Tensor, bias: Optional[torch.Tensor], d: L.MfDirectConvDesc) -> torch.Tensor:
+    """y = conv(x, w) + bias (+ ReLU with d.relu), NHWC [N, Ho, Wo, Cout] (mf_conv2d_direct_f32: any Cin / Cout, kernels up to 11 x 11, stride 1 .. 4)"""
+    what = "conv2d_direct"
+    _dense(what, "x", x, shape=(d.N, d.Hin, d.Win, d.Cin))
+    _dense(what, "w", w_hwio, shape=(d.KH, d.KW, d.Cin, d.Cout))
+    if bias is not None:
+        _dense(what, "bias", bias, shape=(d.Cout,))
+    _gpu(x, w_hwio, bias)
+    ho, wo = direct_conv_out_hw(d)
+    out = torch.empty((d.N, ho, wo, d.Cout), dtype=torch.float32, device=x.device)
+    L.check(L.load().mf_conv2d_direct_f32(x.data_ptr(), w_hwio.data_ptr(), _ptr(bias), out.data_ptr(), C.byref(d), stream()), "mf_conv2d_direct_f32")
+    return out
+
+
+def relu_(x: torch.Tensor) -> torch.Tensor:
+    """x = max(x, 0) in place (mf_relu_f32)"""
+    _dense("relu_", "x", x)
+    _gpu(x)
+    drop_split(x)
+    if x.numel():
+        L.check(L.load().mf_relu_f32(x.data_ptr(), x.numel(), stream()), "mf_relu_f32")
+    return x
+
+
+def maxpool_nhwc(x: torch.Tensor, k: int, stride: int) -> torch.Tensor:
+    """max-pool of an NHWC tensor, (k, stride) = (2, 2) or (3, 2), floor mode, no padding (mf_maxpool_nhwc_f32)"""
+    _dense("maxpool_nhwc", "x", x, dim=4)
+    _gpu(x)
+    N, H, W, Cc = x.shape
+    if (k, stride) not in ((2, 2), (3, 2)) or H < k or W < k:
+        raise RuntimeError(f"medfusion_amd: maxpool_nhwc: window {k} stride {stride} on sides {H} x {W}: (2, 2) or (3, 2), sides of at least the window")
+    out = torch.empty((N, (H - k) // stride + 1, (W - k) // stride + 1, Cc), dtype=torch.float32, device=x.device)
+    L.check(L.load().mf_maxpool_nhwc_f32(x.data_ptr(), out.data_ptr(), N, H, W, Cc, k, stride, stream()), "mf_maxpool_nhwc_f32")
+    return out
+
+
+def lpips_layer(fx: torch.Tensor, fy: torch.Tensor, w: torch.Tensor, terms: Optional[torch.Tensor] = None, layer: int = 0,
+                total: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """term_l of B pairs of feature maps fx, fy [B, ..., C] (NHWC) under the linear weights w [C] -> terms[:, layer] (fp64 [B, layers]; None: a fresh
+    [B, 1]); with `total` (fp32 [B]) also the sum of the pair's terms (mf_lpips_layer_f32 + mf_lpips_finish_f32; partials in the per-stream workspace)"""
+    what = "lpips_layer"
+    _dense(what, "fx", fx)
+    _dense(what, "fy", fy, shape=fx.shape)
+    if fx.dim() < 2:
+        raise RuntimeError(f"medfusion_amd: {what}: fx must be [B, ..., C], got shape {tuple(fx.shape)}")
+    B, Cc = fx.shape[0], fx.shape[-1]
+    _dense(what, "w", w, shape=(Cc,))
+    if terms is None:
+        terms = torch.empty((B, 1), dtype=torch.float64, device=fx.device)
+    _dense(what, "terms", terms, dtype=torch.float64, dim=2, written=True)
+    if terms.shape[0] != B or not 0 <= layer < terms.shape[1]:
+        raise RuntimeError(f"medfusion_amd: {what}: terms {tuple(terms.shape)} must be [B = {B}, layers > {layer}]")
+    if total is not None:
+        _dense(what, "total", total, shape=(B,), written=True)
+    _gpu(fx, fy, w, terms, total)
+    P = fx.numel() // (B * Cc)
+    lib = L.load()
+    need = lib.mf_lpips_workspace_bytes(B, P)
+    ws = Workspace.get(need, fx.device)
+    L.check(lib.mf_lpips_layer_f32(fx.data_ptr(), fy.data_ptr(), w.data_ptr(), ws.data_ptr(), need, B, P, Cc, stream()), "mf_lpips_layer_f32")
+    L.check(lib.mf_lpips_finish_f32(ws.data_ptr(), terms.data_ptr(), _ptr(total), B, P, layer, terms.shape[1], stream()), "mf_lpips_finish_f32")
+    return terms
 
 
 def absdiff_mean_c(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:

@@ -112,6 +112,13 @@ class MfResampleArgs(C.Structure):
                 + [(n, C.c_int32) for n in ("N", "C", "dtype", "h", "w", "out_mode", "reserved", "reserved2")])
 
 
+LPIPS_VGG, LPIPS_ALEX = 0, 1
+
+
+class MfDirectConvDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("N", "Hin", "Win", "Cin", "Cout", "KH", "KW", "stride", "pad", "relu", "reserved", "reserved2")]
+
+
 TRAJ_RECORD, TRAJ_KEEP = 0, 1
 
 
@@ -268,6 +275,16 @@ _SIGS = {
     "mf_resample_plan": (_I, [C.POINTER(MfResampleImage), _I, _I, _I, _I, _I, c_fp, _I64, _I64, _I64, C.POINTER(MfResamplePlan)]),
     "mf_image_resample": (_I, [C.POINTER(MfResampleArgs), c_fp]),
     "mf_minmax_apply_f32": (_I, [c_fp, c_fp, _I, _I64, _I, c_fp]),
+    "mf_lpips_min_side": (_I, [_I]),
+    "mf_lpips_prepare_f32": (_I, [c_fp, c_fp, c_fp, _I, _I, _I, _I, _I, _I, c_fp]),
+    "mf_conv2d_direct_out_dims": (_I, [C.POINTER(MfDirectConvDesc), C.POINTER(C.c_int32)]),
+    "mf_conv2d_direct_f32": (_I, [c_fp, c_fp, c_fp, c_fp, C.POINTER(MfDirectConvDesc), c_fp]),
+    "mf_relu_f32": (_I, [c_fp, _I64, c_fp]),
+    "mf_maxpool_nhwc_f32": (_I, [c_fp, c_fp, _I, _I, _I, _I, _I, _I, c_fp]),
+    "mf_lpips_layer_parts": (_I, [_I64]),
+    "mf_lpips_workspace_bytes": (_SZ, [_I, _I64]),
+    "mf_lpips_layer_f32": (_I, [c_fp, c_fp, c_fp, c_fp, _SZ, _I, _I64, _I, c_fp]),
+    "mf_lpips_finish_f32": (_I, [c_fp, c_fp, c_fp, _I, _I64, _I, _I, c_fp]),
     "mf_absdiff_mean_c_f32": (_I, [c_fp, c_fp, c_fp, _I, _I, _I64, c_fp]),
     "mf_select_cells_f32": (_I, [c_fp, c_fp, c_fp, c_fp, _I, _I, _I64, c_fp]),
     "mf_window_gather_f32": (_I, [c_fp, c_fp, C.POINTER(MfWindowDesc), c_fp]),

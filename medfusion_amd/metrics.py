@@ -226,14 +226,16 @@ class ReconstructionMeter:
     """MS-SSIM and MSE of an embedder's reconstructions, accumulated on the device.  update(x) takes x in [-1, 1], runs
     embedder(x)[0].clamp(-1, 1), maps both to [0, 1] and keeps the per-image MS-SSIM (data_range=None: the range of each pair) and MSE;
     compute() is the only host sync: the mean and torch.std of each over all images seen.  `noise`: the NoiseSource handed to the embedder
-    (a VAE draws its latent); None leaves the embedder its default, exactly as a bare embedder(x) -- the meter itself draws nothing."""
+    (a VAE draws its latent); None leaves the embedder its default, exactly as a bare embedder(x) -- the meter itself draws nothing.
+    `lpips`: an LPIPSNet (medfusion_amd.lpips); update() then also keeps LPIPS of (x, reconstruction) in [-1, 1], and compute() adds
+    "lpips_mean", "lpips_std" and "lpips_score" = 1 - mean (the reference script's figure).  None: exactly the figures above."""
 
-    def __init__(self, embedder, noise=None):
-        self.embedder, self.noise = embedder, noise
+    def __init__(self, embedder, noise=None, lpips=None):
+        self.embedder, self.noise, self.lpips = embedder, noise, _check_lpips_net(lpips)
         self.reset()
 
     def reset(self) -> None:
-        self._ms, self._mse = [], []
+        self._ms, self._mse, self._lp = [], [], []
 
     @torch.no_grad()
     def update(self, x: torch.Tensor) -> None:
@@ -243,6 +245,9 @@ class ReconstructionMeter:
         v, e = ms_ssim_and_mse(a, b, data_range=None)
         self._ms.append(v)
         self._mse.append(e)
+        if self.lpips is not None:
+            from .lpips import lpips
+            self._lp.append(lpips(x, pred, self.lpips))
 
     def values(self):
         """the per-image MS-SSIM and MSE so far, as two device tensors"""
@@ -250,7 +255,30 @@ class ReconstructionMeter:
             raise ValueError("ReconstructionMeter: no update() yet")
         return torch.cat(self._ms), torch.cat(self._mse)
 
+    def lpips_values(self) -> torch.Tensor:
+        """the per-image LPIPS so far, as a device tensor (a meter built with lpips=net)"""
+        if not self._lp:
+            raise ValueError("ReconstructionMeter: no update() with an LPIPS net yet")
+        return torch.cat(self._lp)
+
     def compute(self) -> dict:
         ms, err = self.values()
-        stats = torch.stack([ms.mean(), torch.std(ms), err.mean(), torch.std(err)]).tolist()     # one copy to the host
-        return {"ms_ssim_mean": stats[0], "ms_ssim_std": stats[1], "mse_mean": stats[2], "mse_std": stats[3], "count": int(ms.numel())}
+        return _summary(ms, err, self.lpips_values() if self.lpips is not None else None)
+
+
+def _check_lpips_net(net):
+    if net is not None:
+        from .lpips import LPIPSNet
+        if not isinstance(net, LPIPSNet):
+            raise ValueError(f"lpips: None or an LPIPSNet, got {type(net).__name__}")
+    return net
+
+
+def _summary(ms: torch.Tensor, err: torch.Tensor, lp: Optional[torch.Tensor]) -> dict:
+    """the meters' compute(): one copy to the host"""
+    rows = [ms.mean(), torch.std(ms), err.mean(), torch.std(err)] + ([lp.mean(), torch.std(lp)] if lp is not None else [])
+    stats = torch.stack(rows).tolist()
+    res = {"ms_ssim_mean": stats[0], "ms_ssim_std": stats[1], "mse_mean": stats[2], "mse_std": stats[3], "count": int(ms.numel())}
+    if lp is not None:
+        res.update(lpips_mean=stats[4], lpips_std=stats[5], lpips_score=1.0 - stats[4])
+    return res

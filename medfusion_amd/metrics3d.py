@@ -19,7 +19,7 @@ import torch
 
 from . import kernels as K
 from . import lib as L
-from .metrics import BETAS, _check_ms, _check_range, _check_window, _combine, gaussian_taps, plan_pairs
+from .metrics import BETAS, _check_lpips_net, _check_ms, _check_range, _check_window, _combine, _summary, gaussian_taps, plan_pairs
 
 # the partial sums of one launch: P C tiles 24 bytes, a tile being 16 x 16 x 16 window origins (mf_ssim3d_workspace_bytes).  A pair of 1 x 64 x 128 x 128
 # volumes is 256 tiles = 6 KiB at scale 0 (an image pair of the 2-D metric: 64 tiles of 32 x 32 at 256 x 256), a pair of 1 x 256^3 4096 tiles =
@@ -202,16 +202,18 @@ class VolumeReconstructionMeter:
     takes x [B, C, D, H, W] in [-1, 1], runs embedder(x)[0].clamp(-1, 1), maps both to [0, 1] and keeps the per-volume MS-SSIM (data_range=None:
     the range of each pair) and MSE, both from one pass; compute() is the only host sync: the mean and torch.std of each over all volumes seen.
     `noise`: the NoiseSource handed to the embedder; None leaves the embedder its default, exactly as a bare embedder(x) -- the meter draws nothing.
-    The default pyramid is betas_for(3) at 11 taps (sides >= 44): what the published 64 x 128 x 128 volume admits."""
+    The default pyramid is betas_for(3) at 11 taps (sides >= 44): what the published 64 x 128 x 128 volume admits.
+    `lpips`: an LPIPSNet; update() then also keeps LPIPS of (x, reconstruction) -- per slice, the mean over depth -- and compute() adds "lpips_mean",
+    "lpips_std" and "lpips_score" = 1 - mean.  None: exactly the figures above."""
 
-    def __init__(self, embedder, noise=None, *, betas: Sequence[float] = betas_for(3), kernel_size: int = 11, sigma: float = 1.5):
+    def __init__(self, embedder, noise=None, *, betas: Sequence[float] = betas_for(3), kernel_size: int = 11, sigma: float = 1.5, lpips=None):
         _check_window(kernel_size, sigma)
-        self.embedder, self.noise = embedder, noise
+        self.embedder, self.noise, self.lpips = embedder, noise, _check_lpips_net(lpips)
         self.betas, self.kernel_size, self.sigma = _check_ms(betas, "relu"), kernel_size, sigma
         self.reset()
 
     def reset(self) -> None:
-        self._ms, self._mse = [], []
+        self._ms, self._mse, self._lp = [], [], []
 
     @torch.no_grad()
     def update(self, x: torch.Tensor) -> None:
@@ -221,6 +223,9 @@ class VolumeReconstructionMeter:
         v, e = ms_ssim3d_and_mse(a, b, data_range=None, betas=self.betas, kernel_size=self.kernel_size, sigma=self.sigma)
         self._ms.append(v)
         self._mse.append(e)
+        if self.lpips is not None:
+            from .lpips import lpips
+            self._lp.append(lpips(x, pred, self.lpips))
 
     def values(self):
         """the per-volume MS-SSIM and MSE so far, as two device tensors"""
@@ -228,7 +233,12 @@ class VolumeReconstructionMeter:
             raise ValueError("VolumeReconstructionMeter: no update() yet")
         return torch.cat(self._ms), torch.cat(self._mse)
 
+    def lpips_values(self) -> torch.Tensor:
+        """the per-volume LPIPS so far, as a device tensor (a meter built with lpips=net)"""
+        if not self._lp:
+            raise ValueError("VolumeReconstructionMeter: no update() with an LPIPS net yet")
+        return torch.cat(self._lp)
+
     def compute(self) -> dict:
         ms, err = self.values()
-        stats = torch.stack([ms.mean(), torch.std(ms), err.mean(), torch.std(err)]).tolist()     # one copy to the host
-        return {"ms_ssim_mean": stats[0], "ms_ssim_std": stats[1], "mse_mean": stats[2], "mse_std": stats[3], "count": int(ms.numel())}
+        return _summary(ms, err, self.lpips_values() if self.lpips is not None else None)

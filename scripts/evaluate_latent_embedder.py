@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Reconstruction quality of a latent embedder over a folder of images: MS-SSIM and MSE of embedder(x)[0].clamp(-1, 1) against x, the two
-figures of the reference's evaluation driver that need no downloaded weights, computed on the device (medfusion_amd.metrics.ReconstructionMeter).
+figures of the reference's evaluation driver that need no downloaded weights, computed on the device (medfusion_amd.metrics.ReconstructionMeter),
+and -- given the trunk and linear-layer files -- its third figure, LPIPS (medfusion_amd.lpips).
 
 A folder of PNG files of one size goes to the device as bytes and becomes fp32 NCHW in [-1, 1] there (mf_image_ingress_u8); every batch runs
 through the embedder, both images are mapped to [0, 1], and the per-image MS-SSIM (the range of each pair as data range, relu-normalised -- what
@@ -8,8 +9,10 @@ the reference's per-image call computes) and MSE stay on the device until the en
 
   python scripts/evaluate_latent_embedder.py --checkpoint runs/.../last_vae.ckpt --images reference_test/ --out results/metrics
 
-Writes metrics_<time>.log (MS-SSIM: mean ± std, MSE: mean ± std, in the reference's wording) and metrics_<time>.json next to it.  LPIPS needs VGG
-weights and is not built.  --synthetic builds the tiny test architecture with seeded weights in place of a checkpoint (a smoke run)."""
+Writes metrics_<time>.log (MS-SSIM: mean ± std, MSE: mean ± std, in the reference's wording) and metrics_<time>.json next to it.  LPIPS needs a
+pretrained trunk: --lpips-net vgg|alex --lpips-trunk FILE --lpips-lin FILE take the torchvision state dict and the lpips package's linear-layer file from
+disk (nothing is downloaded) and add `LPIPS Score: 1 - mean`; without them the log says so.  --synthetic builds the tiny test architecture with
+seeded weights in place of a checkpoint (a smoke run)."""
 import argparse
 import json
 import logging
@@ -34,7 +37,10 @@ def parse_args(argv=None):
     ap.add_argument("--seed", type=int, default=0, help="Philox key of the draws a VAE / VAEGAN makes")
     from medfusion_amd.ingest import add_ingest_arguments
     add_ingest_arguments(ap)
+    from medfusion_amd.lpips import add_lpips_arguments, net_from_args
+    add_lpips_arguments(ap)
     args = ap.parse_args(argv)
+    args.lpips = net_from_args(args, ap.error)
     if (args.checkpoint is None) == (not args.synthetic):
         ap.error("exactly one of --checkpoint and --synthetic")
     if args.batch < 1:
@@ -119,15 +125,20 @@ def main(argv=None):
     model = build_embedder(args).to(device).eval()
     channels = getattr(model, "in_channels", None) or 3
     noise = FolderNoise(args.seed)
-    meter = ReconstructionMeter(model, noise=noise)
+    meter = ReconstructionMeter(model, noise=noise, lpips=args.lpips)
     for lo in range(0, len(files), args.batch):
         noise.offset = lo
         meter.update(load_batch(files[lo:lo + args.batch], channels, device, args))
     res = meter.compute()
-    logger.info("LPIPS: not built (needs VGG weights)")
+    if args.lpips is None:
+        logger.info("LPIPS: not built (needs VGG weights)")
+    else:
+        logger.info(f"LPIPS Score: {res['lpips_score']}")
     logger.info(f"MS-SSIM: {res['ms_ssim_mean']} ± {res['ms_ssim_std']}")
     logger.info(f"MSE: {res['mse_mean']} ± {res['mse_std']}")
     res.update(images=str(args.images), checkpoint=args.checkpoint, embedder=args.embedder, synthetic=args.synthetic, lpips=None)
+    if args.lpips is not None:
+        res.update(lpips=res["lpips_score"], lpips_net=args.lpips_net)
     (out / f"metrics_{stamp}.json").write_text(json.dumps(res, indent=1) + "\n")
     return res
 

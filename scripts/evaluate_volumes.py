@@ -36,7 +36,12 @@ def parse_args(argv=None):
     ap.add_argument("--pairs", type=int, default=None, help="also / only the pairwise MS-SSIM of the set over this many distinct random pairs")
     ap.add_argument("--seed", type=int, default=0, help="Philox key of the draws a VAE makes; seed of the pair draw")
     ap.add_argument("--out", default="results/metrics3d", help="folder of the log and the JSON")
+    from medfusion_amd.lpips import add_lpips_arguments, net_from_args
+    add_lpips_arguments(ap)
     args = ap.parse_args(argv)
+    args.lpips = net_from_args(args, ap.error)
+    if args.lpips is not None and args.checkpoint is None:
+        ap.error("--lpips-net: LPIPS is a figure of the reconstructions (--checkpoint)")
     if args.checkpoint is None and args.pairs is None:
         ap.error("at least one of --checkpoint (reconstruction) and --pairs (diversity)")
     if not 1 <= args.scales <= 5:
@@ -116,13 +121,15 @@ def main(argv=None):
         from medfusion_amd.checkpoint import load_module_from_checkpoint
         model = load_module_from_checkpoint(M.VAE, args.checkpoint).to(device).eval()
         noise = FolderNoise(args.seed)
-        meter = M.VolumeReconstructionMeter(model, noise=noise, betas=betas, kernel_size=args.kernel_size)
+        meter = M.VolumeReconstructionMeter(model, noise=noise, betas=betas, kernel_size=args.kernel_size, lpips=args.lpips)
         for lo in range(0, len(files), args.batch):
             noise.offset = lo
             meter.update(load_batch(files[lo:lo + args.batch], args.unit_range, device))
         res.update(meter.compute())
         logger.info(f"MS-SSIM: {res['ms_ssim_mean']} ± {res['ms_ssim_std']}")
         logger.info(f"MSE: {res['mse_mean']} ± {res['mse_std']}")
+        if args.lpips is not None:
+            logger.info(f"LPIPS Score: {res['lpips_score']}")
     if args.pairs is not None:
         if len(files) < 2:
             raise SystemExit(f"{args.volumes}: at least two volumes make a pair")
