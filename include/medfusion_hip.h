@@ -1161,6 +1161,77 @@ size_t mf_lpips_workspace_bytes(int B, int64_t P);
 int mf_lpips_layer_f32(const float* fx, const float* fy, const float* w, void* workspace, size_t workspace_bytes, int B, int64_t P, int C, void* stream);
 int mf_lpips_finish_f32(const void* workspace, double* terms, float* total, int B, int64_t P, int layer, int layers, void* stream);
 
+/* ------------------------------------------------------------------ Inception (additive to ABI 250): the FID variant of Inception-v3 and its layers
+ * Replaces the feature extractor behind torchmetrics' FrechetInceptionDistance and torch-fidelity's precision / recall at scripts/evaluate_images.py
+ * ("FID Score", "Precision", "Recall"): torch-fidelity's `inception-v3-compat`, read from pt_inception-2015-12-05-6726825d.pth.  Nothing pretrained is
+ * shipped or fetched: the caller loads the file a reference run has in its torch hub cache.
+ *
+ * Definition.  Input: uint8 [B][C][H][W], C in {1, 3}; one channel is replicated to three.
+ *   Resize: TF1-style bilinear to S x S (299 is the metric; any S >= 75 runs).  Per axis, s = fl32(in / S): g = fl32(i s), lo = int(g), hi = min(lo + 1,
+ *     in - 1), d = fl32(g - lo) -- no half-pixel offset.  top = fl32(a00 + fl32(fl32(a01 - a00) dx)), bottom likewise, v = fl32(top + fl32(fl32(bottom -
+ *     top) dy)), out = fl32(fl32(v - 128) / 128), written NHWC.  The resize always runs; with in = S it is the identity on the values.
+ *   BasicConv: a convolution without bias, BatchNorm (eps = 0.001, eval mode), ReLU.  The BatchNorm is folded once on the host in fp64:
+ *     s = gamma / sqrt(var + eps), w' = fl32(w s), b' = fl32(beta - mean s); the network is DEFINED as the convolution with w', b' and ReLU.
+ *   Trunk (k square unless (kh, kw); padding (k - 1) / 2 per axis only where marked p; output side at 299 in brackets):
+ *     Conv2d_1a_3x3 3 -> 32 k3 s2 [149]; Conv2d_2a_3x3 32 -> 32 k3 [147]; Conv2d_2b_3x3 32 -> 64 k3 p [147]; max-pool 3 s2 [73] (tap "64");
+ *     Conv2d_3b_1x1 64 -> 80 [73]; Conv2d_4a_3x3 80 -> 192 k3 [71]; max-pool 3 s2 [35] (tap "192");
+ *     Mixed_5b / 5c / 5d = A(in 192 / 256 / 288, pool 32 / 64 / 64) [35]; Mixed_6a = B(288) [17]; Mixed_6b .. 6e = C(768, c7 128 / 160 / 160 / 192) [17]
+ *     (tap "768"); Mixed_7a = D(768) [8]; Mixed_7b = E(1280, avg) [8]; Mixed_7c = E(2048, max) [8]; the mean over the pixels [B][2048] (tap "2048");
+ *     fc 2048 -> F rows (1008 in the FID file): logits_unbiased without the bias, logits with it.
+ *   Blocks, concatenated in the order written:
+ *     A: branch1x1 in -> 64 | branch5x5_1 in -> 48, _2 48 -> 64 k5 p | branch3x3dbl_1 in -> 64, _2 64 -> 96 k3 p, _3 96 -> 96 k3 p | avg-pool(3, s1,
+ *        pad 1, divisor = the number of valid taps), branch_pool in -> pool k1.
+ *     B: branch3x3 in -> 384 k3 s2 | branch3x3dbl_1 in -> 64, _2 64 -> 96 k3 p, _3 96 -> 96 k3 s2 | max-pool(3, s2) of the input.
+ *     C: branch1x1 in -> 192 | branch7x7_1 in -> c7, _2 c7 -> c7 (1,7) p, _3 c7 -> 192 (7,1) p | branch7x7dbl_1 in -> c7, _2 (7,1) p, _3 (1,7) p,
+ *        _4 (7,1) p (all c7 -> c7), _5 c7 -> 192 (1,7) p | the avg-pool of A, branch_pool in -> 192.
+ *     D: branch3x3_1 in -> 192, _2 192 -> 320 k3 s2 | branch7x7x3_1 in -> 192, _2 (1,7) p, _3 (7,1) p (192 -> 192), _4 192 -> 192 k3 s2 | max-pool(3, s2).
+ *     E: branch1x1 in -> 320 | branch3x3_1 in -> 384, then [_2a 384 -> 384 (1,3) p, _2b 384 -> 384 (3,1) p] both of _1 | branch3x3dbl_1 in -> 448,
+ *        _2 448 -> 384 k3 p, then [_3a (1,3) p, _3b (3,1) p] both of _2 | the avg-pool of A (Mixed_7b) or max-pool(3, s1, pad 1) (Mixed_7c), branch_pool
+ *        in -> 192.
+ *   Keys: {layer}.conv.weight, {layer}.bn.{weight, bias, running_mean, running_var}, fc.weight, fc.bias; AuxLogits.* and *.num_batches_tracked ignored.
+ *   Pools: max = the largest valid tap, a NaN wins; avg = the fp32 sum of the valid taps in ascending (kh, kw) order, divided once by their number.
+ *   Mean over the pixels: the fp64 sum in ascending order, divided by the number, rounded once to fp32.
+ *
+ * mf_conv2d_gemm_f32: y = conv(x, w) + bias (bias may be NULL), ReLU with desc.relu; NHWC in, weights [KH][KW][Cin][Cout], KH, KW 1 .. 11 independently,
+ *   stride 1 .. 4, pad_h, pad_w >= 0, any Cin, any Cout >= 1.  The value of output channel co of pixel m lands at y[m ldy + y_offset + co]: a branch
+ *   writes straight into its block's concatenated tensor (ldy = 0: dense, ldy = Cout).  An implicit GEMM on v_mfma_f32_32x32x2_f32 with exact fp32
+ *   operands staged through LDS: M = the output pixels of the whole batch, N = Cout, K = (kh, kw, cin) flattened, k = (kh KW + kw) Cin + cin, never split
+ *   across workgroups; padding taps and every tail are staged as zeros.
+ *     chain = 0: one fmaf chain per output value over all of K ascending from +0, then + bias: the arithmetic of mf_conv2d_direct_f32, bit for bit on
+ *       finite data.
+ *     chain = L > 0: with L' = 32 ceil(L / 32), the K axis is cut at k = L', 2 L', ... (< K): piece j = [j L', min((j + 1) L', K)) is its own fmaf chain
+ *       from +0, t_0 = piece 0, t_j = fl32(t_{j-1} + piece j) in ascending order in registers, then + bias.  The cuts depend on (KH, KW, Cin, L) only.
+ *     tile = 0: the planner picks (from M and Cout); 1: 128 x 128, 2: 128 x 64, 3: 64 x 64 (pixels x channels per workgroup).  No bit of the output
+ *       depends on the tile, the batch, the pixel's place in it, ldy / y_offset, or the load path (16-byte loads when Cin % 4 == 0, Cout % 4 == 0 and both
+ *       operands are 16-byte aligned, else element by element).
+ *   mf_conv2d_gemm_out_dims -> (Hout, Wout); mf_conv2d_gemm_plan -> (tile, workgroups).  Both host-only.
+ * mf_pool2d_nhwc_f32: window 3, stride 1 or 2, pad 0 or 1, floor mode, mode MF_POOL_MAX or MF_POOL_AVG_VALID as defined above; ldy / y_offset as above.
+ * mf_inception_prepare_u8: x uint8 NCHW [B][C][H][W] -> out fp32 NHWC [B][S][S][3]: the resize, the value map and the replication of the definition.
+ * mf_mean_pixels_f32: x [B][P][C] -> out [B][C], the mean over the pixels of the definition; a row's bits do not depend on B or its place.
+ * Refused before any launch, MF_EINVAL unless stated: a null pointer, C not 1 or 3, S < 75 or > 4096, a side above 16384, sizes outside the ranges above,
+ * a slice outside ldy, a non-zero reserved field; a problem too large for the index arithmetic (MF_EUNSUPPORTED). */
+#define MF_POOL_MAX 0
+#define MF_POOL_AVG_VALID 1
+#define MF_INCEPTION_MIN_SIZE 75
+typedef struct MfGemmConvDesc {
+  int32_t N, Hin, Win;
+  int32_t Cin, Cout;
+  int32_t KH, KW;          /* 1 .. 11, independently */
+  int32_t stride;          /* 1 .. 4 */
+  int32_t pad_h, pad_w;    /* >= 0 */
+  int32_t relu;            /* != 0: y = max(y, 0) after the bias */
+  int32_t ldy, y_offset;   /* channels of an output pixel (0: Cout) and the first one written */
+  int32_t chain;           /* 0: one chain over K; L > 0: pieces of 32 ceil(L / 32) */
+  int32_t tile;            /* 0: planned; 1 .. 3: forced */
+  int32_t reserved;        /* 0 */
+} MfGemmConvDesc;
+int mf_conv2d_gemm_out_dims(const MfGemmConvDesc* d, int32_t* out2);
+int mf_conv2d_gemm_plan(const MfGemmConvDesc* d, int32_t* out2);
+int mf_conv2d_gemm_f32(const float* x, const float* w_hwio, const float* bias, float* y, const MfGemmConvDesc* d, void* stream);
+int mf_pool2d_nhwc_f32(const float* x, float* y, int N, int H, int W, int C, int stride, int pad, int mode, int ldy, int y_offset, void* stream);
+int mf_inception_prepare_u8(const uint8_t* x, float* out, int B, int C, int H, int W, int S, void* stream);
+int mf_mean_pixels_f32(const float* x, float* out, int B, int64_t P, int C, void* stream);
+
 /* ------------------------------------------------------------------ built-in launch timing (bench / roofline)
  * When enabled every launch is bracketed by hipEvents on its own stream and attributed to a kernel family.
  * NOT capture-safe; off by default. */

@@ -5,9 +5,10 @@ Drop-in for the reference's sampling API (`DiffusionPipeline.sample/denoise/forw
 C-ABI (include/medfusion_hip.h).  No CPU fallback: the library must load and tensors must be on the GPU.
 """
 from .lib import load as load_library  # noqa: F401
-from . import fidelity, ingest, lpips, metrics  # noqa: F401
+from . import fidelity, inception, ingest, lpips, metrics  # noqa: F401
 from .fidelity import (EmbedderFeatures, FidelityMeter, density_coverage, frechet_distance, kernel_matrix, kid, knn_radii, manifold_hits,  # noqa: F401
                        memorization_report, mmd2, nearest_neighbours, pairwise_sqdist, plan_kid, precision_recall)
+from .inception import InceptionFeatures, InceptionNet, inception_score  # noqa: F401
 from .lpips import LPIPSNet  # noqa: F401
 from .metrics import ReconstructionMeter, ms_ssim, mse, pairwise_ms_ssim, ssim  # noqa: F401
 from .metrics3d import (VolumeReconstructionMeter, betas_for, min_side3d, ms_ssim3d, ms_ssim3d_and_mse, mse3d, pair_range3d,  # noqa: F401

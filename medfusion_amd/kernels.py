@@ -2012,6 +2012,88 @@ def lpips_layer(fx: torch.Tensor, fy: torch.Tensor, w: torch.Tensor, terms: Opti
     return terms
 
 
+def make_gemm_conv_desc(N, Hin, Win, Cin, Cout, kh, kw, stride=1, pad_h=0, pad_w=0, relu=False, ldy=0, y_offset=0, chain=0, tile=0) -> L.MfGemmConvDesc:
+    return L.MfGemmConvDesc(N, Hin, Win, Cin, Cout, kh, kw, stride, pad_h, pad_w, int(bool(relu)), ldy, y_offset, chain, tile, 0)
+
+
+def gemm_conv_out_hw(d: L.MfGemmConvDesc):
+    out = (C.c_int32 * 2)()
+    L.check(L.load().mf_conv2d_gemm_out_dims(C.byref(d), out), "mf_conv2d_gemm_out_dims")
+    return int(out[0]), int(out[1])
+
+
+def gemm_conv_plan(d: L.MfGemmConvDesc):
+    """(tile id, workgroups) of the launch mf_conv2d_gemm_f32 makes for `d` (host only)"""
+    out = (C.c_int32 * 2)()
+    L.check(L.load().mf_conv2d_gemm_plan(C.byref(d), out), "mf_conv2d_gemm_plan")
+    return int(out[0]), int(out[1])
+
+
+def _sliced_out(what: str, out: Optional[torch.Tensor], shape, ldy: int, y_offset: int, device) -> torch.Tensor:
+    """the output of a launch that writes channels [y_offset, y_offset + shape[-1]) of pixels of `ldy` channels: a fresh dense tensor without `out`"""
+    width = ldy if ldy else shape[-1]
+    if out is None:
+        return torch.empty((*shape[:-1], width), dtype=torch.float32, device=device)
+    _dense(what, "out", out, shape=(*shape[:-1], width), written=True)
+    _gpu(out)
+    drop_split(out)
+    return out
+
+
+def conv2d_gemm(x: torch.Tensor, w_hwio: torch.Tensor, bias: Optional[torch.Tensor], d: L.MfGemmConvDesc, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = conv(x, w) + bias (+ ReLU with d.relu) on the fp32 matrix cores, NHWC; channels [d.y_offset, d.y_offset + Cout) of `out` [N, Ho, Wo, d.ldy or
+    Cout] are written, the others left alone (mf_conv2d_gemm_f32: any Cin / Cout, kernels up to 11 x 11 per axis, stride 1 .. 4)"""
+    what = "conv2d_gemm"
+    _dense(what, "x", x, shape=(d.N, d.Hin, d.Win, d.Cin))
+    _dense(what, "w", w_hwio, shape=(d.KH, d.KW, d.Cin, d.Cout))
+    if bias is not None:
+        _dense(what, "bias", bias, shape=(d.Cout,))
+    _gpu(x, w_hwio, bias)
+    ho, wo = gemm_conv_out_hw(d)
+    out = _sliced_out(what, out, (d.N, ho, wo, d.Cout), d.ldy, d.y_offset, x.device)
+    L.check(L.load().mf_conv2d_gemm_f32(x.data_ptr(), w_hwio.data_ptr(), _ptr(bias), out.data_ptr(), C.byref(d), stream()), "mf_conv2d_gemm_f32")
+    return out
+
+
+def pool2d_nhwc(x: torch.Tensor, stride: int, pad: int, mode: int, out: Optional[torch.Tensor] = None, ldy: int = 0, y_offset: int = 0) -> torch.Tensor:
+    """the 3 x 3 pool of an NHWC tensor, stride 1 or 2, pad 0 or 1, mode L.POOL_MAX or L.POOL_AVG_VALID, into channels [y_offset, y_offset + C) of `out`
+    (mf_pool2d_nhwc_f32)"""
+    what = "pool2d_nhwc"
+    _dense(what, "x", x, dim=4)
+    N, H, W, Cc = x.shape
+    if stride not in (1, 2) or pad not in (0, 1) or H + 2 * pad < 3 or W + 2 * pad < 3:
+        raise RuntimeError(f"medfusion_amd: {what}: stride {stride} (1 or 2), pad {pad} (0 or 1) on sides {H} x {W} (padded sides of at least 3)")
+    _gpu(x)
+    out = _sliced_out(what, out, (N, (H + 2 * pad - 3) // stride + 1, (W + 2 * pad - 3) // stride + 1, Cc), ldy, y_offset, x.device)
+    L.check(L.load().mf_pool2d_nhwc_f32(x.data_ptr(), out.data_ptr(), N, H, W, Cc, stride, pad, mode, ldy, y_offset, stream()), "mf_pool2d_nhwc_f32")
+    return out
+
+
+def inception_prepare(x: torch.Tensor, size: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 NCHW [B, 1|3, H, W] -> the network's operand, fp32 NHWC [B, size, size, 3] (mf_inception_prepare_u8)"""
+    what = "inception_prepare"
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or x.dim() != 4 or not x.is_contiguous():
+        raise RuntimeError(f"medfusion_amd: {what}: x must be a contiguous uint8 [B, C, H, W] tensor, got {getattr(x, 'dtype', type(x).__name__)} {tuple(getattr(x, 'shape', ()))}")
+    _gpu(x)
+    B, Cc, H, W = x.shape
+    out = _sliced_out(what, out, (B, size, size, 3), 0, 0, x.device)
+    L.check(L.load().mf_inception_prepare_u8(x.data_ptr(), out.data_ptr(), B, Cc, H, W, size, stream()), "mf_inception_prepare_u8")
+    return out
+
+
+def mean_pixels(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[B, ..., C] fp32 (NHWC) -> [B, C]: the mean over the pixels, summed in fp64 (mf_mean_pixels_f32)"""
+    what = "mean_pixels"
+    _dense(what, "x", x)
+    if x.dim() < 2 or x.numel() == 0:
+        raise RuntimeError(f"medfusion_amd: {what}: x must be a non-empty [B, ..., C], got shape {tuple(x.shape)}")
+    _gpu(x)
+    B, Cc = x.shape[0], x.shape[-1]
+    out = _sliced_out(what, out, (B, Cc), 0, 0, x.device)
+    L.check(L.load().mf_mean_pixels_f32(x.data_ptr(), out.data_ptr(), B, x.numel() // (B * Cc), Cc, stream()), "mf_mean_pixels_f32")
+    return out
+
+
 def absdiff_mean_c(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """[N,C,...] fp32 x 2 -> [N,1,...]: the mean over the channels of |a - b| (mf_absdiff_mean_c_f32)"""
     _gpu(a, b)

@@ -119,6 +119,14 @@ class MfDirectConvDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("N", "Hin", "Win", "Cin", "Cout", "KH", "KW", "stride", "pad", "relu", "reserved", "reserved2")]
 
 
+POOL_MAX, POOL_AVG_VALID = 0, 1
+INCEPTION_MIN_SIZE = 75
+
+
+class MfGemmConvDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("N", "Hin", "Win", "Cin", "Cout", "KH", "KW", "stride", "pad_h", "pad_w", "relu", "ldy", "y_offset", "chain", "tile", "reserved")]
+
+
 TRAJ_RECORD, TRAJ_KEEP = 0, 1
 
 
@@ -285,6 +293,12 @@ _SIGS = {
     "mf_lpips_workspace_bytes": (_SZ, [_I, _I64]),
     "mf_lpips_layer_f32": (_I, [c_fp, c_fp, c_fp, c_fp, _SZ, _I, _I64, _I, c_fp]),
     "mf_lpips_finish_f32": (_I, [c_fp, c_fp, c_fp, _I, _I64, _I, _I, c_fp]),
+    "mf_conv2d_gemm_out_dims": (_I, [C.POINTER(MfGemmConvDesc), C.POINTER(C.c_int32)]),
+    "mf_conv2d_gemm_plan": (_I, [C.POINTER(MfGemmConvDesc), C.POINTER(C.c_int32)]),
+    "mf_conv2d_gemm_f32": (_I, [c_fp, c_fp, c_fp, c_fp, C.POINTER(MfGemmConvDesc), c_fp]),
+    "mf_pool2d_nhwc_f32": (_I, [c_fp, c_fp, _I, _I, _I, _I, _I, _I, _I, _I, _I, c_fp]),
+    "mf_inception_prepare_u8": (_I, [c_fp, c_fp, _I, _I, _I, _I, _I, c_fp]),
+    "mf_mean_pixels_f32": (_I, [c_fp, c_fp, _I, _I64, _I, c_fp]),
     "mf_absdiff_mean_c_f32": (_I, [c_fp, c_fp, c_fp, _I, _I, _I64, c_fp]),
     "mf_select_cells_f32": (_I, [c_fp, c_fp, c_fp, c_fp, _I, _I, _I64, c_fp]),
     "mf_window_gather_f32": (_I, [c_fp, c_fp, C.POINTER(MfWindowDesc), c_fp]),

@@ -5,11 +5,14 @@ reference's evaluate_images.py, computed on the device (medfusion_amd.fidelity).
 Each of --real and --fake is a folder of PNG files of one size, or a .pt / .npy file of precomputed [N, D] features (what the reference script's
 commented "Load features" block reads; a .pt holding a list of per-batch tensors is concatenated).  Folders need an extractor:
 --features embedder:CKPT[:pool] takes the encoder of a latent embedder the user already has (VAE; or VQVAE:CKPT, VQGAN:CKPT, VAEGAN:CKPT for the other
-classes), optionally average-pooled to pool x pool cells (medfusion_amd.EmbedderFeatures).  The Inception / VGG weights of the reference's own
-extractor have to be downloaded and are not built: pass feature files computed elsewhere to reproduce FID proper.
+classes), optionally average-pooled to pool x pool cells (medfusion_amd.EmbedderFeatures).  --features inception:FILE[:layer] is the reference's own
+extractor, the FID variant of Inception-v3 (medfusion_amd.InceptionNet), from the weight file a reference run has on disk
+(pt_inception-2015-12-05-6726825d.pth; nothing is downloaded): the log then reads "FID Score"; layer: 64, 192, 768, 2048 (default), logits_unbiased or
+logits.  --inception-score [SPLITS] adds the Inception Score of the generated set (needs inception features and a folder as --fake).
 
   python scripts/evaluate_images.py --real real_ipr.pt --fake fake_ipr.pt --out results/metrics
   python scripts/evaluate_images.py --real reference/ --fake generated/ --features embedder:runs/.../last_vae.ckpt:4
+  python scripts/evaluate_images.py --real reference/ --fake generated/ --features inception:pt_inception-2015-12-05-6726825d.pth --inception-score
 
 --density-coverage [KNN] adds density / coverage, --memorization [NEIGHBOURS] the authenticity and the quantiles of the copy ratio of the generated set
 against --real as the training set (medfusion_amd.density_coverage, memorization_report; scripts/nearest_train.py lists the suspicious files); both
@@ -68,6 +71,8 @@ def parse_args(argv=None):
     from medfusion_amd.ingest import add_ingest_arguments
     add_ingest_arguments(ap)
     ap.add_argument("--kid-subset-size", type=int, default=1000, metavar="ROWS", help="rows of a subset of --kid (at most the rows of the smaller set)")
+    ap.add_argument("--inception-score", type=int, nargs="?", const=1, default=None, metavar="SPLITS",
+                    help="also the Inception Score of the generated set over SPLITS splits (1 when given without a value); needs --features inception:FILE")
     args = ap.parse_args(argv)
     if args.kid is not None and not 1 <= args.kid <= 65535:
         ap.error("--kid: 1 .. 65535 subsets")
@@ -83,11 +88,50 @@ def parse_args(argv=None):
         ap.error("--batch: at least 1")
     if args.max_samples is not None and args.max_samples < 2:
         ap.error("--max-samples: at least 2")
-    if args.features is not None:
+    inception = args.features is not None and args.features.startswith("inception:")
+    if inception:
+        from medfusion_amd.ingest import ingest_requested
+        try:
+            parse_inception(args.features)
+        except ValueError as e:
+            ap.error(str(e))
+        if ingest_requested(args):
+            ap.error("--features inception: the network resizes the files itself; not with --resize / --crop")
+    if args.inception_score is not None:
+        if args.inception_score < 1:
+            ap.error("--inception-score: at least 1 split")
+        if not inception or is_feature_file(args.fake):
+            ap.error("--inception-score: needs --features inception:FILE and a folder of images as --fake")
+    if inception:
+        pass                                   # (checked above)
+    elif args.features is not None:
         parse_features(args.features)
     elif not (is_feature_file(args.real) and is_feature_file(args.fake)):
         ap.error("--features embedder:CKPT[:pool] is needed when --real or --fake is a folder of images")
     return args
+
+
+def parse_inception(spec: str):
+    """'inception:FILE[:layer]' -> (FILE, layer); a ValueError otherwise"""
+    from medfusion_amd.inception import parse_features_spec
+    return parse_features_spec(spec)
+
+
+def inception_folder_features(folder, net, layers, batch, max_samples, device, args=None):
+    """the files' own bytes through the network: a tuple of [N, D] tensors, one per layer"""
+    import numpy as np
+    import torch
+
+    from evaluate_latent_embedder import list_images, load_png
+    files = list_images(folder, max_samples, getattr(args, "ext", None))
+    parts = []
+    for lo in range(0, len(files), batch):
+        arrs = [load_png(f, 3) for f in files[lo:lo + batch]]
+        if len({a.shape for a in arrs}) != 1:
+            raise SystemExit(f"the images of a batch are not of one size: {sorted({a.shape for a in arrs})}")
+        x = torch.from_numpy(np.stack(arrs)).to(device).permute(0, 3, 1, 2).contiguous()
+        parts.append(net.features(x, tuple(layers)))
+    return tuple(torch.cat([p[i] for p in parts]) for i in range(len(layers)))
 
 
 def load_features(path, max_samples, expect_2d=None):
@@ -133,7 +177,14 @@ def main(argv=None):
     logger.addHandler(logging.FileHandler(out / f"metrics_{stamp}.log", "w", encoding="utf-8"))      # (the KID line is not ASCII; the others are)
 
     extractor, channels, what = None, 3, "precomputed feature files"
-    if args.features is not None and not (is_feature_file(args.real) and is_feature_file(args.fake)):
+    inception = args.features is not None and args.features.startswith("inception:")
+    net = layer = logits = None
+    if inception:
+        path, layer = parse_inception(args.features)
+        what = f"Inception-v3 (FID variant) of {path}, layer {layer}"
+        if not (is_feature_file(args.real) and is_feature_file(args.fake)):
+            net = M.InceptionNet.from_file(path).to(device)
+    elif args.features is not None and not (is_feature_file(args.real) and is_feature_file(args.fake)):
         from medfusion_amd.checkpoint import load_module_from_checkpoint
         kind, ckpt, pool = parse_features(args.features)
         model = load_module_from_checkpoint(getattr(M, kind), ckpt).to(device).eval()
@@ -144,6 +195,10 @@ def main(argv=None):
     for name, src in (("real", args.real), ("fake", args.fake)):
         if is_feature_file(src):
             sets[name] = load_features(src, args.max_samples).to(device)
+        elif inception:
+            layers = (layer, "logits") if name == "fake" and args.inception_score is not None else (layer,)
+            got = inception_folder_features(src, net, layers, args.batch, args.max_samples, device, args)
+            sets[name], logits = got[0], got[1] if len(got) == 2 else logits
         else:
             sets[name] = folder_features(src, extractor, channels, args.batch, args.max_samples, device, args)
     real, fake = sets["real"], sets["fake"]
@@ -151,8 +206,12 @@ def main(argv=None):
     logger.info(f"Samples Fake: {fake.shape[0]}")
     res = M.precision_recall(real, fake, args.knn)
     res["fd"] = M.frechet_distance(real, fake)
-    logger.info("Inception features: not built (needs downloaded weights); pass precomputed feature files")
-    logger.info(f"FD (features: {what}, D = {real.shape[1]}): {res['fd']}")
+    if inception:
+        logger.info(f"FID Score: {res['fd']}")
+        logger.info(f"Features: {what}, D = {real.shape[1]}")
+    else:
+        logger.info("Inception features: not built (needs downloaded weights); pass precomputed feature files")
+        logger.info(f"FD (features: {what}, D = {real.shape[1]}): {res['fd']}")
     logger.info(f"Precision: {res['precision']}, Recall {res['recall']} ")
     if args.density_coverage is not None:
         dc = M.density_coverage(real, fake, args.density_coverage)
@@ -172,7 +231,11 @@ def main(argv=None):
         kid = M.kid(real, fake, subsets=args.kid, subset_size=size)
         res.update(kid_mean=kid["kid_mean"], kid_std=kid["kid_std"], kid_subsets=args.kid, kid_subset_size=size)
         logger.info(f"KID: {kid['kid_mean']} ± {kid['kid_std']} ({args.kid} × {size})")
-    res.update(real=str(args.real), fake=str(args.fake), features=args.features, feature_width=int(real.shape[1]), inception=None)
+    if logits is not None:
+        score = M.inception_score(logits, args.inception_score)
+        res.update(score, inception_score_splits=args.inception_score)
+        logger.info(f"Inception Score: {score['inception_score_mean']} ± {score['inception_score_std']} ({args.inception_score} splits)")
+    res.update(real=str(args.real), fake=str(args.fake), features=args.features, feature_width=int(real.shape[1]), inception=layer)
     (out / f"metrics_{stamp}.json").write_text(json.dumps(res, indent=1) + "\n")
     return res
 
