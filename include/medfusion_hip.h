@@ -1126,10 +1126,14 @@ int mf_minmax_apply_f32(float* x, const float* minmax, int N, int64_t n, int cen
  *
  * mf_lpips_prepare_f32: x, y NCHW [B][C][H][W] -> out NHWC [2B][H][W][3], the scaled operand: rows [0, B) from x, rows [B, 2B) from y, so that the
  *   trunk runs once over both.
- * mf_conv2d_direct_f32: y = conv(x, w) + bias (bias may be NULL), ReLU with desc.relu, NHWC in and out; a deliberately simple kernel for the layers
- *   the implicit-GEMM path does not take (Cin = 3, 11x11 stride 4, 5x5): any Cin and Cout, KH, KW <= 11, stride 1 .. 4, any pad >= 0; one fp32 fma chain
- *   per output value in (kh, kw, cin) order, padding taps skipped, then + bias.  Weights [KH][KW][Cin][Cout] (OIHW permuted once at load time).
- * mf_relu_f32: in place, x < 0 -> 0 (a NaN stays).  mf_maxpool_nhwc_f32: (k, stride) = (2, 2) or (3, 2), floor mode, no padding; a NaN wins.
+ * mf_conv2d_direct_f32: y = conv(x, w) + bias (bias may be NULL), ReLU with desc.relu, NHWC in and out, for the layers mf_conv2d_f32's implicit-GEMM
+ *   path does not take (Cin = 3, 11x11 stride 4, 5x5): any Cin and Cout, KH, KW <= 11, stride 1 .. 4, any pad >= 0.  DEFINED as mf_conv2d_gemm_f32
+ *   ("Inception" below; one kernel runs both) with pad_h = pad_w = pad, chain = 0, tile = 0 and a dense output: one fp32 fma chain per output value
+ *   from +0 in (kh, kw, cin) order, padding taps as zeros, then + bias.  A padding tap is a term 0 w: it leaves no trace on finite weights, and makes a
+ *   NaN of a non-finite weight under it (the one-thread-per-output kernel this entry ran before skipped those taps).  Its launches are timed as
+ *   MF_FAM_CONV_IGEMM.  Weights [KH][KW][Cin][Cout] (OIHW permuted once at load time).
+ * mf_relu_f32: in place, x < 0 -> 0 (a NaN stays).  mf_maxpool_nhwc_f32: (k, stride) = (2, 2) or (3, 2), floor mode, no padding; a NaN wins; the max
+ *   of mf_pool2d_nhwc_f32's kernel without padding, which also has the window 2.
  * mf_lpips_layer_f32: fx, fy [B][P][C] (the two halves of a tap's feature map), w [C] -> per-workgroup partial sums of d_p in `workspace`
  *   (mf_lpips_workspace_bytes(B, P)); evaluated in fp64 on the fp32 features, channel and pixel sums in a fixed order, no atomics.  A pair's bits depend
  *   on its own feature values only: not on B, its place in the batch, or the load path (16-byte loads when both operands are 16-byte aligned and
@@ -1197,8 +1201,8 @@ int mf_lpips_finish_f32(const void* workspace, double* terms, float* total, int 
  *   writes straight into its block's concatenated tensor (ldy = 0: dense, ldy = Cout).  An implicit GEMM on v_mfma_f32_32x32x2_f32 with exact fp32
  *   operands staged through LDS: M = the output pixels of the whole batch, N = Cout, K = (kh, kw, cin) flattened, k = (kh KW + kw) Cin + cin, never split
  *   across workgroups; padding taps and every tail are staged as zeros.
- *     chain = 0: one fmaf chain per output value over all of K ascending from +0, then + bias: the arithmetic of mf_conv2d_direct_f32, bit for bit on
- *       finite data.
+ *     chain = 0: one fmaf chain per output value over all of K ascending from +0, then + bias.  This is what mf_conv2d_direct_f32 ("LPIPS" above)
+ *       runs; on finite data a padding tap, staged as a zero, leaves the chain's bits as if it were skipped.
  *     chain = L > 0: with L' = 32 ceil(L / 32), the K axis is cut at k = L', 2 L', ... (< K): piece j = [j L', min((j + 1) L', K)) is its own fmaf chain
  *       from +0, t_0 = piece 0, t_j = fl32(t_{j-1} + piece j) in ascending order in registers, then + bias.  The cuts depend on (KH, KW, Cin, L) only.
  *     tile = 0: the planner picks (from M and Cout); 1: 128 x 128, 2: 128 x 64, 3: 64 x 64 (pixels x channels per workgroup).  No bit of the output

@@ -14,7 +14,7 @@ HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 OBJ = CSRC / "build"
 LIB = HERE / "libmedfusion_hip.so"
-SOURCES = ["api.hip", "conv.hip", "conv_f16x2.hip", "groupnorm.hip", "small_ops.hip", "sched_noise.hip", "attention.hip", "edge_ops.hip", "vq.hip", "conv3d.hip", "window_ops.hip", "metrics.hip", "fidelity.hip", "metrics3d.hip", "loss.hip", "guide.hip", "ingest.hip", "lpips.hip", "inception.hip"]
+SOURCES = ["api.hip", "conv.hip", "conv_f16x2.hip", "groupnorm.hip", "small_ops.hip", "sched_noise.hip", "attention.hip", "edge_ops.hip", "vq.hip", "conv3d.hip", "window_ops.hip", "metrics.hip", "fidelity.hip", "metrics3d.hip", "loss.hip", "guide.hip", "ingest.hip", "lpips.hip", "inception.hip", "cnn_layers.hip"]
 HEADERS = ["common.h", "philox.h", "gn_partial.h", "conv_igemm.h", "conv_f16x2.h", "conv_f16x2_body.inc", "conv_f16x2_halo.h", "conv_f16x2_halo_body.inc", "conv_f16x2_group.h", "conv_f16x2_epilogue.inc", "conv_plan.h", "split_f16.h", "conv_plan_table.inc", "winograd.h", "conv_f16x2_wino.inc", "wino_plan_table.inc"]
 # -packed-fp32-ops for conv_f16x2.hip.  gfx950 erratum, root-caused in round 3 (profiles/r03_pk_repro.txt, scripts/pk_repro_min.hip): a packed
 # fp32 instruction whose LOW result takes the HIGH half of src1 ("v_pk_mul_f32 vD, vA, vB op_sel:[0,1]") reads that operand as 0.0 in lanes
@@ -36,8 +36,9 @@ CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc",
 # loss.hip: the pooled target's sums and the variance terms are plain fp32 VALU work that hipcc packs with the failing operand selection: built the same way.
 # guide.hip: the guidance combine, the rescale multiply and the threshold's clamp / divide are plain fp32 VALU work of the same kind: built the same way.
 # ingest.hip: the value map's divide / subtract chain and the min-max apply are plain fp32 VALU work of the same kind: built the same way.
-# lpips.hip: the scaling layer's subtract / divide, the direct convolution's fma chain and the ReLU are plain fp32 VALU work of the same kind: built the same way.
-# inception.hip: the resize's interpolation, the pools' sums and the convolution's piece sums and epilogue are plain fp32 VALU work next to MFMAs and LDS reads: built the same way.
+# lpips.hip: the scaling layer's subtract / divide is plain fp32 VALU work of the same kind: built the same way.
+# inception.hip: the resize's interpolation is plain fp32 VALU work of the same kind: built the same way.
+# cnn_layers.hip: the pools' sums, the ReLU and the convolution's piece sums and epilogue are plain fp32 VALU work next to MFMAs and LDS reads: built the same way.
 EXTRA_CFLAGS = {"conv_f16x2.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                 "vq.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                 "conv3d.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
@@ -49,7 +50,8 @@ EXTRA_CFLAGS = {"conv_f16x2.hip": ["-Xclang", "-target-feature", "-Xclang", "-pa
                 "guide.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                 "ingest.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                 "lpips.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
-                "inception.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+                "inception.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+                "cnn_layers.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 LFLAGS = ["--offload-arch=gfx950", "-shared", "-fPIC", "-fno-gpu-rdc"]
 
 

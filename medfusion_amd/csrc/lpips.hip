@@ -1,6 +1,5 @@
-// lpips.hip -- LPIPS v0.1 on the device (include/medfusion_hip.h, "LPIPS"): the scaling layer, the plain layers of a pretrained-CNN trunk the
-// implicit-GEMM convolution does not take (a direct convolution, ReLU, max-pool) and the distance of two feature maps of a tap.
-// The direct convolution is deliberately simple: one thread per output value, one fp32 fma chain in (kh, kw, cin) order.  The distance is evaluated in
+// lpips.hip -- LPIPS v0.1 on the device (include/medfusion_hip.h, "LPIPS"): the scaling layer and the distance of two feature maps of a tap.  The
+// trunk's plain layers (mf_conv2d_direct_f32, mf_relu_f32, mf_maxpool_nhwc_f32) are the general layers of cnn_layers.hip.  The distance is evaluated in
 // fp64 on the fp32 features: channel sums and pixel sums in a fixed order, per-workgroup partials in a caller-supplied workspace, no atomics -- a pair's
 // bits depend on that pair's feature values only, not on the batch, the pair's place in it or the load path (metrics.hip's rule).
 #include "common.h"
@@ -37,71 +36,6 @@ __global__ __launch_bounds__(LANES) void lpips_prepare_kernel(const float* __res
     const float d = v - shift[c];
     out[i * 3 + c] = d / scale[c];
   }
-}
-
-// ---------------------------------------------------------------------------------------------- direct convolution, NHWC
-struct DirectP {
-  const float* x; const float* w; const float* bias; float* y;
-  int N, Hin, Win, Cin, Cout, KH, KW, stride, pad, Hout, Wout, relu;
-  long total;
-};
-
-// one thread per output value (pixel, cout), cout fastest: the lanes of a wave read one input value and consecutive weights ([KH][KW][Cin][Cout])
-__global__ __launch_bounds__(LANES) void conv_direct_nhwc_kernel(const DirectP p) {
-#pragma clang fp contract(off)
-  const long idx = (long)blockIdx.x * LANES + threadIdx.x;
-  if (idx >= p.total) return;
-  const int co = (int)(idx % p.Cout);
-  long r = idx / p.Cout;
-  const int wo = (int)(r % p.Wout);
-  r /= p.Wout;
-  const int ho = (int)(r % p.Hout);
-  const long n = r / p.Hout;
-  float acc = 0.f;
-  for (int kh = 0; kh < p.KH; ++kh) {
-    const int hi = ho * p.stride - p.pad + kh;
-    if (hi < 0 || hi >= p.Hin) continue;
-    for (int kw = 0; kw < p.KW; ++kw) {
-      const int wi = wo * p.stride - p.pad + kw;
-      if (wi < 0 || wi >= p.Win) continue;
-      const float* __restrict__ xp = p.x + ((n * p.Hin + hi) * p.Win + wi) * p.Cin;
-      const float* __restrict__ wp = p.w + (long)(kh * p.KW + kw) * p.Cin * p.Cout + co;
-      for (int ci = 0; ci < p.Cin; ++ci) acc = __builtin_fmaf(xp[ci], wp[(long)ci * p.Cout], acc);
-    }
-  }
-  if (p.bias) acc = acc + p.bias[co];
-  if (p.relu) acc = acc < 0.f ? 0.f : acc;
-  p.y[idx] = acc;
-}
-
-// ---------------------------------------------------------------------------------------------- ReLU in place, max-pool (floor mode, no padding)
-__global__ __launch_bounds__(LANES) void relu_kernel(float* __restrict__ x, long n, long nq) {
-  const long stride = (long)gridDim.x * LANES;
-  const long tid = (long)blockIdx.x * LANES + threadIdx.x;
-  for (long i = tid; i < nq; i += stride) {
-    float4 v = *reinterpret_cast<float4*>(x + i * 4);
-    v.x = v.x < 0.f ? 0.f : v.x, v.y = v.y < 0.f ? 0.f : v.y, v.z = v.z < 0.f ? 0.f : v.z, v.w = v.w < 0.f ? 0.f : v.w;
-    *reinterpret_cast<float4*>(x + i * 4) = v;
-  }
-  for (long i = nq * 4 + tid; i < n; i += stride) x[i] = x[i] < 0.f ? 0.f : x[i];
-}
-
-__global__ __launch_bounds__(LANES) void maxpool_nhwc_kernel(const float* __restrict__ x, float* __restrict__ y, int H, int W, int C, int Ho, int Wo, int k, int s, long total) {
-  const long idx = (long)blockIdx.x * LANES + threadIdx.x;
-  if (idx >= total) return;
-  const int c = (int)(idx % C);
-  long r = idx / C;
-  const int wo = (int)(r % Wo);
-  r /= Wo;
-  const int ho = (int)(r % Ho);
-  const long n = r / Ho;
-  float m = -INFINITY;
-  for (int dy = 0; dy < k; ++dy)
-    for (int dx = 0; dx < k; ++dx) {     // (floor mode: every window lies inside the image)
-      const float v = x[((n * H + ho * s + dy) * W + wo * s + dx) * C + c];
-      if (v > m || v != v) m = v;         // a NaN wins, as in F.max_pool2d
-    }
-  y[idx] = m;
 }
 
 // ---------------------------------------------------------------------------------------------- the distance of two feature maps of a tap
@@ -209,63 +143,6 @@ int mf_lpips_prepare_f32(const float* x, const float* y, float* out, int B, int 
   ProfScope ps(MF_FAM_MISC, s, 6.0 * total, 4.0 * total * (C + 3));
   MF_LAUNCH(lpips_prepare_kernel, dim3((unsigned)((total + LANES - 1) / LANES)), dim3(LANES), 0, s, x, y, out, B, C, HW, normalize ? 1 : 0, total);
   return check_launch("lpips_prepare");
-}
-
-int mf_conv2d_direct_out_dims(const MfDirectConvDesc* d, int32_t* out2) {
-  MF_REQUIRE(d && out2, MF_EINVAL, "conv2d_direct: null pointer");
-  MF_REQUIRE(d->N > 0 && d->Hin > 0 && d->Win > 0 && d->Cin > 0 && d->Cout > 0, MF_EINVAL, "conv2d_direct: bad dims");
-  MF_REQUIRE(d->KH >= 1 && d->KH <= 11 && d->KW >= 1 && d->KW <= 11, MF_EINVAL, "conv2d_direct: kernel %dx%d (1 .. 11)", d->KH, d->KW);
-  MF_REQUIRE(d->stride >= 1 && d->stride <= 4 && d->pad >= 0, MF_EINVAL, "conv2d_direct: stride %d (1 .. 4), pad %d", d->stride, d->pad);
-  MF_REQUIRE(d->reserved == 0, MF_EINVAL, "conv2d_direct: reserved must be 0");
-  const long ho = ((long)d->Hin + 2L * d->pad - d->KH) / d->stride + 1, wo = ((long)d->Win + 2L * d->pad - d->KW) / d->stride + 1;
-  MF_REQUIRE((long)d->Hin + 2L * d->pad >= d->KH && (long)d->Win + 2L * d->pad >= d->KW && ho > 0 && wo > 0 && ho < (1L << 30) && wo < (1L << 30), MF_EINVAL,
-             "conv2d_direct: empty output");
-  out2[0] = (int32_t)ho, out2[1] = (int32_t)wo;
-  return MF_OK;
-}
-
-int mf_conv2d_direct_f32(const float* x, const float* w_hwio, const float* bias, float* y, const MfDirectConvDesc* d, void* stream) {
-  int32_t hw[2];
-  const int rc = mf_conv2d_direct_out_dims(d, hw);
-  if (rc) return rc;
-  MF_REQUIRE(x && w_hwio && y, MF_EINVAL, "conv2d_direct: null pointer");
-  DirectP p;
-  p.x = x, p.w = w_hwio, p.bias = bias, p.y = y;
-  p.N = d->N, p.Hin = d->Hin, p.Win = d->Win, p.Cin = d->Cin, p.Cout = d->Cout, p.KH = d->KH, p.KW = d->KW, p.stride = d->stride, p.pad = d->pad;
-  p.Hout = hw[0], p.Wout = hw[1], p.relu = d->relu ? 1 : 0;
-  p.total = (long)d->N * hw[0] * hw[1] * d->Cout;
-  const long blocks = (p.total + LANES - 1) / LANES;
-  MF_REQUIRE(blocks < (1L << 31) && (long)d->N * d->Hin * d->Win * d->Cin < (1L << 40), MF_EUNSUPPORTED, "conv2d_direct: problem too large");
-  hipStream_t s = (hipStream_t)stream;
-  const double K = (double)d->KH * d->KW * d->Cin;
-  ProfScope ps(MF_FAM_CONV_DIRECT, s, 2.0 * p.total * K, 4.0 * ((double)d->N * d->Hin * d->Win * d->Cin + K * d->Cout + (double)p.total));
-  MF_LAUNCH(conv_direct_nhwc_kernel, dim3((unsigned)blocks), dim3(LANES), 0, s, p);
-  return check_launch("conv2d_direct");
-}
-
-int mf_relu_f32(float* x, int64_t n, void* stream) {
-  MF_REQUIRE(x && n > 0, MF_EINVAL, "relu: bad args");
-  const long nq = ((uintptr_t)x & 15) == 0 ? (long)n / 4 : 0;
-  long blocks = ((nq ? nq : (long)n) + LANES - 1) / LANES;
-  if (blocks > 4096) blocks = 4096;
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(MF_FAM_MISC, s, (double)n, 8.0 * n);
-  MF_LAUNCH(relu_kernel, dim3((unsigned)blocks), dim3(LANES), 0, s, x, (long)n, nq);
-  return check_launch("relu");
-}
-
-int mf_maxpool_nhwc_f32(const float* x, float* y, int N, int H, int W, int C, int k, int stride, void* stream) {
-  MF_REQUIRE(x && y, MF_EINVAL, "maxpool: null pointer");
-  MF_REQUIRE((k == 2 && stride == 2) || (k == 3 && stride == 2), MF_EINVAL, "maxpool: window %d stride %d ((2, 2) or (3, 2))", k, stride);
-  MF_REQUIRE(N > 0 && C > 0 && H >= k && W >= k, MF_EINVAL, "maxpool: bad dims (sides of at least the window)");
-  const int Ho = (H - k) / stride + 1, Wo = (W - k) / stride + 1;
-  const long total = (long)N * Ho * Wo * C;
-  const long blocks = (total + LANES - 1) / LANES;
-  MF_REQUIRE(blocks < (1L << 31), MF_EUNSUPPORTED, "maxpool: problem too large");
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(MF_FAM_MISC, s, (double)total * k * k, 4.0 * ((double)N * H * W * C + (double)total));
-  MF_LAUNCH(maxpool_nhwc_kernel, dim3((unsigned)blocks), dim3(LANES), 0, s, x, y, H, W, C, Ho, Wo, k, stride, total);
-  return check_launch("maxpool");
 }
 
 int mf_lpips_layer_parts(int64_t P) { return P > 0 ? layer_parts((long)P) : 0; }

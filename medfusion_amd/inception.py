@@ -1,5 +1,5 @@
 """The FID variant of Inception-v3 on the device: the 2048-wide pool features behind FID, precision / recall and the Inception Score, from
-user-supplied weights (csrc/inception.hip, include/medfusion_hip.h "Inception"; README "Inception features" has the definition).
+user-supplied weights (csrc/inception.hip, the general layers of csrc/cnn_layers.hip, include/medfusion_hip.h "Inception"; README "Inception features" has the definition).
 
 Nothing pretrained is shipped or fetched.  InceptionNet.from_file takes the file a reference run already has on disk -- torch-fidelity's
 pt_inception-2015-12-05-6726825d.pth, which torchmetrics' FID puts into the torch hub cache --, InceptionNet.seeded draws weights for tests and the

@@ -1,10 +1,11 @@
-"""LPIPS v0.1 on the device: the VGG16 / AlexNet trunks from user-supplied weights and the learned distance on top (csrc/lpips.hip,
-include/medfusion_hip.h "LPIPS"; README "LPIPS" has the definition).
+"""LPIPS v0.1 on the device: the VGG16 / AlexNet trunks from user-supplied weights and the learned distance on top (csrc/lpips.hip, the plain layers
+of csrc/cnn_layers.hip, include/medfusion_hip.h "LPIPS"; README "LPIPS" has the definition).
 
 Nothing pretrained is shipped or fetched.  LPIPSNet.from_files takes the two files anyone who trained with the reference has on disk -- the
 torchvision trunk state dict and the lpips package's linear-layer file --, LPIPSNet.seeded draws weights for tests and the benchmark.
 
-The first convolution of both trunks (Cin = 3) and AlexNet's 5 x 5 run on the direct kernel (mf_conv2d_direct_f32, bias and ReLU fused); every
+The first convolution of both trunks (Cin = 3) and AlexNet's 5 x 5 run on mf_conv2d_direct_f32 (the general fp32 matrix-core convolution
+of cnn_layers.hip with one fma chain per output, the one the Inception trunk runs; bias and ReLU fused; no bit depends on the tile it plans); every
 other 3 x 3 layer runs on the implicit-GEMM convolution mf_conv2d_f32 in one of its fp32-class arithmetics -- chosen HERE, per net, never through
 blocks.CONV_PRECISION -- followed by mf_relu_f32.  The tile and the split of the K loop of those layers are pinned by rules that look at the layer
 only, never at the batch, so a pair's bits do not depend on how many pairs travel with it: chunk=1 gives the bits of chunk=None.

@@ -18,24 +18,27 @@ PEAK_TF = 157.3
 
 
 def kernel_resources():
-    """VGPRs, LDS, scratch and spills of the kernels of inception.hip, from the device assembly the build's ISA lint keeps"""
+    """VGPRs, LDS, scratch and spills of the kernels of inception.hip and of the kernels of cnn_layers.hip the network runs (the convolution and the
+    window-3 pool), from the device assembly the build's ISA lint keeps"""
     from medfusion_amd import build as B
-    asm = B.OBJ / "lint" / "inception.s"
-    if not asm.exists() or asm.stat().st_mtime < (B.CSRC / "inception.hip").stat().st_mtime:
-        B.lint_isa()
     out, cur = [], {}
-    for line in asm.read_text().splitlines():
-        mt = re.match(r"\s*\.(name|vgpr_count|agpr_count|sgpr_count|private_segment_fixed_size|group_segment_fixed_size|sgpr_spill_count|vgpr_spill_count):\s*(\S+)", line)
-        if not mt:
-            continue
-        cur[mt.group(1)] = mt.group(2)
-        if mt.group(1) == "vgpr_spill_count":
-            name = re.sub(r"^_ZN\d+_GLOBAL__N_1\d+", "", cur.get("name", "?"))
-            args = re.findall(r"Li(\d+)E", name.split("Ev")[0])
-            short = re.match(r"[a-z0-9_]+kernel", name).group(0) + (f"<{', '.join(args)}>" if args else "")
-            out.append(f"{short:34s} vgpr {cur.get('vgpr_count'):>3s} (agpr {cur.get('agpr_count', '0'):>3s})  sgpr {cur.get('sgpr_count'):>3s}  lds {cur.get('group_segment_fixed_size'):>5s} B  "
-                       f"scratch {cur.get('private_segment_fixed_size')} B  spilled sgprs {cur.get('sgpr_spill_count')} vgprs {cur.get('vgpr_spill_count')}")
-            cur = {}
+    for unit, used in (("cnn_layers.hip", ("conv_gemm_kernel", "pool_nhwc_kernel<3>")), ("inception.hip", None)):
+        asm = B.OBJ / "lint" / (Path(unit).stem + ".s")
+        if not asm.exists() or asm.stat().st_mtime < (B.CSRC / unit).stat().st_mtime:
+            B.lint_isa()
+        for line in asm.read_text().splitlines():
+            mt = re.match(r"\s*\.(name|vgpr_count|agpr_count|sgpr_count|private_segment_fixed_size|group_segment_fixed_size|sgpr_spill_count|vgpr_spill_count):\s*(\S+)", line)
+            if not mt:
+                continue
+            cur[mt.group(1)] = mt.group(2)
+            if mt.group(1) == "vgpr_spill_count":
+                name = re.sub(r"^_ZN\d+_GLOBAL__N_1\d+", "", cur.get("name", "?"))
+                args = re.findall(r"Li(\d+)E", name.split("Ev")[0])
+                short = re.match(r"[a-z0-9_]+kernel", name).group(0) + (f"<{', '.join(args)}>" if args else "")
+                if used is None or any(short.startswith(u) for u in used):
+                    out.append(f"{short:34s} vgpr {cur.get('vgpr_count'):>3s} (agpr {cur.get('agpr_count', '0'):>3s})  sgpr {cur.get('sgpr_count'):>3s}  lds {cur.get('group_segment_fixed_size'):>5s} B  "
+                               f"scratch {cur.get('private_segment_fixed_size')} B  spilled sgprs {cur.get('sgpr_spill_count')} vgprs {cur.get('vgpr_spill_count')}")
+                cur = {}
     return out
 
 

@@ -16,28 +16,31 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 IMAGES = (100, 3, 256, 256)
 VOLUMES = (4, 1, 64, 128, 128)
 NETS = ("vgg", "alex")
+UNITS = ("lpips.hip", "cnn_layers.hip")
 SHIFT, SCALE = (-.030, -.088, -.188), (.458, .448, .450)
 
 
 def kernel_resources():
-    """VGPRs, LDS and scratch of the kernels of lpips.hip, from the device assembly the build's ISA lint keeps"""
+    """VGPRs, LDS and scratch of the kernels of lpips.hip and of the general layers of cnn_layers.hip (the trunk runs every one of them: the convolution
+    under mf_conv2d_direct_f32, both pool windows, the ReLU), from the device assembly the build's ISA lint keeps"""
     from medfusion_amd import build as B
-    asm = B.OBJ / "lint" / "lpips.s"
-    if not asm.exists() or asm.stat().st_mtime < (B.CSRC / "lpips.hip").stat().st_mtime:
-        B.lint_isa()
     out, cur = [], {}
-    for line in asm.read_text().splitlines():
-        mt = re.match(r"\s*\.(name|vgpr_count|sgpr_count|private_segment_fixed_size|group_segment_fixed_size|vgpr_spill_count):\s*(\S+)", line)
-        if not mt:
-            continue
-        cur[mt.group(1)] = mt.group(2)
-        if mt.group(1) == "vgpr_spill_count":
-            name = re.sub(r"^_ZN\d+_GLOBAL__N_1\d+", "", cur.get("name", "?"))
-            flags = ", ".join(("false", "true")[int(b)] for b in re.findall(r"Lb(\d)E", name.split("Ev")[0]))
-            short = re.match(r"[a-z0-9_]+kernel", name).group(0) + (f"<{flags}>" if flags else "")
-            out.append(f"{short:32s} vgpr {cur.get('vgpr_count'):>3s}  sgpr {cur.get('sgpr_count'):>3s}  lds {cur.get('group_segment_fixed_size'):>5s} B  "
-                       f"scratch {cur.get('private_segment_fixed_size')} B  spilled vgprs {cur.get('vgpr_spill_count')}")
-            cur = {}
+    for unit in UNITS:
+        asm = B.OBJ / "lint" / (Path(unit).stem + ".s")
+        if not asm.exists() or asm.stat().st_mtime < (B.CSRC / unit).stat().st_mtime:
+            B.lint_isa()
+        for line in asm.read_text().splitlines():
+            mt = re.match(r"\s*\.(name|vgpr_count|sgpr_count|private_segment_fixed_size|group_segment_fixed_size|vgpr_spill_count):\s*(\S+)", line)
+            if not mt:
+                continue
+            cur[mt.group(1)] = mt.group(2)
+            if mt.group(1) == "vgpr_spill_count":
+                name = re.sub(r"^_ZN\d+_GLOBAL__N_1\d+", "", cur.get("name", "?"))
+                flags = ", ".join(v if kind == "i" else ("false", "true")[int(v)] for kind, v in re.findall(r"L([bi])(\d+)E", name.split("Ev")[0]))
+                short = re.match(r"[a-z0-9_]+kernel", name).group(0) + (f"<{flags}>" if flags else "")
+                out.append(f"{short:32s} vgpr {cur.get('vgpr_count'):>3s}  sgpr {cur.get('sgpr_count'):>3s}  lds {cur.get('group_segment_fixed_size'):>5s} B  "
+                           f"scratch {cur.get('private_segment_fixed_size')} B  spilled vgprs {cur.get('vgpr_spill_count')}")
+                cur = {}
     return out
 
 
@@ -49,7 +52,7 @@ def plan_rows():
             p = LP.plan(net, h, w)
             direct = [l["key"] for l in p["layers"] if l["kernel"] == "mf_conv2d_direct_f32"]
             step = max(1, LP.PIXEL_BUDGET // (h * w))
-            rows.append(f"{net:4s} {label}: {p['launches']} launches per trunk pass, taps {p['taps']}, direct kernel on {direct}, distance workspace "
+            rows.append(f"{net:4s} {label}: {p['launches']} launches per trunk pass, taps {p['taps']}, mf_conv2d_direct_f32 on {direct}, distance workspace "
                         f"{p['workspace_bytes']} B per pair, {step} pairs per pass by default (largest activation {step * p['activation_bytes'] / 2 ** 20:.0f} MiB)")
     return rows
 
@@ -105,7 +108,7 @@ def main(argv=None):
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None, help="also write the lines to this file")
     args = ap.parse_args(argv)
-    lines = plan_rows() + ["kernels of lpips.hip (gfx950):"] + ["  " + r for r in kernel_resources()]
+    lines = plan_rows() + ["kernels of lpips.hip and cnn_layers.hip (gfx950):"] + ["  " + r for r in kernel_resources()]
     if not args.plan:
         import torch
         from medfusion_amd import lpips as LP

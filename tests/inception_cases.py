@@ -1,6 +1,10 @@
 """The Inception network of medfusion_amd.inception restated in plain torch (include/medfusion_hip.h "Inception" is the definition), and the shape
 lists of its tests.  Everything here runs on the CPU; the resize and the pools are restated operation by operation in fp32, so their results are the
-kernels' bits; the network is restated in a chosen dtype (fp64: the reference; fp32: the yardstick of the tolerance)."""
+kernels' bits; the convolution with one chain has an exact oracle (fma_chain_conv); the network is restated in a chosen dtype (fp64: the reference;
+fp32: the yardstick of the tolerance)."""
+import functools
+
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -37,6 +41,46 @@ def conv_case(case, seed=0):
     wt = torch.randn((kh, kw, cin, cout), generator=g) * (2.0 / (cin * kh * kw)) ** 0.5
     b = torch.randn((cout,), generator=g) * 0.1
     return x, wt, b, ((kh - 1) // 2 if padded else 0, (kw - 1) // 2 if padded else 0)
+
+
+def fma32(a, b, c):
+    """fp32 fma(a, b, c) of fp32 numpy arrays, exactly (finite data): the product of two fp32 values is exact in fp64; c is added in fp64 with the TwoSum
+    error term; where the error is non-zero and the sum's last mantissa bit is even the sum moves one fp64 step toward the error (round to odd: 53 bits
+    rounded to odd, then to 24, is one rounding to 24); then round to fp32.  Plain (double) a b + c rounded to fp32 rounds twice and is NOT this."""
+    p = a.astype(np.float64) * b.astype(np.float64)
+    c = c.astype(np.float64)
+    s = p + c
+    t = s - p
+    e = (p - (s - t)) + (c - t)
+    odd = (e != 0) & ((s.view(np.int64) & 1) == 0)
+    s = np.where(odd, np.nextafter(s, np.where(e > 0, np.inf, -np.inf)), s)
+    return s.astype(np.float32)
+
+
+def fma_chain_conv(x: torch.Tensor, w: torch.Tensor, pads, stride: int) -> torch.Tensor:
+    """The exact oracle of the convolution with one chain: x NHWC, w [KH][KW][Cin][Cout] -> fp32 NHWC, every output ONE fused multiply-add chain from +0
+    over k = (kh KW + kw) Cin + cin ascending, padding taps as zeros.  On the CPU, vectorised over the outputs and sequential over K.  The bias is one
+    fp32 add on top and ReLU is v < 0 ? 0 : v: derive those from this result."""
+    n, h, w_, cin = x.shape
+    kh_, kw_, _, cout = w.shape
+    ho, wo = (h + 2 * pads[0] - kh_) // stride + 1, (w_ + 2 * pads[1] - kw_) // stride + 1
+    xp = np.zeros((n, h + 2 * pads[0], w_ + 2 * pads[1], cin), dtype=np.float32)
+    xp[:, pads[0]:pads[0] + h, pads[1]:pads[1] + w_] = x.numpy()
+    wn = w.numpy()
+    acc = np.zeros((n, ho, wo, cout), dtype=np.float32)
+    for kh in range(kh_):
+        for kw in range(kw_):
+            tap = xp[:, kh:kh + (ho - 1) * stride + 1:stride, kw:kw + (wo - 1) * stride + 1:stride]
+            for ci in range(cin):
+                acc = fma32(tap[..., ci:ci + 1], wn[kh, kw, ci], acc)
+    return torch.from_numpy(acc)
+
+
+@functools.lru_cache(maxsize=None)
+def conv_oracle(case) -> torch.Tensor:
+    """fma_chain_conv of conv_case(case) without the bias, computed once per case and never modified"""
+    x, w, _, pads = conv_case(case)
+    return fma_chain_conv(x, w, pads, case[3])
 
 
 def prepare_ref(x: torch.Tensor, size: int) -> torch.Tensor:

@@ -7,6 +7,7 @@ import math
 import re
 from pathlib import Path
 
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -206,6 +207,7 @@ def test_the_entry_points_are_declared_exported_bound_wrapped_and_documented():
     assert C.sizeof(L.MfGemmConvDesc) == 16 * 4 and "#define MF_VERSION 250" in hdr
     from medfusion_amd import build as B
     assert "inception.hip" in B.SOURCES and "-packed-fp32-ops" in B.EXTRA_CFLAGS["inception.hip"]
+    assert "cnn_layers.hip" in B.SOURCES and "-packed-fp32-ops" in B.EXTRA_CFLAGS["cnn_layers.hip"]
     assert (L.POOL_MAX, L.POOL_AVG_VALID, L.INCEPTION_MIN_SIZE) == tuple(int(re.search(rf"#define {n} (\d+)", hdr).group(1)) for n in ("MF_POOL_MAX", "MF_POOL_AVG_VALID", "MF_INCEPTION_MIN_SIZE"))
 
 
@@ -263,6 +265,32 @@ def test_average_pool_of_the_restatement_against_torch():
     print(f"[measured] average pool restatement == F.avg_pool2d(count_include_pad=False) bit for bit: {agree}")
     x64 = torch.randn((1, 2, 6, 6), generator=g, dtype=torch.float64)
     assert torch.allclose(IC.pool_ref(x64, 1, 1, L.POOL_AVG_VALID), F.avg_pool2d(x64, 3, 1, 1, count_include_pad=False), rtol=1e-14, atol=0)
+
+
+def test_the_single_fma_of_the_oracle_on_a_double_rounding_case():
+    """a = 1 + 2^-10, b = 2^-24 (1 - 2^-10 + 2^-20), c = 1: a b = 2^-24 + 2^-54, so a b + c lies just above the fp32 tie 1 + 2^-24 and the fma is
+    1 + 2^-23; fp64 rounds the sum to the tie itself and the second rounding, to fp32, takes it to the even neighbour 1.0"""
+    a, b, c = np.float32(1 + 2.0 ** -10), np.float32(2.0 ** -24 * (1 - 2.0 ** -10 + 2.0 ** -20)), np.float32(1.0)
+    assert float(a) == 1 + 2.0 ** -10 and float(b) == 2.0 ** -24 * (1 - 2.0 ** -10 + 2.0 ** -20)               # both are fp32 values
+    for sign in (1.0, -1.0):
+        x, z = np.array([sign * a], dtype=np.float32), np.array([sign * c], dtype=np.float32)
+        assert float(IC.fma32(x, np.array([b]), z)[0]) == sign * (1 + 2.0 ** -23)
+        assert float(np.float32(np.float64(x[0]) * np.float64(b) + np.float64(z[0]))) == sign * 1.0
+    exact = np.array([1.5, -2.0, 0.0], dtype=np.float32)                                                       # no rounding at all: the plain value
+    assert IC.fma32(exact, exact, exact).tolist() == [3.75, 2.0, 0.0]
+
+
+def test_the_exact_convolution_oracle_sits_inside_the_fp64_bound():
+    """fma_chain_conv against fp64 F.conv2d on every CONV_SHAPES case: |y - y64| <= (K + 2) 2^-24 sum |w||x|, the bound the device is held to"""
+    for case in IC.CONV_SHAPES:
+        x, w, _, pads = IC.conv_case(case)
+        got = IC.conv_oracle(case)
+        x64, w64 = x.permute(0, 3, 1, 2).double(), w.permute(3, 2, 0, 1).double()
+        y64 = F.conv2d(x64, w64, None, stride=case[3], padding=pads).permute(0, 2, 3, 1)
+        mag = F.conv2d(x64.abs(), w64.abs(), None, stride=case[3], padding=pads).permute(0, 2, 3, 1)
+        kk = case[0] * case[2][0] * case[2][1]
+        assert got.dtype == torch.float32 and got.shape == y64.shape
+        assert float(((got.double() - y64).abs() / ((kk + 2) * 2.0 ** -24 * mag)).max()) <= 1.0, case
 
 
 def test_prepare_restatement_is_the_identity_at_the_networks_size():

@@ -1,5 +1,5 @@
 """The Inception network on the device against the restatement of tests/inception_cases.py: the tiled implicit-GEMM convolution alone (equal to the
-direct kernel, inside the derived element bound, the same bits whatever the tile / batch / slice), the pools, the resize and the pixel mean, the whole
+exact fma-chain oracle, inside the derived element bound, the same bits whatever the tile / batch / slice), the pools, the resize and the pixel mean, the whole
 network on seeded weights against fp64, its invariances, and the meter on top.
 
 Measured on one MI355X (profiles/inception_parity_measured.txt has every row): the convolution's worst element sits at 0.014 of its derived bound;
@@ -37,26 +37,19 @@ def _gemm(xd, wd, bd, pads, stride, relu=False, chain=0, tile=0, ldy=0, y_offset
     return K.conv2d_gemm(xd, wd, bd, d, out=out)
 
 
-def _direct(xd, wd, bd, pads, stride, relu):
-    """mf_conv2d_direct_f32 has one padding for both axes: run it with the larger one and cut the rows / columns of the smaller out (stride 1 there)"""
-    n, h, w, cin = xd.shape
-    kh, kw, _, cout = wd.shape
-    p = max(pads)
-    assert pads[0] == pads[1] or stride == 1
-    y = K.conv2d_direct(xd, wd, bd, K.make_direct_conv_desc(n, h, w, cin, cout, kh, kw, stride, p, relu=relu))
-    ho, wo = h + 2 * pads[0] - kh + 1, w + 2 * pads[1] - kw + 1
-    return y if pads[0] == pads[1] else y[:, p - pads[0]:p - pads[0] + ho, p - pads[1]:p - pads[1] + wo]
-
-
 # ------------------------------------------------------------------------------------------------ 1. the convolution alone
 @pytest.mark.parametrize("case", IC.CONV_SHAPES, ids=IC.CONV_IDS)
 def test_gemm_convolution_chain0_equals_the_direct_kernel(dev, case):
+    """chain = 0 against the exact CPU oracle (one fma chain per output, IC.fma_chain_conv), bit for bit: mf_conv2d_direct_f32 is this kernel now, so
+    the oracle holds both; the bias is one fp32 add on the chain and ReLU is v < 0 ? 0 : v"""
     x, w, b, pads = IC.conv_case(case)
     xd, wd, bd = x.to(dev), w.to(dev), b.to(dev)
+    chain = IC.conv_oracle(case)
     for relu in (False, True):
         for bias in (bd, None):
-            got = _gemm(xd, wd, bias, pads, case[3], relu=relu)
-            want = _direct(xd, wd, bias, pads, case[3], relu)
+            got = _gemm(xd, wd, bias, pads, case[3], relu=relu).cpu()
+            want = chain if bias is None else chain + b
+            want = torch.where(want < 0, torch.zeros_like(want), want) if relu else want
             assert got.shape == want.shape and torch.equal(got, want), (relu, bias is not None, int((got != want).sum()))
 
 

@@ -13,6 +13,7 @@ from medfusion_amd import kernels as K
 from medfusion_amd import lpips as LP
 from oracle import restate as R
 from oracle import synth as S
+from tests import inception_cases as IC
 from tests import lpips_cases as LC
 
 pytestmark = pytest.mark.gpu
@@ -42,6 +43,9 @@ def test_direct_convolution(dev, case):
     nobias = K.conv2d_direct(xd, wd, None, K.make_direct_conv_desc(n, h, w_, cin, cout, k, k, s, p))
     want = F.conv2d(x.permute(0, 3, 1, 2).double(), w.double(), None, stride=s, padding=p).permute(0, 2, 3, 1)
     assert float(((nobias.cpu().double() - want).abs() / bound).max()) <= 1.0
+    # the exact oracle: one fma chain per output from +0 over (kh, kw, cin) ascending, padding taps as zeros; then one fp32 add of the bias
+    chain = IC.fma_chain_conv(x, w.permute(2, 3, 1, 0).contiguous(), (p, p), s)
+    assert torch.equal(nobias.cpu(), chain) and torch.equal(plain.cpu(), chain + b)
 
 
 # ------------------------------------------------------------------------------------------------ 2. pooling and ReLU
